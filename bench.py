@@ -2,7 +2,7 @@
 """bench.py -- the hot path of BASELINE.json on MI355X: rasterizer forward + backward (+ the caller's
 activation / Adam step that BASELINE config C3 names) on synthetic data.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3|C2|C1]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3|C2|C1] [--full] [--dump-outputs DIR]
 
 One STEP = one optimiser iteration over one 1920x1080 view per GPU of the C3 scene (2 M Gaussians, seed 3,
 SH degree 0 -- the product setting): activations (sigmoid / exp / normalize / cat)
@@ -21,14 +21,23 @@ that really ran.  Rank r renders view r of the same scene (yaw offsets of SURVEY
 reported as `broadcast_ms`), then every rank runs the full step on its own view with no collective per step (the path
 has no exchange step).  --sync-mode allreduce sums the per-view gradients with one all-reduce of the flat gradient
 buffer (112 MB at M = 1) per step and every rank applies the identical Adam step to its replica (SURVEY.md 8(e));
---sync-mode owner = reduce to rank 0 + parameter broadcast.  With N > 1 the default run times `scatter` (the headline
+--sync-mode owner = reduce to rank 0 + parameter broadcast.  With N > 1, --full times `scatter` (the headline
 `value`) AND `allreduce` back to back and reports both under "sync_modes" on the one JSON line.  The rasterizer itself
 never communicates.  scaling = "weak".
 
-Extra objects on the JSON line: "roofline" (dominant kernel: its bound, the live hipEvent-measured launch time over
-the timed region, algorithmic bytes vs 8 TB/s under "hbm", VALU issue rate where the kernel is VALU-bound),
-"cpu_baseline" (the CPU oracle on the same workload, host cores, rank 0 at N = 1 only), "kernels" (per-kernel ms per
-step), "whole_path", "workload_stats" (measured P_vis, R, list lengths) and "work_units".
+A plain run sets up, warms up, times exactly K steps, writes --dump-outputs if asked and prints the line.  --full
+adds what takes runs of its own: an untimed survey pass with hipEvents around every kernel before the timed region,
+events around the dominant kernel inside it, one extra forward for the workload statistics, the CPU oracle, and at
+N > 1 the `allreduce` run after `scatter`.  Extra objects on a --full line: "roofline" (dominant kernel: its bound,
+the live hipEvent-measured launch time over the timed region, algorithmic bytes vs 8 TB/s under "hbm", VALU issue
+rate where the kernel is VALU-bound), "cpu_baseline" (the CPU oracle on the same workload, host cores, rank 0 at
+N = 1 only), "kernels" (per-kernel ms per step), "whole_path", "workload_stats" (measured P_vis, R, list lengths) and
+"work_units".
+
+--dump-outputs DIR (rank 0): what the last timed step handed its caller, as DIR/<name>.npy in float32 -- per view the
+rendered colour, depth and accumulated alpha (a seeded pixel sample when the images of all views exceed the budget)
+and the radii, and, when the step ran Adam, the updated pre-activation parameters; every per-Gaussian array at the
+same seeded sample of 65 536 Gaussians.  At most 64 MB in all.  The inputs depend on the arguments only.
 """
 import argparse
 import json
@@ -126,7 +135,8 @@ def parse_args():
                          "step replicated Adam (one 56 B/Gaussian collective per step); 'owner' = reduce to rank 0, "
                          "Adam there, broadcast the parameters (two collectives per step)")
     ap.add_argument("--single-sync-mode", action="store_true",
-                    help="N > 1: time only --sync-mode (default: 'scatter' is followed by an 'allreduce' run, both reported)")
+                    help="N > 1: time only --sync-mode (with --full, 'scatter' is otherwise followed by an 'allreduce' run, both "
+                         "reported)")
     ap.add_argument("--dist-backend", default="nccl", choices=("nccl", "gloo"),
                     help="gloo = rehearsal of the multi-rank control flow (collectives staged through the host)")
     ap.add_argument("--views-per-step", type=int, default=1,
@@ -155,7 +165,15 @@ def parse_args():
     ap.add_argument("--reference-rects", action="store_true",
                     help="bin with the reference's full 3-sigma tile squares (gsr_set_reference_rects(1)) instead of the "
                          "footprint-culled default: the reference's own instance count through the whole path")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel survey pass, roofline, workload statistics, CPU baseline and (N > 1) the "
+                         "allreduce run; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class _JsonLinesToStdout:
@@ -271,9 +289,10 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         return float(tt.item())
 
-    def run_mode(sync_mode, survey):
+    def run_mode(sync_mode, survey, dump_dir=None):
         """W warm-up steps, (survey: an untimed pass with hipEvents around every kernel,) then EXACTLY K timed steps
-        between barrier + synchronize pairs; returns the max-over-ranks time and what the stats need."""
+        between barrier + synchronize pairs (dump_dir: the last one's outputs written there); returns the
+        max-over-ranks time and what the stats need."""
         # ---- leaf parameters in one flat buffer (the "Gaussian buffer" of BASELINE C4), pre-activation ----
         params = MV.GaussianBuffer(P, M, dev)
         grads = MV.GaussianBuffer(P, M, dev)
@@ -361,9 +380,7 @@ def main():
             views = [rasters[(it * K + j) % len(rasters)] for j in range(K)] if rotate else [raster] * K
             if args.forward_only:
                 with torch.no_grad():
-                    for j, rv in enumerate(views):
-                        rv(xyz, sinks["t"][j], op, shs=shs, scales=sc, rotations=rot)
-                return
+                    return [rv(xyz, sinks["t"][j], op, shs=shs, scales=sc, rotations=rot) for j, rv in enumerate(views)]
             if workers is None:
                 outs = [rv(xyz, sinks["t"][j], op, shs=shs, scales=sc, rotations=rot) for j, rv in enumerate(views)]
             else:
@@ -395,6 +412,7 @@ def main():
             if not flat_grads:
                 for p in leaves.values():
                     p.grad = None
+            return outs
 
         for _ in range(args.warmup):
             step()
@@ -414,8 +432,10 @@ def main():
             G.profile_enable(True, only=[dom_name])
         spec0 = G.speculation_stats()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
+        for i in range(args.steps):
+            outs = step()
+            if i + 1 < args.steps:  # (only the last step's outputs stay alive, for --dump-outputs)
+                del outs
         barrier()
         elapsed = max_over_ranks(time.perf_counter() - t0)
         spec1 = G.speculation_stats()
@@ -427,6 +447,13 @@ def main():
         if survey:
             G.profile_enable(False)
             prof_timed = G.profile_read()
+        if dump_dir and rank == 0:
+            adam = not (args.no_adam or args.forward_only)
+            updated = {k: getattr(model, name) for k, name in (
+                ("means3D", "_xyz"), ("features_dc", "_features_dc"), ("features_rest", "_features_rest"),
+                ("scales", "_scaling"), ("rotations", "_rotation"), ("opacities", "_opacity"))} if adam else {}
+            dump_outputs(dump_dir, outs, updated)
+        del outs
         per_step = None
         if args.per_step:  # diagnostic pass, synchronised step by step (never part of `value`)
             per_step = []
@@ -455,113 +482,135 @@ def main():
                     grown=counter["grown"], P_end=int(model._xyz.shape[0]), collective_bytes_per_step=(
                         0 if not joint else params.nbytes() * (2 if owner_mode else 1)))
 
-    main_run = run_mode(args.sync_mode, survey=True)
-    elapsed, prof, prof_timed, dom_name = (main_run[k] for k in ("elapsed", "prof", "prof_timed", "dom_name"))
+    main_run = run_mode(args.sync_mode, survey=args.full, dump_dir=args.dump_outputs)
+    elapsed = main_run["elapsed"]
     activated, tail = main_run["activated"], main_run["tail"]
     P0, P = P, main_run["P_end"]  # (--grow-every: the statistics below describe the model as the run left it)
 
-    # ---- workload statistics from one direct forward with the current parameters ----
-    with torch.no_grad():
-        xyz, op, sc, rot, shs = [t.contiguous() for t in activated()]
-        e = torch.empty(0, device=dev)
-        fw = G.rasterize_forward(bg, xyz, e, op, sc, rot, 1.0, e, settings.viewmatrix, settings.projmatrix,
-                                 settings.tanfovx, settings.tanfovy, H, W, shs, D, settings.camera_center)
-        R, radii = fw[0], fw[4]
-        nf_split, nf_near, nf_far = G.last_near_far()  # was this frame binned near / far, and the two chains' instances
-        P_vis = int((radii > 0).sum())
-        v = G.state_views(fw[5], fw[6], fw[7], P, R, W, H)
-        ln = (v["ranges"][:, 1] - v["ranges"][:, 0]).float()
-        walk = v["quad_last"].long().max(1).values  # list entries the backward walks, per tile
-        R_bwd = int(walk.sum())
-        # instance count of the REFERENCE's binning (getRect on the 3-sigma radius, auxiliary.h:46-57) for the same
-        # frame: the footprint-box culling emits fewer
-        vis = radii > 0
-        px, py, rr = v["splats"][vis, 0], v["splats"][vis, 1], radii[vis].float()
-        gx, gy = (W + 15) // 16, (H + 15) // 16
-        x0 = ((px - rr) / 16).trunc().clamp(0, gx); x1 = ((px + rr + 15) / 16).trunc().clamp(0, gx)
-        y0 = ((py - rr) / 16).trunc().clamp(0, gy); y1 = ((py + rr + 15) / 16).trunc().clamp(0, gy)
-        R_ref = int(((x1 - x0) * (y1 - y0)).double().sum())
-        stats = dict(P=P, P_vis=P_vis, R=R, R_reference_binning=R_ref, R_walked_by_backward=R_bwd, tiles=int(ln.numel()),
-                     mean_tile_list=float(ln.mean()), max_tile_list=int(ln.max()),
-                     mean_contrib_per_pixel=float(v["n_contrib"].float().mean()),
-                     backward_walk_per_tile=dict(mean=float(walk.float().mean()), max=int(walk.max()),
-                                                 p50=int(walk.float().quantile(0.5)), p90=int(walk.float().quantile(0.9)),
-                                                 p99=int(walk.float().quantile(0.99))),
-                     binning="reference rectangles" if args.reference_rects else "footprint-culled (default)",
-                     near_far=dict(split=bool(nf_split), near_instances=nf_near, far_instances=nf_far))
-        del fw, v
-    tiles = stats["tiles"]
-    alg = algorithmic_bytes(P, P_vis, R, R_bwd, W, H, M, tiles)
-    kernels = {}
-    for name, (ms, cnt) in prof.items():
-        if cnt:
-            kernels[name] = dict(ms_per_step=ms / args.steps, launches_per_step=cnt / args.steps,
-                                 avg_launch_ms=ms / cnt,
-                                 alg_GBps=(alg.get(name, 0) / (ms / cnt * 1e-3) / 1e9) if ms > 0 else None)
-    dom = dom_name if alg.get(dom_name) else max((k for k in kernels if alg.get(k)),
-                                                 key=lambda k: kernels[k]["ms_per_step"])
-    if prof_timed.get(dom, (0, 0))[1]:  # the dominant kernel's duration over the TIMED region
-        ms, cnt = prof_timed[dom]
-        kernels[dom].update(ms_per_step=ms / args.steps, avg_launch_ms=ms / cnt,
-                            alg_GBps=alg[dom] / (ms / cnt * 1e-3) / 1e9)
-    launch_ms = kernels[dom]["avg_launch_ms"]
-    hbm_achieved = alg[dom] / (launch_ms * 1e-3) / 1e9
-    # Committed counter summaries (PMC collection cannot run inside a timed bench): used ONLY when they were taken
-    # on this workload with these flags (their "_meta"), otherwise the fields stay null.
-    this_meta = dict(workload=args.workload, sh_degree=D, loss=args.loss, forward_only=bool(args.forward_only),
-                     reference_rects=bool(args.reference_rects), n_gpus=n_gpus)
-    plain_run = K == 1 and not rotate and not args.grow_every and args.opacity_scale == 1.0 and not args.near_entries
+    def full_report(ms_per_step):
+        """--full: the fields the survey pass and one extra forward feed (roofline, kernels, workload_stats...)."""
+        prof, prof_timed, dom_name = (main_run[k] for k in ("prof", "prof_timed", "dom_name"))
+        # ---- workload statistics from one direct forward with the current parameters ----
+        with torch.no_grad():
+            xyz, op, sc, rot, shs = [t.contiguous() for t in activated()]
+            e = torch.empty(0, device=dev)
+            fw = G.rasterize_forward(bg, xyz, e, op, sc, rot, 1.0, e, settings.viewmatrix, settings.projmatrix,
+                                     settings.tanfovx, settings.tanfovy, H, W, shs, D, settings.camera_center)
+            R, radii = fw[0], fw[4]
+            nf_split, nf_near, nf_far = G.last_near_far()  # was this frame binned near / far, and the two chains' instances
+            P_vis = int((radii > 0).sum())
+            v = G.state_views(fw[5], fw[6], fw[7], P, R, W, H)
+            ln = (v["ranges"][:, 1] - v["ranges"][:, 0]).float()
+            walk = v["quad_last"].long().max(1).values  # list entries the backward walks, per tile
+            R_bwd = int(walk.sum())
+            # instance count of the REFERENCE's binning (getRect on the 3-sigma radius, auxiliary.h:46-57) for the same
+            # frame: the footprint-box culling emits fewer
+            vis = radii > 0
+            px, py, rr = v["splats"][vis, 0], v["splats"][vis, 1], radii[vis].float()
+            gx, gy = (W + 15) // 16, (H + 15) // 16
+            x0 = ((px - rr) / 16).trunc().clamp(0, gx); x1 = ((px + rr + 15) / 16).trunc().clamp(0, gx)
+            y0 = ((py - rr) / 16).trunc().clamp(0, gy); y1 = ((py + rr + 15) / 16).trunc().clamp(0, gy)
+            R_ref = int(((x1 - x0) * (y1 - y0)).double().sum())
+            stats = dict(P=P, P_vis=P_vis, R=R, R_reference_binning=R_ref, R_walked_by_backward=R_bwd, tiles=int(ln.numel()),
+                         mean_tile_list=float(ln.mean()), max_tile_list=int(ln.max()),
+                         mean_contrib_per_pixel=float(v["n_contrib"].float().mean()),
+                         backward_walk_per_tile=dict(mean=float(walk.float().mean()), max=int(walk.max()),
+                                                     p50=int(walk.float().quantile(0.5)), p90=int(walk.float().quantile(0.9)),
+                                                     p99=int(walk.float().quantile(0.99))),
+                         binning="reference rectangles" if args.reference_rects else "footprint-culled (default)",
+                         near_far=dict(split=bool(nf_split), near_instances=nf_near, far_instances=nf_far))
+            del fw, v
+        tiles = stats["tiles"]
+        alg = algorithmic_bytes(P, P_vis, R, R_bwd, W, H, M, tiles)
+        kernels = {}
+        for name, (ms, cnt) in prof.items():
+            if cnt:
+                kernels[name] = dict(ms_per_step=ms / args.steps, launches_per_step=cnt / args.steps,
+                                     avg_launch_ms=ms / cnt,
+                                     alg_GBps=(alg.get(name, 0) / (ms / cnt * 1e-3) / 1e9) if ms > 0 else None)
+        dom = dom_name if alg.get(dom_name) else max((k for k in kernels if alg.get(k)),
+                                                     key=lambda k: kernels[k]["ms_per_step"])
+        if prof_timed.get(dom, (0, 0))[1]:  # the dominant kernel's duration over the TIMED region
+            ms, cnt = prof_timed[dom]
+            kernels[dom].update(ms_per_step=ms / args.steps, avg_launch_ms=ms / cnt,
+                                alg_GBps=alg[dom] / (ms / cnt * 1e-3) / 1e9)
+        launch_ms = kernels[dom]["avg_launch_ms"]
+        hbm_achieved = alg[dom] / (launch_ms * 1e-3) / 1e9
+        # Committed counter summaries (PMC collection cannot run inside a timed bench): used ONLY when they were taken
+        # on this workload with these flags (their "_meta"), otherwise the fields stay null.
+        this_meta = dict(workload=args.workload, sh_degree=D, loss=args.loss, forward_only=bool(args.forward_only),
+                         reference_rects=bool(args.reference_rects), n_gpus=n_gpus)
+        plain_run = K == 1 and not rotate and not args.grow_every and args.opacity_scale == 1.0 and not args.near_entries
 
-    def committed(fname):
-        try:
-            with open(os.path.join(ROOT, "profiles", fname)) as fh:
-                d = json.load(fh)
-        except (OSError, ValueError):
-            return None
-        meta = d.get("_meta") or {}
-        return d if plain_run and all(meta.get(k) == val for k, val in this_meta.items()) else None
+        def committed(fname):
+            try:
+                with open(os.path.join(ROOT, "profiles", fname)) as fh:
+                    d = json.load(fh)
+            except (OSError, ValueError):
+                return None
+            meta = d.get("_meta") or {}
+            return d if plain_run and all(meta.get(k) == val for k, val in this_meta.items()) else None
 
-    def source_of(fname, d):
-        """Where a counter figure of this line comes from: PMC collection cannot run inside the timed bench, so these
-        are read from the committed summary of a counter pass over the same workload -- said so in the line."""
-        if not d:
-            return None
-        return "profiles/%s (%s; counter passes run with GSR_ASYNC_FAR=0: host-decided far chain)" % (
-            fname, (d.get("_meta") or {}).get("tag", "committed counter pass"))
+        def source_of(fname, d):
+            """Where a counter figure of this line comes from: PMC collection cannot run inside the timed bench, so these
+            are read from the committed summary of a counter pass over the same workload -- said so in the line."""
+            if not d:
+                return None
+            return "profiles/%s (%s; counter passes run with GSR_ASYNC_FAR=0: host-decided far chain)" % (
+                fname, (d.get("_meta") or {}).get("tag", "committed counter pass"))
 
-    pmc = committed("pmc_traffic_latest.json")
-    # device-side names behind one profiler id (the blend backward is one of two kernels, chosen by the tile count)
-    dev_names = {"k_blend_backward": ("k_blend_backward_tile", "k_blend_backward")}.get(dom, (dom,))
-    traffic = next(((pmc or {})[k].get("hbm_bytes_per_launch") for k in dev_names if k in (pmc or {})), None)
-    sq = committed("sq_counters_latest.json")
-    ent = next((val for name in dev_names for k, val in (sq or {}).items()
-                if k.split("<")[0] == name and isinstance(val, dict)), None)
-    hbm = dict(achieved=round(hbm_achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(hbm_achieved / HBM_PEAK_GBS, 4),
-               algorithmic_bytes_per_launch=int(alg[dom]))
-    valu_bound = dom in ("k_blend_backward", "k_blend_forward")  # DESIGN.md section 4: bound by VALU issue, not bytes
-    if valu_bound and ent and ent.get("SQ_INSTS_VALU"):
-        # VALU issue roofline: wave-instructions per launch (SQ_INSTS_VALU of the committed counter pass on this same
-        # workload) over the LIVE launch time, against one wave64 VALU op per 2 cycles per SIMD-32
-        ginst = ent["SQ_INSTS_VALU"] / (launch_ms * 1e-3) / 1e9
-        roofline = dict(kernel=dom, bound="valu", achieved=round(ginst, 1), peak=VALU_PEAK_GINST,
-                        unit="G wave-instr/s", frac=round(ginst / VALU_PEAK_GINST, 4), traffic=traffic,
-                        traffic_source=source_of("pmc_traffic_latest.json", pmc) if traffic else None,
-                        avg_launch_ms=round(launch_ms, 4), wave_instructions_per_launch=ent["SQ_INSTS_VALU"],
-                        wave_instructions_source=source_of("sq_counters_latest.json", sq),
-                        # the same against the rate MEASURED for plain f32 ops at 4-8 waves per SIMD
-                        # (tools/microbench/valu_rate.hip: v_fma / v_mul 3.0-3.3 cycles, v_add_f32_dpp 4.4-4.7, v_exp 8.3)
-                        frac_of_measured_3cycle_rate=round(ginst / (1024 * 2.4 / 3.0), 4), hbm=hbm)
-    else:
-        roofline = dict(kernel=dom, bound="hbm", achieved=hbm["achieved"], peak=HBM_PEAK_GBS, unit="GB/s",
-                        frac=hbm["frac"], traffic=traffic,
-                        traffic_source=source_of("pmc_traffic_latest.json", pmc) if traffic else None,
-                        avg_launch_ms=round(launch_ms, 4),
-                        algorithmic_bytes_per_launch=int(alg[dom]),
-                        note=("VALU-issue-bound kernel (DESIGN.md section 4); no counter summary committed for this "
-                              "workload, so only its HBM figure is given") if valu_bound else None)
-    # whole path: sum over kernels of (algorithmic bytes per launch x launches per step)
-    b_path = sum(alg.get(k, 0) * d["launches_per_step"] for k, d in kernels.items())
-    raster_ms = sum(k["ms_per_step"] for k in kernels.values())
+        pmc = committed("pmc_traffic_latest.json")
+        # device-side names behind one profiler id (the blend backward is one of two kernels, chosen by the tile count)
+        dev_names = {"k_blend_backward": ("k_blend_backward_tile", "k_blend_backward")}.get(dom, (dom,))
+        traffic = next(((pmc or {})[k].get("hbm_bytes_per_launch") for k in dev_names if k in (pmc or {})), None)
+        sq = committed("sq_counters_latest.json")
+        ent = next((val for name in dev_names for k, val in (sq or {}).items()
+                    if k.split("<")[0] == name and isinstance(val, dict)), None)
+        hbm = dict(achieved=round(hbm_achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(hbm_achieved / HBM_PEAK_GBS, 4),
+                   algorithmic_bytes_per_launch=int(alg[dom]))
+        valu_bound = dom in ("k_blend_backward", "k_blend_forward")  # DESIGN.md section 4: bound by VALU issue, not bytes
+        if valu_bound and ent and ent.get("SQ_INSTS_VALU"):
+            # VALU issue roofline: wave-instructions per launch (SQ_INSTS_VALU of the committed counter pass on this same
+            # workload) over the LIVE launch time, against one wave64 VALU op per 2 cycles per SIMD-32
+            ginst = ent["SQ_INSTS_VALU"] / (launch_ms * 1e-3) / 1e9
+            roofline = dict(kernel=dom, bound="valu", achieved=round(ginst, 1), peak=VALU_PEAK_GINST,
+                            unit="G wave-instr/s", frac=round(ginst / VALU_PEAK_GINST, 4), traffic=traffic,
+                            traffic_source=source_of("pmc_traffic_latest.json", pmc) if traffic else None,
+                            avg_launch_ms=round(launch_ms, 4), wave_instructions_per_launch=ent["SQ_INSTS_VALU"],
+                            wave_instructions_source=source_of("sq_counters_latest.json", sq),
+                            # the same against the rate MEASURED for plain f32 ops at 4-8 waves per SIMD
+                            # (tools/microbench/valu_rate.hip: v_fma / v_mul 3.0-3.3 cycles, v_add_f32_dpp 4.4-4.7, v_exp 8.3)
+                            frac_of_measured_3cycle_rate=round(ginst / (1024 * 2.4 / 3.0), 4), hbm=hbm)
+        else:
+            roofline = dict(kernel=dom, bound="hbm", achieved=hbm["achieved"], peak=HBM_PEAK_GBS, unit="GB/s",
+                            frac=hbm["frac"], traffic=traffic,
+                            traffic_source=source_of("pmc_traffic_latest.json", pmc) if traffic else None,
+                            avg_launch_ms=round(launch_ms, 4),
+                            algorithmic_bytes_per_launch=int(alg[dom]),
+                            note=("VALU-issue-bound kernel (DESIGN.md section 4); no counter summary committed for this "
+                                  "workload, so only its HBM figure is given") if valu_bound else None)
+        # whole path: sum over kernels of (algorithmic bytes per launch x launches per step)
+        b_path = sum(alg.get(k, 0) * d["launches_per_step"] for k, d in kernels.items())
+        raster_ms = sum(k["ms_per_step"] for k in kernels.values())
+        return {
+            "roofline": roofline,
+            "whole_path": {"kernel_ms_per_step": round(raster_ms, 4), "algorithmic_GB_per_step": round(b_path / 1e9, 3),
+                           "alg_GBps_over_kernel_time": round(b_path / (raster_ms * 1e-3) / 1e9, 1) if raster_ms else None},
+            "kernels": {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in d.items()}
+                        for k, d in sorted(kernels.items(), key=lambda kv: -kv[1]["ms_per_step"])},
+            "workload_stats": stats,
+            # SURVEY.md 8(d) work units: instances through the binning per second of step time, and (pixel, contributor)
+            # pairs per second of each blend kernel's own time (contributors = n_contrib summed over the image)
+            "work_units": {
+                "Minstances_per_s": round(stats["R"] / (ms_per_step * 1e-3) / 1e6, 1),
+                "Gpairs_per_s_blend_forward": (round(stats["mean_contrib_per_pixel"] * W * H /
+                                                     (kernels["k_blend_forward"]["avg_launch_ms"] * 1e-3) / 1e9, 2)
+                                               if "k_blend_forward" in kernels else None),
+                "Gpairs_per_s_blend_backward": (round(stats["mean_contrib_per_pixel"] * W * H /
+                                                      (kernels["k_blend_backward"]["avg_launch_ms"] * 1e-3) / 1e9, 2)
+                                                if "k_blend_backward" in kernels else None),
+            },
+        }
 
     ms_per_step = elapsed / args.steps * 1e3
     mpix = n_gpus * K * W * H * args.steps / elapsed / 1e6  # every rendered (and differentiated) view counts
@@ -595,26 +644,11 @@ def main():
         # scale in 1/256 of the configured entries per tile)
         "speculation": main_run["speculation"],
         "per_step": main_run["per_step"],
-        "roofline": roofline,
-        "whole_path": {"kernel_ms_per_step": round(raster_ms, 4), "algorithmic_GB_per_step": round(b_path / 1e9, 3),
-                       "alg_GBps_over_kernel_time": round(b_path / (raster_ms * 1e-3) / 1e9, 1) if raster_ms else None},
-        "kernels": {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in d.items()}
-                    for k, d in sorted(kernels.items(), key=lambda kv: -kv[1]["ms_per_step"])},
-        "workload_stats": stats,
-        # forwards whose instance count reached the host through the fallback stream query (0 in a healthy run)
-        "mailbox_slow_path_hits": int(G.lib().gsr_mailbox_slow_path_hits()),
-        # SURVEY.md 8(d) work units: instances through the binning per second of step time, and (pixel, contributor)
-        # pairs per second of each blend kernel's own time (contributors = n_contrib summed over the image)
-        "work_units": {
-            "Minstances_per_s": round(stats["R"] / (ms_per_step * 1e-3) / 1e6, 1),
-            "Gpairs_per_s_blend_forward": (round(stats["mean_contrib_per_pixel"] * W * H /
-                                                 (kernels["k_blend_forward"]["avg_launch_ms"] * 1e-3) / 1e9, 2)
-                                           if "k_blend_forward" in kernels else None),
-            "Gpairs_per_s_blend_backward": (round(stats["mean_contrib_per_pixel"] * W * H /
-                                                  (kernels["k_blend_backward"]["avg_launch_ms"] * 1e-3) / 1e9, 2)
-                                            if "k_blend_backward" in kernels else None),
-        },
     }
+    if args.full:
+        out.update(full_report(ms_per_step))
+    # forwards whose instance count reached the host through the fallback stream query (0 in a healthy run)
+    out["mailbox_slow_path_hits"] = int(G.lib().gsr_mailbox_slow_path_hits())
     if n_gpus > 1:
         def mode_line(r):
             ms = r["elapsed"] / args.steps * 1e3
@@ -623,18 +657,58 @@ def main():
                         broadcast_of_the_gaussian_buffer_ms=round(r["broadcast_ms"], 3),
                         gaussian_buffer_bytes=P * MV.floats_per_gaussian(M) * 4)
         out["sync_modes"] = {args.sync_mode: mode_line(main_run)}
-        if args.sync_mode == "scatter" and not (args.single_sync_mode or args.forward_only or args.no_adam):
+        if args.full and args.sync_mode == "scatter" and not (args.single_sync_mode or args.forward_only or args.no_adam):
             del main_run, activated
             torch.cuda.empty_cache()
             out["sync_modes"]["allreduce"] = mode_line(run_mode("allreduce", survey=False))
         out["dist_backend"] = args.dist_backend
 
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and not args.forward_only:
+    if args.full and rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and not args.forward_only:
         out["cpu_baseline"] = cpu_baseline(g, cam, dcol, dacc, W, H, D)
     if rank == 0:
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 63_000_000  # array data: with the .npy headers the files stay within 64 MB
+DUMP_GAUSSIANS = 65536
+DUMP_SEED = 20240917
+
+
+def dump_outputs(dirname, outs, params):
+    """--dump-outputs: outs = the last step's (color, radii, depth, acc) per view, params = name -> updated (P, ...)
+    leaf (empty without an Adam step).  Per-Gaussian arrays keep the same seeded sample of DUMP_GAUSSIANS Gaussians;
+    the images are whole unless all views together exceed what the budget leaves, then a seeded pixel sample
+    (C, n) of each.  The samples depend on the shapes only, so two runs with the same arguments compare row for row."""
+    P = int(outs[0][1].shape[0])
+    rng = np.random.default_rng(DUMP_SEED)
+    gidx = None if P <= DUMP_GAUSSIANS else np.sort(rng.choice(P, DUMP_GAUSSIANS, replace=False))
+    take = lambda t: t if gidx is None else t[torch.from_numpy(gidx).to(t.device)]  # noqa: E731
+    gauss = {k: take(v.detach()) for k, v in params.items() if v.numel()}
+    radii = [take(o[1].detach()) for o in outs]
+    g_bytes = 4 * (sum(t.numel() for t in gauss.values()) + sum(t.numel() for t in radii))
+    C, H, W = outs[0][0].shape
+    px_bytes = 4 * (C + 2) * len(outs)  # colour + depth + acc, every view
+    pidx = None
+    if px_bytes * H * W > DUMP_BUDGET_BYTES - g_bytes:
+        n = (DUMP_BUDGET_BYTES - g_bytes) // px_bytes
+        pidx = torch.from_numpy(np.sort(rng.choice(H * W, n, replace=False))).to(outs[0][0].device)
+    arrays = {}
+    for j, (color, _, depth, acc) in enumerate(outs):
+        sfx = "" if len(outs) == 1 else "_view%d" % j
+        for name, img in (("color", color), ("depth", depth), ("acc", acc)):
+            img = img.detach()
+            arrays[name + sfx] = img if pidx is None else img.reshape(img.shape[0], -1)[:, pidx]
+        arrays["radii" + sfx] = radii[j]
+    arrays.update(gauss)
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.float().cpu().numpy())
+        total += a.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    assert total <= DUMP_BUDGET_BYTES, total
 
 
 def cpu_baseline(g, cam, dcol, dacc, W, H, D):

@@ -97,15 +97,18 @@ def test_tile_culling_leaves_images_and_gradients_bit_identical(P, W, H, seed, D
 
 def test_small_matrix_helpers_match_the_references_glm():
     """oracle/_ref/check_glm is built from the reference's own vendored GLM (external/glm) and dumps mat3
-    products, dot products and lengths of LCG-random inputs; the oracle's restated helpers must reproduce them
-    bit for bit.  Skipped where neither /root/reference nor a prebuilt binary exists."""
+    products, dot products and lengths of LCG-random inputs; its output is stored in tests/golden/glm_check_n2000.npy
+    (tests/golden/make_golden_glm.py).  The oracle's restated helpers must reproduce it bit for bit; where the
+    binary can be built, its output must still be the stored one."""
     import ctypes as C
     import subprocess
-    exe = O.build_ref()
-    if exe is None:
-        pytest.skip("reference GLM not available and no prebuilt oracle/_ref/check_glm")
     n = 2000
-    ref = np.frombuffer(subprocess.check_output([exe, str(n)]), dtype=np.float32).reshape(n, 22)
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "glm_check_n%d.npy" % n))
+    assert ref.shape == (n, 22) and ref.dtype == np.float32
+    exe = O.build_ref()
+    if exe is not None:
+        live = np.frombuffer(subprocess.check_output([exe, str(n)]), dtype=np.float32).reshape(n, 22)
+        assert np.array_equal(live.view(np.uint32), ref.view(np.uint32))
     L = O.lib()
     for f in ("gsro_test_dot3", "gsro_test_dot4", "gsro_test_len3"):
         getattr(L, f).restype = C.c_float

@@ -13,7 +13,7 @@ out=gpurun_out/loop_$tag
 mkdir -p "$out"
 f="$out/${tag}_loop_sweep.jsonl"
 : > "$f"
-run() { python3 bench.py --no-cpu-baseline "$@" >> "$f" 2>> "$out/err.log"; echo "[loop_sweep] $* done"; }
+run() { python3 bench.py --full --no-cpu-baseline "$@" >> "$f" 2>> "$out/err.log"; echo "[loop_sweep] $* done"; }
 run
 run --views-per-step 3
 run --views-per-step 8 --per-step

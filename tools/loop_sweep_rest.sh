@@ -6,7 +6,7 @@ out=gpurun_out/loop_$tag
 mkdir -p "$out"
 f="$out/${tag}_loop_sweep_rest.jsonl"
 : > "$f"
-run() { python3 bench.py --no-cpu-baseline "$@" >> "$f" 2>> "$out/err_rest.log"; echo "[loop_sweep] $* done"; }
+run() { python3 bench.py --full --no-cpu-baseline "$@" >> "$f" 2>> "$out/err_rest.log"; echo "[loop_sweep] $* done"; }
 run --views-per-step 3 --view-threads 3
 run --rotate-views --per-step
 run --views-per-step 4 --grow-every 3 --per-step

@@ -3,9 +3,9 @@
 MI355X_MICROARCH.md "rocprofv3 PMC slots" requires: FETCH_SIZE costs 3 of the 4 TCC slots, WRITE_SIZE 2)
 into per-kernel HBM traffic per launch.
 
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d gpurun_out/pmc_fetch -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d gpurun_out/pmc_write -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    python tools/pmc_summary.py gpurun_out/pmc_fetch gpurun_out/pmc_write profiles/<name>.json
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d <out>/pmc_fetch -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d <out>/pmc_write -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    python tools/pmc_summary.py <out>/pmc_fetch <out>/pmc_write profiles/<name>.json
 
 Corrections (MI355X_MICROARCH.md, section HBM): the counters are in KiB; on gfx950 FETCH_SIZE reports
 exactly half of the bytes of a coalesced streaming read, so it is doubled.  Calibration in THIS access

@@ -8,7 +8,7 @@ out=gpurun_out/${tag}_shape_sweep.jsonl
 for flags in "--workload C1" "--workload C2" "--workload C2 --forward-only" "--workload C5shape" \
              "--workload C5shape --loss photometric" "--workload C3 --sh-degree 3" "--workload C3 --loss photometric" \
              "--workload C3"; do
-  python3 bench.py $flags --no-cpu-baseline >> "$out" 2>> gpurun_out/${tag}_shape_sweep.err
+  python3 bench.py --full $flags --no-cpu-baseline >> "$out" 2>> "${out%.jsonl}.err"
   echo "[shape_sweep] $flags done"
 done
 python3 - "$out" <<'PY'

@@ -15,7 +15,7 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA
            "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_BRANCH" \
            "SQ_THREAD_CYCLES_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_INST_LEVEL_LDS SQ_INST_LEVEL_VMEM SQ_ACCUM_PREV_HIRES SQ_WAVE_CYCLES"; do
   i=$((i + 1))
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d "$out/p$i" -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline \
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d "$out/p$i" -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline \
       > /dev/null 2> "$out/p$i.err" || echo "[sq_probe] pass $i failed (see $out/p$i.err)"
   echo "[sq_probe] pass $i done"
 done

@@ -2,8 +2,8 @@
 """Per-kernel SQ counter summary from one rocprofv3 --pmc run (own run, --kernel-trace only):
 
     rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_BUSY_CYCLES \
-        --output-format csv -d gpurun_out/pmc_sq -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-    python tools/sq_summary.py gpurun_out/pmc_sq profiles/<name>.json
+        --output-format csv -d <out>/pmc_sq -o run -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+    python tools/sq_summary.py <out>/pmc_sq profiles/<name>.json
 
 valu_issue_ms = wave-instructions x 2 cycles (wave64 on the SIMD-32 VALU, MI355X_MICROARCH.md) / (1024 SIMDs x 2.4 GHz):
 the time the kernel would need if VALU issue were the only limit."""
