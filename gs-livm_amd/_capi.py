@@ -61,7 +61,7 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_mark_visible", "gsr_geometry_byte
            "gsr_photometric_loss", "gsr_photometric_loss_workspace", "gsr_init_gaussians", "gsr_ply_row_floats",
            "gsr_pack_ply_rows", "gsr_model_step", "gsr_set_reference_rects", "gsr_reference_rects",
            "gsr_last_num_rendered", "gsr_set_binning_capacity_hint", "gsr_speculative_forwards",
-           "gsr_speculation_overflows", "gsr_mailbox_slow_path_last", "gsr_set_near_far", "gsr_near_far",
+           "gsr_speculation_overflows", "gsr_emit_guard_trips", "gsr_mailbox_slow_path_last", "gsr_set_near_far", "gsr_near_far",
            "gsr_last_near_far", "gsr_set_near_far_hints", "gsr_near_far_forwards", "gsr_set_far_speculation",
            "gsr_last_far_skipped", "gsr_far_skips", "gsr_far_skip_misses", "gsr_async_far_frames",
            "gsr_near_budget_scale", "gsr_near_budget_feedback", "gsr_near_far_pause", "gsr_set_near_far_thread",
@@ -113,7 +113,7 @@ def lib():
     L.gsr_last_num_rendered.argtypes = []
     L.gsr_set_binning_capacity_hint.restype = C.c_longlong
     L.gsr_set_binning_capacity_hint.argtypes = [C.c_longlong]
-    for n in ("gsr_speculative_forwards", "gsr_speculation_overflows"):
+    for n in ("gsr_speculative_forwards", "gsr_speculation_overflows", "gsr_emit_guard_trips"):
         getattr(L, n).restype = C.c_ulonglong
         getattr(L, n).argtypes = []
     L.gsr_set_near_far.restype = ci
@@ -300,6 +300,13 @@ def speculation_stats():
                 async_outcomes_lost=int(L.gsr_async_outcomes_lost()), frame_note_misses=int(L.gsr_frame_note_misses()),
                 near_budget_scale_q8=int(L.gsr_near_budget_scale()),
                 mailbox_slow_path_hits=int(L.gsr_mailbox_slow_path_hits()))
+
+
+def emit_guard_trips():
+    """Emit chunks whose chunk-table entries the emitters refused (include/gsraster.h, gsr_emit_guard_trips): 0 unless
+    binning has a defect.  Reads device memory, so -- unlike speculation_stats, which bench.py reads around its timed
+    region -- it waits for the work enqueued so far."""
+    return int(lib().gsr_emit_guard_trips())
 
 
 def mailbox_slow_path_last():

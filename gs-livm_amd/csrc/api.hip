@@ -1142,10 +1142,12 @@ int gsr_forward(gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn bi
           c.last_far_skipped = true;
           order_remember(iblob);
           R_far = 0;
-        } else if (async_far && live == 0u) {
+        } else if (async_far && live == 0u) {  // (an asynchronous frame whose far capacity was forced: scored here)
+          ++g_far_skips;
           R_far = 0;
           c.last_far_skipped = true;
         } else {
+          if (async_far) ++g_far_skip_misses;
           if (skip_far) {  // unfinished quads after all
             ++g_far_skip_misses;
             rc = enqueue_chain(fp, g, im, b, far_chain, c, dord, background, out_color, out_depth, out_acc, debug, stream);
@@ -1288,6 +1290,7 @@ long long gsr_set_binning_capacity_hint(long long capacity) {
 }
 unsigned long long gsr_speculative_forwards(void) { return g_speculative_forwards.load(); }
 unsigned long long gsr_speculation_overflows(void) { return g_speculation_overflows.load(); }
+unsigned long long gsr_emit_guard_trips(void) { return emit_guard_trips(); }
 int gsr_mailbox_slow_path_last(gsr_mailbox_event* out) {
   if (!out) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
   std::lock_guard<std::mutex> lk(g_slow_mu);

@@ -211,6 +211,12 @@ struct BinningState {
   SortScratch tsort;
   float4* grad_inst;     // [R][3], aliases tkeysA..tsort
   uint8_t* inst_flag;    // [R] 1 = grad_inst[slot] was written by the blend backward
+  // Invariant of both chunk tables (k_scan_offsets, k_scan_offsets_far; emit_stage relies on it): for every chunk e an
+  // emitter processes -- e * EMIT_CHUNK < min(count, capacity) -- THIS frame has written chunk_first[e] and
+  // chunk_first[e + 1], and both index descriptors this frame has written: [e] the Gaussian covering slot e*EMIT_CHUNK,
+  // [e + 1] the one covering slot (e+1)*EMIT_CHUNK or, for the last chunk, the one covering slot min(count, capacity)-1
+  // (whose successor's descriptor, or the sentinel, is written too).  The blob is not cleared: an entry this frame
+  // did not write holds whatever the memory held before.
   uint32_t* chunk_first; // [R/EMIT_CHUNK + 2] depth-order index of the Gaussian covering slot k*EMIT_CHUNK
   uint32_t* chunk_firstB; // [R/EMIT_CHUNK + 2] the same for the far phase of a near/far frame (index into sdescB)
   static BinningState carve(char* blob, size_t R, size_t* bytes = nullptr) {
@@ -314,6 +320,8 @@ hipError_t launch_scan_offsets_far(const FrameParams& fp, GeomState g, Count cap
                                    uint32_t ticket, hipStream_t s);
 // (digit_shift0 / digit_mask0: the digit of the tile sort's first pass, whose per-sort-tile counts the emitter leaves in
 // counts0 -- the low bits of the tile id for the LSD sort, its top eight bits for the bucket sort, see tile_sort_buckets)
+// chunks whose chunk-table entries emit_stage refused (gsr_emit_guard_trips; reads the current device's counter)
+unsigned long long emit_guard_trips();
 hipError_t launch_emit(const FrameParams& fp, const uint4* sdesc, Count R, uint32_t* chunk_first, uint32_t* tkeys_out,
                        uint32_t* ivals_out, uint8_t* inst_flag, uint32_t* counts0, uint32_t digit_shift0,
                        uint32_t digit_mask0, bool key16, bool store_pairs, hipStream_t s);

@@ -1071,7 +1071,10 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_scan_offsets_far(const FrameParam
     const uint32_t end_c = end < RB_cap ? end : RB_cap;
     for (uint32_t c = (off + EMIT_CHUNK - 1) / EMIT_CHUNK; (unsigned long long)c * EMIT_CHUNK < end_c; c++)
       chunk_firstB[c] = j;
-    if (off < RB_cap && end > RB_cap)  // overflowed frame: the emitters stop at the capacity, inside this run
+    // the run in which the emitters stop (the last slot below the capacity is its): in an overflowed frame the
+    // frame-end entry above is not written, so this one is the last chunk's upper bound -- also when the run ENDS
+    // exactly at the capacity (as k_scan_offsets: `end >= R`)
+    if (off < RB_cap && end >= RB_cap)
       chunk_firstB[(size_t)((RB_cap + EMIT_CHUNK - 1) / EMIT_CHUNK)] = j;
     run += (1ull << 32) | n[k];
   }
@@ -1082,13 +1085,32 @@ struct EmitStage {
   uint32_t s_off[EMIT_CHUNK + 2], s_id[EMIT_CHUNK + 1], s_rect[EMIT_CHUNK + 1], s_inv[EMIT_CHUNK + 1];
 };
 
-// descriptors of the Gaussians covering slots [c0, c1) of emit chunk `e` -> LDS; returns their count S
+// Chunks whose table entries broke the invariant of BinningState::chunk_first (gsr_emit_guard_trips): process-wide per
+// device, never reset.  Zero in every correct frame.
+__device__ unsigned long long g_emit_guard_trips;
+
+unsigned long long emit_guard_trips() {
+  unsigned long long v = 0;
+  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_emit_guard_trips), sizeof(v), 0, hipMemcpyDeviceToHost) != hipSuccess) return 0;
+  return v;
+}
+
+// descriptors of the Gaussians covering slots [c0, c1) of emit chunk `e` -> LDS; returns their count S.  The table
+// entries are checked before anything is read through them (the descriptor arrays have P + 1 entries): a chunk whose
+// entries are not a valid range stages nothing, returns 0 -- emit_walk8 then gives its slots (tile 0, Gaussian 0),
+// in-bounds garbage -- and counts a trip.
 __device__ __forceinline__ int emit_stage(const uint4* __restrict__ sdesc, const uint32_t* __restrict__ chunk_first, int e,
-                                          uint32_t c1, int R, int tid, EmitStage& st) {
+                                          uint32_t c1, int R, int P, int tid, EmitStage& st) {
   const int i0 = (int)chunk_first[e];
   int i1 = (int)chunk_first[e + 1];
-  if (c1 < (uint32_t)R && sdesc[i1].x >= c1) i1--;    // the Gaussian covering slot c1 starts exactly there
+  bool bad = i0 < 0 || i1 < i0 || i1 > P;
+  if (!bad && c1 < (uint32_t)R && sdesc[i1].x >= c1) i1--;  // the Gaussian covering slot c1 starts exactly there
   const int S = i1 - i0 + 1;                          // <= EMIT_CHUNK + 1: every staged Gaussian owns >= 1 slot
+  bad = bad || S < 1 || S > EMIT_CHUNK + 1 || i1 >= P;  // (workgroup-uniform; staging reads sdesc[i0 .. i1 + 1])
+  if (bad) {
+    if (tid == 0) atomicAdd(&g_emit_guard_trips, 1ull);
+    return 0;
+  }
   for (int j = tid; j <= S; j += 256) {               // s_off[S] = start of the first run beyond this chunk
     const uint4 d = sdesc[i0 + j];                    // (the descriptor arrays have P + 1 entries)
     st.s_off[j] = d.x;
@@ -1104,6 +1126,11 @@ __device__ __forceinline__ int emit_stage(const uint4* __restrict__ sdesc, const
 // (tile id, Gaussian id) of the eight slots [t0, t0 + 8); those >= c1 are meaningless
 __device__ __forceinline__ void emit_walk8(uint32_t t0, uint32_t c1, int S, const EmitStage& st, uint32_t gx,
                                            uint32_t tk[8], uint32_t iv[8]) {
+  if (S == 0) {  // (emit_stage refused the chunk's table entries)
+#pragma unroll
+    for (int k = 0; k < 8; k++) { tk[k] = 0u; iv[k] = 0u; }
+    return;
+  }
   int lo = 0, hi = S - 1;  // largest j with s_off[j] <= t0
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -1162,7 +1189,7 @@ __global__ __launch_bounds__(256) void k_emit_scatter(const FrameParams fp, cons
     const bool live = c0 < (uint32_t)R;  // workgroup-uniform
     const uint32_t c1 = c0 + EMIT_CHUNK < (uint32_t)R ? c0 + EMIT_CHUNK : (uint32_t)R;
     int S = 0;
-    if (live) S = emit_stage(sdesc, chunk_first, e, c1, R, tid, sm.st);
+    if (live) S = emit_stage(sdesc, chunk_first, e, c1, R, fp.P, tid, sm.st);
     __syncthreads();
     const uint32_t t0 = c0 + (uint32_t)tid * 8u;
     if (live && t0 < c1) emit_walk8(t0, c1, S, sm.st, (uint32_t)fp.gx, tk[r], iv[r]);
@@ -1217,7 +1244,7 @@ __global__ __launch_bounds__(256) void k_emit(const FrameParams fp, const uint4*
   hist[tid] = 0;
   const uint32_t c0 = (uint32_t)chunk * EMIT_CHUNK;
   const uint32_t c1 = c0 + EMIT_CHUNK < (uint32_t)R ? c0 + EMIT_CHUNK : (uint32_t)R;
-  const int S = emit_stage(sdesc, chunk_first, chunk, c1, R, tid, st);
+  const int S = emit_stage(sdesc, chunk_first, chunk, c1, R, fp.P, tid, st);
   __syncthreads();
   // Each thread owns EIGHT consecutive slots: one bisection for the first, then it walks (row, col) and steps to
   // the next Gaussian when a run ends -- 4x fewer LDS round trips than a search per slot, 32-byte stores.

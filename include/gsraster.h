@@ -86,6 +86,11 @@ int gsr_last_num_rendered(void);
 long long gsr_set_binning_capacity_hint(long long capacity);
 unsigned long long gsr_speculative_forwards(void);  /* process-wide counters */
 unsigned long long gsr_speculation_overflows(void);
+/* Emit chunks whose chunk-table entries the emitters refused (not a valid descriptor range: the chunk's slots are
+ * emitted as tile 0 / Gaussian 0 instead of reading out of bounds).  Zero unless binning has a defect.  Process-wide
+ * count of the CURRENT device, never reset; unlike the counters above it reads device memory and so waits for the
+ * work already enqueued on the null stream. */
+unsigned long long gsr_emit_guard_trips(void);
 
 /* Near/far frames.  A tile's list is depth-ordered and a pixel stops reading it once its transmittance
  * is below 1e-4 (forward.cu:380-383); in dense scenes every tile is finished after a few per cent of

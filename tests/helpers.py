@@ -3,6 +3,7 @@ import numpy as np
 import torch
 
 import gs_livm_amd as G
+from gs_livm_amd import synthetic as S
 
 
 def to_dev(scene, dev):
@@ -95,3 +96,65 @@ def conic_condition(conic_opacity):
     with np.errstate(divide="ignore", invalid="ignore"):
         k = np.where(lo > 0, (mid + disc) / lo, np.inf)
     return np.where(np.isfinite(k), k, 1e6)
+
+
+def check_near_far_against_one_chain(sc, dev, near_entries, far_capacity=None, expect_redo=False, speculate_far=None):
+    """One scene binned in one chain (the reference's structure) and near/far: observable results bit-identical, lists
+    consistent (module docstring of include/gsraster.h, "Near/far frames")."""
+    P, W, H = sc["means3D"].shape[0], sc["W"], sc["H"]
+    G.set_binning_capacity_hint(0)
+    t0, one = hip_forward(sc, dev, debug=False)                     # synchronous, one chain
+    v1 = G.state_views(one[5], one[6], one[7], P, one[0], W, H)
+    assert not v1["near_far"]
+    assert torch.equal(v1["ranges_near"], v1["ranges"])             # one chain: the composed view is the raw one
+    dcol, dacc = S.make_upstream_grads(W, H, 5)
+    g1 = hip_backward(sc, t0, one, dcol, dacc, dev, debug=False)
+    before = G.speculation_stats()
+    G.set_near_far_hints(near_entries, far_capacity)
+    if speculate_far is not None:   # True: this forward enqueues its far chain only once it has seen live tiles
+        G.set_far_speculation(speculate_far)
+    t1, two = hip_forward(sc, dev, debug=False, near_far=True)      # speculative, near/far
+    for i, (x, y) in enumerate(zip(one[1:5], two[1:5])):
+        assert torch.equal(x, y), i                                 # colour, depth, silhouette, radii
+    # host-side figures only now that the frame has completed: an asynchronous frame (far-chain speculation on a second
+    # stream, include/gsraster.h) returns before its far chain's outcome is known and reports it once it is there
+    torch.cuda.synchronize()
+    far_skipped = G.last_far_skipped()
+    st = G.speculation_stats()
+    split, n_near, n_far = G.last_near_far()
+    assert st["overflows"] - before["overflows"] == (1 if expect_redo else 0)
+    assert split == (not expect_redo) and st["near_far_forwards"] == before["near_far_forwards"] + 1
+    v2 = G.state_views(two[5], two[6], two[7], P, two[0], W, H)
+    for k in ("n_contrib", "final_T", "quad_last", "tiles_touched"):
+        assert torch.equal(v1[k], v2[k]), k
+    g2 = hip_backward(sc, t1, two, dcol, dacc, dev, debug=False)
+    for k in g1:
+        assert np.array_equal(g1[k], g2[k]), k                      # every gradient, bit for bit
+    if expect_redo:
+        assert int(two[0]) == int(one[0]) and torch.equal(v1["point_list"], v2["point_list"])
+        return None
+    assert v2["near_far"] and G.last_num_rendered() == n_near + n_far == v2["num_rendered"] <= int(one[0])
+    assert int(two[0]) in (n_near, n_near + n_far)                  # (taken when the forward returned)
+    # lists: per tile the near/far list is the one-chain list with far entries removed only where the tile was finished
+    # by the near phase -- so its first max(n_contrib) entries, all that any pixel reads, are the same
+    r1, r2 = v1["ranges"].long().cpu().numpy(), v2["ranges"].long().cpu().numpy()
+    p1, p2 = v1["point_list"].cpu().numpy(), v2["point_list"].cpu().numpy()
+    need = v1["quad_last"].long().max(1).values.cpu().numpy()
+    rn, rf = v2["ranges_near"].long().cpu().numpy(), v2["ranges_far"].long().cpu().numpy()
+    live = ~(v2["counters"][9] == 0)
+    full_tiles = 0
+    for tidx in range(r1.shape[0]):
+        a, b = p1[r1[tidx, 0]:r1[tidx, 1]], p2[r2[tidx, 0]:r2[tidx, 1]]
+        assert len(b) <= len(a) and np.array_equal(a[:need[tidx]], b[:need[tidx]]), tidx
+        ln = rn[tidx, 1] - rn[tidx, 0]
+        assert np.array_equal(a[:ln], b[:ln])                       # the near segment is a prefix of the whole list
+        assert np.isin(b, a).all()
+        full_tiles += int(len(a) == len(b))
+    if speculate_far:   # completed without a far chain iff the near chain left no tile live
+        assert far_skipped == (v2["counters"][9] == 0)
+        assert st["far_skips"] - before["far_skips"] == int(far_skipped)
+        assert st["far_skip_misses"] - before["far_skip_misses"] == int(not far_skipped)
+    elif speculate_far is False:
+        assert not far_skipped and st["far_skips"] == before["far_skips"]
+    return dict(near=n_near, far=n_far, one=int(one[0]), live_tiles=v2["counters"][9], full_tiles=full_tiles,
+                tiles=r1.shape[0], far_skipped=far_skipped)
