@@ -2,13 +2,13 @@
 // stage sequencing.  Restates the ORCHESTRATION of CudaRasterizer::Rasterizer::forward / backward
 // (reference rasterizer_impl.cu:181-342, :346-457); all device work is in the sibling .hip files.
 //
-// How a forward is sequenced (gsr_forward):
-//   synchronous  (a thread's first, debug, GSR_SYNC_FORWARD)  k_preprocess + depth sort, host waits for num_rendered
-//                (mailbox), exact binning blob, one binning chain (enqueue_chain) + blend;
-//   speculative  blob sized from the thread's recent frames, everything enqueued at once, counts read on the device,
-//                the mailbox read after the last enqueue; overflow -> the chain is enqueued again with the exact size;
-//   near / far   (dense frames) two chains over the Gaussians in depth order -- near up to a budget, then only the far
-//                Gaussians whose rectangle still holds an unfinished tile;
+// How a forward is sequenced (gsr_forward; plan_frame picks the kind of frame, enqueue_chain enqueues one chain):
+//   synchronous  (sync_frame: a thread's first, debug, GSR_SYNC_FORWARD)  k_preprocess + depth sort, host waits for
+//                num_rendered (mailbox), exact binning blob, one binning chain + blend;
+//   speculative  (one_chain_frame) blob sized from the thread's recent frames, everything enqueued at once, counts read
+//                on the device, the mailbox read after the last enqueue; overflow -> redo_frame, exact size;
+//   near / far   (near_far_frame: dense frames) two chains over the Gaussians in depth order -- near up to a budget,
+//                then only the far Gaussians whose rectangle still holds an unfinished tile;
 //   + far-chain speculation (after two split frames that left nothing unfinished): the far chain is not enqueued on
 //                the caller's stream -- ASYNCHRONOUS: gated, on the library's own stream behind a stream-side wait for
 //                the near blend's decision, the caller's stream waiting for the frame's go word; or HOST-DECIDED: the
@@ -239,16 +239,23 @@ constexpr int MAILBOX_WORDS = 32;
 // other prediction here: a wrong one costs a redo or a far chain, never a result).  A view seen for the first time
 // starts from the thread's most recently used history, so a caller that passes a fresh matrix tensor every frame -- or
 // renders one camera only -- gets exactly the per-thread behaviour.
+// The last four instance counts of a view (ViewHist), most recent at pos - 1.
+struct Recent4 {
+  uint32_t v[4] = {0, 0, 0, 0};
+  int pos = 0;
+  void push(uint32_t n) { v[pos] = n; pos = (pos + 1) & 3; }
+  uint32_t max() const { return std::max(std::max(v[0], v[1]), std::max(v[2], v[3])); }
+  bool empty() const { return (v[0] | v[1] | v[2] | v[3]) == 0u; }  // (all zero: nothing remembered)
+  void clear() { v[0] = v[1] = v[2] = v[3] = 0u; }
+};
 struct ViewHist {
   const void* key = nullptr;
   int W = 0, H = 0;
   unsigned long long used = 0;                // LRU stamp (0 = free)
   unsigned generation = 0;                    // bumped when the slot is given to another view
-  // speculative binning size: capacity the next forward allocates before it knows its instance count (0 = none)
-  uint32_t recent[4] = {0, 0, 0, 0};
-  int recent_pos = 0;
-  uint32_t recent_far[4] = {0, 0, 0, 0};      // far-phase instance counts of this view's recent near/far frames
-  int recent_far_pos = 0;
+  // speculative binning size: capacity the next forward allocates before it knows its instance count (all 0 = none)
+  Recent4 recent;
+  Recent4 recent_far;                         // far-phase instance counts of this view's recent near/far frames
   bool have_far = false;
   int far_idle_streak = 0;                    // consecutive near/far frames of this view that left no tile live
   // adaptive near budget (budget_feedback): the configured entries per tile x near_scale_q8 / 256
@@ -637,6 +644,25 @@ static void budget_feedback(const ThreadCtx& c, ViewHist& h, uint32_t live, uint
   }
 }
 
+// What a near/far frame's far chain came to -- quads the near chain left unfinished and the instance counts -- scored
+// and fed back into the view's history (h: null when the view's slot has gone to another view).  `speculated`: the
+// frame expected its far chain to stay idle (the speculation's own score: frames that enqueued their far chain outright
+// are not counted).  `latest`: the thread's most recent forward, whose outcome gsr_last_far_skipped reports.
+static void record_far_outcome(ThreadCtx& c, ViewHist* h, uint32_t live, uint32_t R_near, uint32_t R_far,
+                               uint32_t R_total, bool speculated, bool latest) {
+  if (speculated) {
+    if (live == 0u) ++g_far_skips;
+    else ++g_far_skip_misses;
+  }
+  if (h) {
+    budget_feedback(c, *h, live, R_near, R_far, R_total);
+    h->recent_far.push(R_far);
+    h->have_far = true;
+    h->far_idle_streak = live == 0u ? h->far_idle_streak + 1 : 0;
+  }
+  if (latest) c.last_far_skipped = speculated && live == 0u;
+}
+
 // The history the calling thread keeps for a view (see ViewHist).  A new view inherits the most recently used one's.
 static ViewHist& view_hist(ThreadCtx& c, const void* key, int W, int H) {
   int hit = -1, lru = 0, mru = -1;
@@ -646,8 +672,7 @@ static ViewHist& view_hist(ThreadCtx& c, const void* key, int W, int H) {
     if (v.used < c.views[lru].used || lru == hit) lru = k;
     if (v.used && (mru < 0 || v.used > c.views[mru].used)) mru = k;
   }
-  const bool known = hit >= 0 && (c.views[hit].recent[0] | c.views[hit].recent[1] | c.views[hit].recent[2] |
-                                  c.views[hit].recent[3]) != 0u;
+  const bool known = hit >= 0 && !c.views[hit].recent.empty();
   const int slot = hit >= 0 ? hit : lru;
   ViewHist& v = c.views[slot];
   if (!known) {  // a new view, or one whose history was forgotten: the thread's most recent history
@@ -672,21 +697,12 @@ static void lazy_resolve(ThreadCtx& c) {
     uint32_t live = 0, far = 0;
     if (!peek_word(c, p.w_live, p.ticket, &live)) return;
     if (live != 0u && !peek_word(c, p.w_far, p.ticket, &far)) return;
-    if (p.speculated) {  // (the speculation's own score: frames that enqueued their far chain outright are not counted)
-      if (live == 0u) ++g_far_skips;
-      else ++g_far_skip_misses;
-    }
     ViewHist& h = c.views[p.view];
-    if (h.generation == p.gen) {  // (unless the slot has gone to another view meanwhile)
-      budget_feedback(c, h, live, p.near, far, p.total);
-      h.recent_far[h.recent_far_pos] = far;
-      h.recent_far_pos = (h.recent_far_pos + 1) & 3;
-      h.have_far = true;
-      h.far_idle_streak = live == 0u ? h.far_idle_streak + 1 : 0;
-    }
-    if (p.ticket == c.ticket) {  // the thread's most recent forward: what gsr_last_* report
+    const bool latest = p.ticket == c.ticket;  // the thread's most recent forward: what gsr_last_* report
+    record_far_outcome(c, h.generation == p.gen ? &h : nullptr,  // (unless the slot has gone to another view meanwhile)
+                       live, p.near, far, p.total, p.speculated, latest);
+    if (latest) {
       c.last_far = far;
-      c.last_far_skipped = p.speculated && live == 0u;
       c.last_R = c.last_near + c.last_far;
     }
     c.pending_head = (c.pending_head + 1) & 7;
@@ -732,7 +748,7 @@ static bool several_threads_render(const void* me) {
 }
 
 // One binning chain: scan -> emit -> tile sort -> ranges, followed by the blend.  A whole frame is one chain over the
-// blob (phase 0).  A near/far frame (gsr_forward) runs two chains over ONE blob carved for capA + capB instances:
+// blob (phase 0).  A near/far frame (near_far_frame) runs two chains over ONE blob carved for capA + capB instances:
 // phase 1 bins the near Gaussians into slots / list positions [0, capA), phase 2 the far Gaussians that still matter
 // into [capA, capA + capB); the sort scratch is shared (the chains are ordered on the stream).
 struct Chain {
@@ -749,10 +765,56 @@ struct DepthOrder {
   const uint32_t* ghist;       // k_preprocess's digit counts of all P keys (for that full sort), or null
 };
 
-static int enqueue_chain(const FrameParams& fp, GeomState& g, ImageState& im, BinningState& b, const Chain& ch,
-                         ThreadCtx& c, const DepthOrder& dord, const float* background, float* out_color,
-                         float* out_depth, float* out_acc, int debug, hipStream_t stream,
+// The environment variables a forward reads (gsraster.h), once per process (forward_env).
+struct ForwardEnv {
+  // GSR_ASYNC_FAR_MT=1, diagnostics: asynchronous frames although several threads render -- the combination that faulted
+  bool async_mt = getenv("GSR_ASYNC_FAR_MT") != nullptr;
+  bool depth_hist_pass = getenv("GSR_DEPTH_HIST_PASS") != nullptr;  // the depth sort's own histogram pass
+  bool sync_forward = getenv("GSR_SYNC_FORWARD") != nullptr;        // every forward synchronous
+  bool host_trace = getenv("GSR_HOST_TRACE") != nullptr;            // diagnostics: host-side waits
+  long near_entries = getenv("GSR_NEAR_ENTRIES") ? atol(getenv("GSR_NEAR_ENTRIES")) : 320;  // near budget per tile
+  unsigned long long near_far_min_ratio_q2 =
+      getenv("GSR_NEAR_FAR_MIN_RATIO_Q2") ? strtoull(getenv("GSR_NEAR_FAR_MIN_RATIO_Q2"), nullptr, 10) : 12ull;
+  bool full_depth_sort = getenv("GSR_FULL_DEPTH_SORT") != nullptr;    // diagnostics / fallback: no partial depth sort
+  bool ranges_from_keys = getenv("GSR_RANGES_FROM_KEYS") != nullptr;  // diagnostics / fallback (enqueue_chain)
+};
+static const ForwardEnv& forward_env() {
+  static const ForwardEnv env;
+  return env;
+}
+
+// One forward, as the functions that enqueue its parts see it.
+struct Forward {
+  const FrameParams& fp;
+  GeomState& g;
+  ImageState& im;
+  ThreadCtx& c;
+  ViewHist& h;      // the view's history (view_hist)
+  const ForwardEnv& env;
+  DepthOrder dord;  // (enqueue_depth_order)
+  const float* background;
+  float *out_color, *out_depth, *out_acc;
+  int debug;
+  hipStream_t stream;  // the caller's
+  char* iblob;
+  gsr_alloc_fn binning_alloc;
+  void* binning_ctx;
+  std::chrono::steady_clock::time_point t_enq;  // (host trace) when the binning began to be enqueued
+};
+
+// What a frame kind leaves for gsr_forward: the capacity the binning blob was carved for (what the caller passes back
+// to gsr_backward), the frame's instance count R, the near / far instances emitted, and whether R overflowed the blob.
+struct FrameResult { int key = 0; uint32_t R = 0, near = 0, far = 0; bool redo = false; };
+
+// (STAGE synchronises `stream`, the stream the chain is enqueued on: the caller's or c.far_stream)
+static int enqueue_chain(const Forward& f, BinningState& b, const Chain& ch, hipStream_t stream,
                          AsyncWords aw = AsyncWords()) {
+  const FrameParams& fp = f.fp;
+  GeomState& g = f.g;
+  ImageState& im = f.im;
+  ThreadCtx& c = f.c;
+  const DepthOrder& dord = f.dord;
+  const int debug = f.debug;
   const Count cnt = ch.cnt;  // (carries the gate of an asynchronous frame's far chain)
   const int tiles = fp.gx * fp.gy;
   const int tile_bits = (int)gsr_higher_msb((uint32_t)tiles);  // the `bit` of rasterizer_impl.cu:295
@@ -798,9 +860,8 @@ static int enqueue_chain(const FrameParams& fp, GeomState& g, ImageState& im, Bi
   const EmitFusion ef = {fp, sdesc, cnt, chunk_first};
   // 16-bit keys and at least two passes: the last pass counts the instances of every tile into the zeroed ranges
   // instead of writing the sorted keys, and a one-workgroup scan turns the counts into ranges; otherwise the range
-  // kernel reads the sorted keys as the reference's identifyTileRanges does
-  static const bool ranges_from_keys = getenv("GSR_RANGES_FROM_KEYS") != nullptr;  // diagnostics / fallback
-  const bool count_ranges = key16 && sort_passes(tile_bits) >= 2 && !ranges_from_keys;
+  // kernel reads the sorted keys as the reference's identifyTileRanges does (GSR_RANGES_FROM_KEYS)
+  const bool count_ranges = key16 && sort_passes(tile_bits) >= 2 && !f.env.ranges_from_keys;
   const BucketPass bp = {ranges, tiles, ch.base};
   STAGE(launch_sort_pairs(b.tkeysA, point_list, b.tkeysB, b.ivalsB, b.tsort, cnt, tile_bits, start_in_A,
                           /*is_depth_sort=*/false, key16, /*first_hist_done=*/true, key16 ? &ef : nullptr,
@@ -819,9 +880,32 @@ static int enqueue_chain(const FrameParams& fp, GeomState& g, ImageState& im, Bi
     if (bad) return fail(GSR_ERR_HIP, "%u adjacent list entries out of (depth, id) order after the sort", bad);
   }
   // (the near blend counts the quads it leaves unfinished into the host's mailbox: done word 1, mailbox word 3)
-  STAGE(launch_blend_forward(fp, g, b, im, background, out_color, out_depth, out_acc, ch.phase, c.done_counter + 1,
-                             c.mailbox_dev + c.w_live, c.ticket, ch.phase == 1 ? aw : AsyncWords(), cnt, stream));
+  STAGE(launch_blend_forward(fp, g, b, im, f.background, f.out_color, f.out_depth, f.out_acc, ch.phase,
+                             c.done_counter + 1, c.mailbox_dev + c.w_live, c.ticket, ch.phase == 1 ? aw : AsyncWords(),
+                             cnt, stream));
   return GSR_OK;
+}
+
+// The binning blob for `cap` instances, from the caller's allocator.
+static int carve_binning(const Forward& f, int cap, BinningState* b) {
+  char* bblob = f.binning_alloc(f.binning_ctx, gsr_binning_bytes(cap));
+  if (!bblob) return fail(GSR_ERR_ALLOC, "binning allocator returned NULL");
+  *b = BinningState::carve(bblob, (size_t)cap);
+  return GSR_OK;
+}
+
+// One chain over a blob carved for exactly R instances, a count the host has read: the synchronous frame, and the redo
+// of a speculative one that overflowed (sync_trace: the synchronous frame's host-trace line).
+static int enqueue_exact(const Forward& f, uint32_t R, bool sync_trace) {
+  const std::chrono::steady_clock::time_point ta = std::chrono::steady_clock::now();
+  BinningState b;
+  const int rc = carve_binning(f, (int)R, &b);
+  if (sync_trace && f.env.host_trace)
+    fprintf(stderr, "[gsr] synchronous forward: R=%u, waited %.1f us, binning alloc %.1f us\n", R,
+            std::chrono::duration<double, std::micro>(ta - f.t_enq).count(),
+            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - ta).count());
+  if (rc != GSR_OK) return rc;
+  return enqueue_chain(f, b, Chain{0, Count{nullptr, (int)R}, 0xFFFFFFFFu, 0u}, f.stream);
 }
 
 // near/far frames (gsr_set_near_far): 1 = allowed (default), 0 = never
@@ -833,6 +917,290 @@ static std::atomic<int>& near_far_flag() {
   return flag;
 }
 static std::atomic<unsigned long long> g_near_far_forwards{0};
+
+// What kind of frame this forward is, decided from the thread's test hooks and the view's history before the binning
+// is enqueued (no HIP call; the hooks it consumes and the history it updates are noted where that happens).
+struct FramePlan {
+  uint32_t hint;                // binning capacity to allocate for (0: nothing predicted)
+  unsigned long long budget64;  // near budget: list entries over all tiles
+  bool speculate;               // everything enqueued before R is known (otherwise the synchronous frame)
+  bool near_far;                // two chains, near and far (near_far_frame)
+  bool speculate_far;           // a near/far frame that expects its far chain to stay idle
+  bool partial_sort;            // only the near candidates are sorted by depth up front (enqueue_depth_order)
+};
+static FramePlan plan_frame(ThreadCtx& c, ViewHist& h, const FrameParams& fp, const ForwardEnv& env, int debug) {
+  FramePlan p;
+  uint32_t hint = 0, pred = 0;  // capacity to allocate for / instance count predicted (the decisions below use the latter)
+  if (c.hint_override >= 0) {
+    hint = pred = (uint32_t)c.hint_override;
+    c.hint_override = -1;
+  } else {
+    hint = h.recent.max();
+    if (hint) {
+      hint = round_capacity((uint32_t)std::min<unsigned long long>(0x7fffffffull, (unsigned long long)hint * 5 / 4 + 65536));
+      pred = hint;
+      if (hint > h.cap_hw) {  // (ViewHist::cap_hw)
+        h.cap_hw = round_capacity((uint32_t)std::min<unsigned long long>(0x7fffffffull, (unsigned long long)hint * 5 / 4));
+        h.cap_low_run = 0;
+      } else if (hint < h.cap_hw / 2u) {
+        if (++h.cap_low_run >= 64) { h.cap_hw = hint; h.cap_low_run = 0; }
+      } else {
+        h.cap_low_run = 0;
+      }
+      hint = h.cap_hw;
+    } else {
+      h.cap_hw = 0;
+    }
+  }
+  p.hint = hint;
+  p.speculate = !debug && !env.sync_forward && hint > 0;
+  // Near/far frame (speculative forwards in the default binning mode, when the predicted instance count is at least
+  // three times the near budget): the tiles' lists are depth-ordered and a pixel stops reading its list once its
+  // transmittance falls below 1e-4 (forward.cu:380-383) -- at 2 M Gaussians / 1080p every tile is finished after
+  // ~3 % of its list, and emitting, sorting and ranging the other 97 % is most of the forward.  So the frame is binned
+  // in two chains over the Gaussians in depth order: the NEAR chain takes Gaussians until they fill a budget of
+  // `near_entries` list entries per tile on average, is sorted and blended; then only the FAR Gaussians whose tile
+  // rectangle still contains an unfinished tile are binned and blended on top (k_scan_offsets_far).  Instances that
+  // are not emitted lie, in every tile they would have gone to, behind the point where every pixel has stopped: the
+  // images, n_contrib, final_T and all gradients are bit-identical to the one-chain frame (tested), only the lists
+  // are shorter.  gsr_set_reference_rects(1) frames are never split: their lists are the reference's, whole.
+  const long long near_entries = c.near_entries_override >= 0
+                                     ? c.near_entries_override
+                                     : (env.near_entries * (long long)h.near_scale_q8 + 255) / 256;  // (budget_feedback)
+  p.budget64 = (unsigned long long)(fp.gx * fp.gy) * (unsigned long long)near_entries;
+  bool split_paused = false;
+  if (h.split_pause > 0 && c.near_entries_override < 0) {  // (budget_feedback: this view's splits kept missing)
+    h.split_pause--;
+    split_paused = true;
+  }
+  // (three times: BASELINE C2 -- 500 k Gaussians at 1280x720, 3.6 M instances, 3.1 budgets -- bins 1.15 M of them and its
+  // forward goes 0.31 -> 0.245 ms; at 1.5 budgets, the 640x512 shape, a split saves nothing.  In quarters:
+  // GSR_NEAR_FAR_MIN_RATIO_Q2)
+  p.near_far = p.speculate && (t_near_far >= 0 ? t_near_far != 0 : near_far_flag().load() != 0) && !fp.ref_rects &&
+               near_entries > 0 && p.budget64 < 0x20000000ull && !split_paused &&
+               (c.near_entries_override >= 0 ||
+                4ull * (unsigned long long)pred >= env.near_far_min_ratio_q2 * p.budget64);  // (hook: always)
+  // Far-chain speculation (near_far_frame): after two split frames in a row that left no quad unfinished (or when the
+  // test hook asks) the thread's next split frame expects its far chain to stay idle.
+  p.speculate_far = p.near_far && (c.far_skip_override >= 0 ? c.far_skip_override == 1 : h.far_idle_streak >= 2);
+  const bool speculation_forced = p.near_far && c.far_skip_override == 1;  // (test hook: also overrides the guard below)
+  if (speculation_forced) c.far_skip_override = -1;
+  // (no partial depth sort while the candidates are more than a third of the scene -- the line is drawn at top-byte
+  // granularity, a factor of four in depth: the last partial sort's count says so; every 64th frame tries again)
+  if (h.near_list_too_long && (c.ticket & 63u) == 0u) h.near_list_too_long = false;
+  p.partial_sort = p.speculate_far && c.top_hist != nullptr && !env.full_depth_sort &&
+                   (!h.near_list_too_long || speculation_forced);
+  return p;
+}
+
+// Depth order of the Gaussians.  A frame that speculates on its far chain needs it for the NEAR candidates only
+// (k_compact_near): they are compacted into the sort's second buffer pair and sorted there (partial depth sort: at
+// 2 M Gaussians / 1080p some 50 000 pairs instead of 2 M, 0.11 -> 0.05 ms); the full sort moves into the far chain, for
+// the frames that run it.
+static int enqueue_depth_order(Forward& f, const FramePlan& p, const uint32_t* ghist_acc) {
+  GeomState& g = f.g;
+  ThreadCtx& c = f.c;
+  const int debug = f.debug, P = f.fp.P;
+  const hipStream_t stream = f.stream;
+  f.dord = DepthOrder{g.order, p.partial_sort, ghist_acc};
+  if (p.partial_sort) {
+    STAGE(launch_compact_near(f.fp, g, c.top_hist, (uint32_t)p.budget64, g.dkeysB, g.dvalsB, g.total + 15,
+                              g.dsort.ghist_near((size_t)P), c.mailbox_dev + 4, c.ticket, stream));
+    c.near_count_pending = true;
+    c.near_count_ticket = c.ticket;
+    c.near_count_view = c.cur;
+    c.near_count_gen = f.h.generation;
+    STAGE(launch_depth_sort(g.dkeysB, g.dvalsB, g.nkeys2, g.nvals2, g.dsort, Count{g.total + 15, P},
+                            g.dsort.ghist_near((size_t)P), /*vals_are_positions=*/false, stream));
+    f.dord.near_order = g.dvalsB;
+  } else {
+    STAGE(launch_depth_sort(g.dkeysA, g.order, g.dkeysB, g.dvalsB, g.dsort, Count{nullptr, P}, ghist_acc,
+                            /*vals_are_positions=*/true, stream));
+  }
+  return GSR_OK;
+}
+
+// Synchronous frame: the host waits for k_preprocess's count and bins the frame in one chain of exactly that size.
+static int sync_frame(const Forward& f, FrameResult* r) {
+  const int rc = wait_num_rendered(f.c, f.stream, &r->R);
+  if (rc != GSR_OK) return rc;
+  if (r->R > 0x7fffffffu) return fail(GSR_ERR_UNSUPPORTED, "more than 2^31 splat instances");
+  r->key = (int)r->R;
+  r->near = r->R;
+  return enqueue_exact(f, r->R, /*sync_trace=*/true);
+}
+
+// Speculative one-chain frame: one chain over a blob carved for the predicted capacity.
+static int one_chain_frame(const Forward& f, uint32_t cap, FrameResult* r) {
+  r->key = (int)cap;
+  BinningState b;
+  int rc;
+  if ((rc = carve_binning(f, r->key, &b)) != GSR_OK ||
+      (rc = enqueue_chain(f, b, Chain{0, Count{f.g.total, r->key}, 0xFFFFFFFFu, 0u}, f.stream)) != GSR_OK)
+    return rc;
+  const std::chrono::steady_clock::time_point tw = std::chrono::steady_clock::now();
+  if ((rc = wait_num_rendered(f.c, f.stream, &r->R)) != GSR_OK) return rc;
+  if (f.env.host_trace)
+    fprintf(stderr, "[gsr] speculative forward: capacity %d, R=%u, enqueue %.1f us, then waited %.1f us\n", r->key,
+            r->R, std::chrono::duration<double, std::micro>(tw - f.t_enq).count(),
+            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count());
+  ++g_speculative_forwards;
+  r->redo = r->R > cap;
+  r->near = r->R;
+  return GSR_OK;
+}
+
+// Near/far frame (plan_frame): the near chain, then the far chain over the Gaussians behind the budget.
+// Far-chain speculation.  In a dense scene the near chain finishes every quad, frame after frame, and the far chain's
+// launches find nothing to do (~60 us at 1080p).  After two such frames in a row (or when the test hook asks) the
+// thread's next split frame is
+//   * ASYNCHRONOUS where the device has stream-side waits (async_far_ready): the far chain goes to the library's own
+//     stream behind a wait for the near blend's decision, every kernel of it gated on "quads were left unfinished"; the
+//     caller's stream waits for the frame's go word, which the near blend's last workgroup stores itself when nothing
+//     is left to do (otherwise the far chain's last kernel does).  Nobody waits for the decision on the host; with no
+//     host in the loop the far segment is sized for every instance behind the near budget, so it cannot overflow;
+//   * otherwise decided by the host: the near blend publishes the count of unfinished quads to the mailbox and the far
+//     chain is enqueued only if there are any (one host round trip instead of eleven idle launches).
+// The near blend parks the unfinished pixels' state in the same way in every variant: same result.  A frame that does
+// not speculate enqueues its far chain outright.
+static int near_far_frame(const Forward& f, const FramePlan& p, bool multi_thread, FrameResult* r) {
+  GeomState& g = f.g;
+  ThreadCtx& c = f.c;
+  const hipStream_t stream = f.stream;
+  const bool async_far = p.speculate_far && !multi_thread && async_far_ready(c);
+  const bool skip_far = p.speculate_far && !async_far;
+  // the blob: capA instances for the near chain (the run the budget falls into ends at most one rectangle later), capB
+  // for the far one
+  const uint32_t budget = (uint32_t)p.budget64;
+  const uint32_t behind = p.hint > budget ? p.hint - budget : 0u;  // room for every instance behind the budget
+  const uint32_t capA = budget + (uint32_t)(f.fp.gx * f.fp.gy);
+  uint32_t capB = 0;
+  const bool capB_forced = c.far_hint_override >= 0;  // (test hook: may be too small on purpose)
+  if (capB_forced) {
+    capB = (uint32_t)c.far_hint_override;
+    c.far_hint_override = -1;
+  } else if (f.h.have_far) {
+    capB = f.h.recent_far.max();
+    // (half again as much as the view's recent far chains held: an overflow bins the whole frame a second time, ~1 ms
+    // at 2 M Gaussians, the margin costs 53 bytes per instance -- a camera that comes round every eighth iteration of a
+    // scene that is being optimised outgrew a quarter, twice in 72 frames)
+    capB = (uint32_t)std::min<unsigned long long>(0x7fffffffull - capA, (unsigned long long)capB * 3 / 2 + 131072);
+    capB = std::min(round_capacity(capB), 0x7fffffffu - capA);
+  } else {
+    capB = behind;  // no history
+  }
+  // (Measured and not kept: frames that enqueue their far chain outright sizing the far segment like the asynchronous
+  // ones and returning without waiting for the far count.  Eight views per iteration from one thread: 0.985 -> 0.994 ms
+  // per view -- that loop is bound by the GPU, not by the host's wait -- at 1.9 GB of binning blob per view in flight.)
+  const bool lazy_cap = async_far && !capB_forced;
+  const uint32_t far_expect = std::max<uint32_t>(capB, 1u << 20);  // (from history, before the capacity is widened)
+  if (lazy_cap) capB = std::max(capB, behind);
+  if (capB < 4096u) capB = 4096u;
+  if ((unsigned long long)capA + capB > 0x7fffffffull) capB = 0x7fffffffu - capA;
+  r->key = (int)(capA + capB);
+  BinningState b;
+  int rc;
+  if ((rc = carve_binning(f, r->key, &b)) != GSR_OK) return rc;
+  AsyncWords aw;
+  if (async_far) {
+    if (c.async_seq >= 0x3FFFFFF0u) {  // (the decision word carries 2 seq + 1)
+      HIP_TRY(hipStreamSynchronize(stream));
+      HIP_TRY(hipStreamSynchronize(c.far_stream));
+      HIP_TRY(hipMemset(c.sig_decide, 0, 8));
+      HIP_TRY(hipMemset(c.sig_go, 0, 8));
+      HIP_TRY(hipMemset(c.done_counter + 2, 0, 8));
+      c.async_seq = 0;
+    }
+    aw.decide = c.sig_decide;
+    aw.go = c.sig_go;
+    aw.gate_dev = reinterpret_cast<uint32_t*>(c.done_counter + 2);
+    aw.seq = ++c.async_seq;
+  }
+  if (lazy_cap) {
+    c.w_live = 16 + 2 * (int)(++c.lazy_seq & 7u);  // this frame's own outcome slot (lazy_resolve)
+    c.w_far = c.w_live + 1;
+  }
+  if ((rc = enqueue_chain(f, b, Chain{1, Count{g.total + 6, (int)capA}, budget, 0u}, stream, aw)) != GSR_OK) return rc;
+  Chain far_chain{2, Count{g.total + 8, (int)capB}, 0xFFFFFFFFu, capA, far_expect};
+  far_chain.cnt.bounded = lazy_cap;  // (a capacity that is rarely used: grid-stride over a bounded grid)
+  uint32_t live = 0;
+  c.last_far_skipped = false;
+  if (async_far) {
+    far_chain.cnt.gate = aw.gate_dev;
+    far_chain.cnt.gate_open = 2u * aw.seq + 1u;
+    // (quads left unfinished: the far chain is opened from behind the near blend's kernel boundary, render.hip)
+    HIP_TRY(launch_decide_far(g.total + 13, aw, stream));
+    HIP_TRY(hipStreamWaitValue32(c.far_stream, c.sig_decide, 2u * aw.seq, hipStreamWaitValueGte));
+    // (not timed by the event profiler: the chain waits on its stream for the decision and then, as a rule, only
+    // launches and leaves; its kernels run beside the other stream's and would be booked twice)
+    t_prof_suppress = true;
+    rc = enqueue_chain(f, b, far_chain, c.far_stream);
+    t_prof_suppress = false;
+    if (rc != GSR_OK) return rc;
+    HIP_TRY(launch_release_go(far_chain.cnt, c.sig_go, aw.seq, c.far_stream));
+    HIP_TRY(hipStreamWaitValue32(stream, c.sig_go, aw.seq, hipStreamWaitValueGte));
+    HIP_TRY(launch_tile_order(f.fp, f.im, stream));  // (after the go word: the far chain may move quad_last)
+    order_remember(f.iblob);
+    ++g_async_frames;
+  } else if (skip_far) {
+    if (launch_tile_order(f.fp, f.im, stream) != hipSuccess) return fail(GSR_ERR_HIP, "k_tile_order launch failed");
+  } else {
+    if ((rc = enqueue_chain(f, b, far_chain, stream)) != GSR_OK) return rc;
+  }
+  const std::chrono::steady_clock::time_point tw = std::chrono::steady_clock::now();
+  if ((rc = wait_num_rendered(c, stream, &r->R)) != GSR_OK) return rc;
+  if ((rc = wait_num_rendered(c, stream, &r->near, 2)) != GSR_OK) return rc;
+  bool know_far = true;
+  if (lazy_cap && (unsigned long long)r->R - r->near <= (unsigned long long)capB) {
+    // the far segment holds whatever the far chain may emit: nothing left for the host to check or to wait for
+    know_far = false;
+    lazy_push(c, c.ticket, r->near, r->R, /*speculated=*/async_far);
+  } else {
+    if ((rc = wait_num_rendered(c, stream, &live, c.w_live)) != GSR_OK) return rc;
+    if (p.speculate_far && live == 0u) {  // the far chain was not needed (an asynchronous frame here: capacity forced)
+      if (skip_far) order_remember(f.iblob);
+    } else {
+      if (skip_far && (rc = enqueue_chain(f, b, far_chain, stream)) != GSR_OK) return rc;  // unfinished quads after all
+      if ((rc = wait_num_rendered(c, stream, &r->far, c.w_far)) != GSR_OK) return rc;
+    }
+    record_far_outcome(c, &f.h, live, r->near, r->far, r->R, /*speculated=*/p.speculate_far, /*latest=*/true);
+  }
+  if (f.env.host_trace)
+    fprintf(stderr, "[gsr] near/far forward: capacity %u + %u, near %u, far %u of %u instances, %u unfinished quads%s, "
+                    "enqueue %.1f us, then waited %.1f us\n", capA, capB, r->near, r->far, r->R, live,
+            async_far ? (know_far ? " (asynchronous far chain, checked by the host)" : " (asynchronous far chain)")
+            : skip_far ? (live ? " (far chain enqueued late)" : " (far chain not enqueued)")
+            : "",
+            std::chrono::duration<double, std::micro>(tw - f.t_enq).count(),
+            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count());
+  ++g_speculative_forwards;
+  ++g_near_far_forwards;
+  c.last_was_near_far = true;
+  r->redo = r->far > capB;
+  if (!r->redo) frame_note(f.iblob, NOTE_SPLIT);
+  return GSR_OK;
+}
+
+// Misprediction: the clamped results are discarded and the frame is binned again, in one exact chain.
+static int redo_frame(const Forward& f, FrameResult* r) {
+  GeomState& g = f.g;
+  const hipStream_t stream = f.stream;
+  ++g_speculation_overflows;
+  order_forget(f.iblob);
+  // the scans run a second time: their tile tickets, look-back status words and the near-budget marker (cleared by
+  // k_preprocess for the first run) must be zero again
+  const size_t nscan = ((size_t)f.fp.P + SCAN_TILE - 1) / SCAN_TILE;
+  HIP_TRY(hipMemsetAsync(g.dsort.tickets() + 4, 0, 2 * sizeof(uint32_t), stream));
+  HIP_TRY(hipMemsetAsync(g.dsort.scan_status(), 0, sizeof(unsigned long long) * 2 * nscan, stream));  // both scans'
+  HIP_TRY(hipMemsetAsync(g.total + 11, 0, sizeof(uint32_t), stream));
+  const int rc = enqueue_exact(f, r->R, /*sync_trace=*/false);
+  if (rc != GSR_OK) return rc;
+  f.c.last_was_near_far = false;
+  r->key = (int)r->R;
+  r->near = r->R;
+  r->far = 0;
+  return GSR_OK;
+}
 
 int gsr_forward(gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn binning_alloc, void* binning_ctx,
                 gsr_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background, int width,
@@ -889,9 +1257,8 @@ int gsr_forward(gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn bi
   //     waits for the host.  If R exceeds the capacity the kernels have clamped to it (in-bounds garbage); the
   //     host then allocates an exact blob and enqueues the binning chain again -- the only cost of a misprediction.
   ThreadCtx& c = g_ctx;
-  // (GSR_ASYNC_FAR_MT=1, diagnostics: asynchronous frames although several threads render -- the combination that faulted)
-  static const bool env_async_mt = getenv("GSR_ASYNC_FAR_MT") != nullptr;
-  const bool multi_thread = several_threads_render(&c) && !env_async_mt;
+  const ForwardEnv& env = forward_env();
+  const bool multi_thread = several_threads_render(&c) && !env.async_mt;
   lazy_resolve(c);  // (what the thread's earlier asynchronous frames left open, as far as the mailbox has it by now)
   c.w_live = 3;
   c.w_far = 1;
@@ -903,16 +1270,13 @@ int gsr_forward(gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn bi
     c.near_count_pending = false;
   }
   ViewHist& h = view_hist(c, viewmatrix, width, height);  // what this view's recent frames predict
-  {
-    const int rc = ctx_prepare(c, stream);
-    if (rc != GSR_OK) return rc;
-  }
+  int rc = ctx_prepare(c, stream);
+  if (rc != GSR_OK) return rc;
   // Digit histograms of the depth sort, counted by k_preprocess: two library-owned [4][256] buffers behind the
   // counter, used alternately -- a forward counts into one (zero on entry) and clears the other for the next
   // forward of this thread, so a call that ends early never leaves a dirty buffer in the way.
   // GSR_DEPTH_HIST_PASS=1 restores the sort's own histogram pass (k_sort_hist_all).
-  static const bool env_hist_pass = getenv("GSR_DEPTH_HIST_PASS") != nullptr;
-  const bool own_hist_pass = env_hist_pass || !preprocess_counts_depth_digits(fp, shs, colors_precomp);
+  const bool own_hist_pass = env.depth_hist_pass || !preprocess_counts_depth_digits(fp, shs, colors_precomp);
   uint32_t* const ghist2 = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(c.done_counter) + 64);
   if (!own_hist_pass) c.hist_flip ^= 1u;  // only a call that uses the pair advances it (the other buffer is clean)
   // (5 rows of 256: the four digit histograms + the tile counts summed by top byte, k_preprocess)
@@ -924,309 +1288,27 @@ int gsr_forward(gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn bi
   c.top_hist = ghist_acc ? ghist_acc + 3 * 256 : nullptr;  // rows 3 (counts by top byte) and 4 (tile sums) are adjacent
   if (debug) STAGE(launch_point_offsets(fp, g, stream));  // the reference's array, for the views only
 
-  static const bool env_sync = getenv("GSR_SYNC_FORWARD") != nullptr;
-  static const bool host_trace = getenv("GSR_HOST_TRACE") != nullptr;  // diagnostics: host-side waits
-  uint32_t hint = 0, pred = 0;  // capacity to allocate for / instance count predicted (the decisions below use the latter)
-  if (c.hint_override >= 0) {
-    hint = pred = (uint32_t)c.hint_override;
-    c.hint_override = -1;
-  } else {
-    for (int k = 0; k < 4; k++) hint = h.recent[k] > hint ? h.recent[k] : hint;
-    if (hint) {
-      hint = round_capacity((uint32_t)std::min<unsigned long long>(0x7fffffffull, (unsigned long long)hint * 5 / 4 + 65536));
-      pred = hint;
-      if (hint > h.cap_hw) {  // (ViewHist::cap_hw)
-        h.cap_hw = round_capacity((uint32_t)std::min<unsigned long long>(0x7fffffffull, (unsigned long long)hint * 5 / 4));
-        h.cap_low_run = 0;
-      } else if (hint < h.cap_hw / 2u) {
-        if (++h.cap_low_run >= 64) { h.cap_hw = hint; h.cap_low_run = 0; }
-      } else {
-        h.cap_low_run = 0;
-      }
-      hint = h.cap_hw;
-    } else {
-      h.cap_hw = 0;
-    }
-  }
-  const bool speculate = !debug && !env_sync && hint > 0;
-  const std::chrono::steady_clock::time_point t_enq = std::chrono::steady_clock::now();
-  uint32_t R_host = 0;
-  int key = 0;  // what the caller passes back to gsr_backward: the capacity the binning blob was carved for
+  const FramePlan plan = plan_frame(c, h, fp, env, debug);
+  Forward f{fp, g, im, c, h, env, DepthOrder{}, background, out_color, out_depth, out_acc, debug, stream, iblob,
+            binning_alloc, binning_ctx, std::chrono::steady_clock::now()};
   c.last_was_near_far = false;
-  // Near/far frame (speculative forwards in the default binning mode, when the predicted instance count is at least
-  // three times the near budget): the tiles' lists are depth-ordered and a pixel stops reading its list once its
-  // transmittance falls below 1e-4 (forward.cu:380-383) -- at 2 M Gaussians / 1080p every tile is finished after
-  // ~3 % of its list, and emitting, sorting and ranging the other 97 % is most of the forward.  So the frame is binned
-  // in two chains over the Gaussians in depth order: the NEAR chain takes Gaussians until they fill a budget of
-  // `near_entries` list entries per tile on average, is sorted and blended; then only the FAR Gaussians whose tile
-  // rectangle still contains an unfinished tile are binned and blended on top (k_scan_offsets_far).  Instances that
-  // are not emitted lie, in every tile they would have gone to, behind the point where every pixel has stopped: the
-  // images, n_contrib, final_T and all gradients are bit-identical to the one-chain frame (tested), only the lists
-  // are shorter.  gsr_set_reference_rects(1) frames are never split: their lists are the reference's, whole.
-  static const long env_near_entries = getenv("GSR_NEAR_ENTRIES") ? atol(getenv("GSR_NEAR_ENTRIES")) : 320;
-  const int tiles_n = fp.gx * fp.gy;
-  const long long near_entries = c.near_entries_override >= 0
-                                     ? c.near_entries_override
-                                     : (env_near_entries * (long long)h.near_scale_q8 + 255) / 256;  // (budget_feedback)
-  const unsigned long long budget64 = (unsigned long long)tiles_n * (unsigned long long)near_entries;
-  bool split_paused = false;
-  if (h.split_pause > 0 && c.near_entries_override < 0) {  // (budget_feedback: this view's splits kept missing)
-    h.split_pause--;
-    split_paused = true;
-  }
-  // (three times: BASELINE C2 -- 500 k Gaussians at 1280x720, 3.6 M instances, 3.1 budgets -- bins 1.15 M of them and its
-  // forward goes 0.31 -> 0.245 ms; at 1.5 budgets, the 640x512 shape, a split saves nothing.  In quarters:)
-  static const unsigned long long env_ratio_q2 =
-      getenv("GSR_NEAR_FAR_MIN_RATIO_Q2") ? strtoull(getenv("GSR_NEAR_FAR_MIN_RATIO_Q2"), nullptr, 10) : 12ull;
-  const bool near_far = speculate && (t_near_far >= 0 ? t_near_far != 0 : near_far_flag().load() != 0) && !fp.ref_rects && near_entries > 0 &&
-                        budget64 < 0x20000000ull && !split_paused &&
-                        (c.near_entries_override >= 0 || 4ull * (unsigned long long)pred >= env_ratio_q2 * budget64);  // (hook: always)
-  // Far-chain speculation (see the near/far branch below): after two split frames in a row that left no quad
-  // unfinished (or when the test hook asks) the thread's next split frame expects its far chain to stay idle.
-  const bool speculate_far = near_far && (c.far_skip_override >= 0 ? c.far_skip_override == 1 : h.far_idle_streak >= 2);
-  const bool speculation_forced = near_far && c.far_skip_override == 1;  // (test hook: also overrides the guard below)
-  if (speculation_forced) c.far_skip_override = -1;
-  // Depth order of the Gaussians.  Such a frame needs it for the NEAR candidates only (k_compact_near): they are
-  // compacted into the sort's second buffer pair and sorted there (partial depth sort: at 2 M Gaussians / 1080p some
-  // 50 000 pairs instead of 2 M, 0.11 -> 0.05 ms); the full sort moves into the far chain, for the frames that run it.
-  static const bool env_full_sort = getenv("GSR_FULL_DEPTH_SORT") != nullptr;  // diagnostics / fallback
-  // (not while the candidates are more than a third of the scene -- the line is drawn at top-byte granularity, a factor
-  // of four in depth: the last partial sort's count says so; every 64th frame tries again)
-  if (h.near_list_too_long && (c.ticket & 63u) == 0u) h.near_list_too_long = false;
-  const bool partial_sort = speculate_far && c.top_hist != nullptr && !env_full_sort &&
-                            (!h.near_list_too_long || speculation_forced);
-  const uint32_t* near_order = g.order;
-  if (partial_sort) {
-    STAGE(launch_compact_near(fp, g, c.top_hist, (uint32_t)budget64, g.dkeysB, g.dvalsB, g.total + 15,
-                              g.dsort.ghist_near((size_t)P), c.mailbox_dev + 4, c.ticket, stream));
-    c.near_count_pending = true;
-    c.near_count_ticket = c.ticket;
-    c.near_count_view = c.cur;
-    c.near_count_gen = h.generation;
-    STAGE(launch_depth_sort(g.dkeysB, g.dvalsB, g.nkeys2, g.nvals2, g.dsort, Count{g.total + 15, P},
-                            g.dsort.ghist_near((size_t)P), /*vals_are_positions=*/false, stream));
-    near_order = g.dvalsB;
-  } else {
-    STAGE(launch_depth_sort(g.dkeysA, g.order, g.dkeysB, g.dvalsB, g.dsort, Count{nullptr, P}, ghist_acc,
-                            /*vals_are_positions=*/true, stream));
-  }
-  // what a chain needs to know about the depth order (enqueue_chain)
-  const DepthOrder dord = {near_order, partial_sort, ghist_acc};
-  if (!speculate) {
-    const int rc = wait_num_rendered(c, stream, &R_host);
-    if (rc != GSR_OK) return rc;
-    if (R_host > 0x7fffffffu) return fail(GSR_ERR_UNSUPPORTED, "more than 2^31 splat instances");
-    const std::chrono::steady_clock::time_point ta = std::chrono::steady_clock::now();
-    char* bblob = binning_alloc(binning_ctx, gsr_binning_bytes((int)R_host));
-    if (host_trace)
-      fprintf(stderr, "[gsr] synchronous forward: R=%u, waited %.1f us, binning alloc %.1f us\n", R_host,
-              std::chrono::duration<double, std::micro>(ta - t_enq).count(),
-              std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - ta).count());
-    if (!bblob) return fail(GSR_ERR_ALLOC, "binning allocator returned NULL");
-    key = (int)R_host;
-    BinningState b = BinningState::carve(bblob, (size_t)key);
-    const int rc2 = enqueue_chain(fp, g, im, b, Chain{0, Count{nullptr, key}, 0xFFFFFFFFu, 0u}, c, dord, background, out_color,
-                                  out_depth, out_acc, debug, stream);
-    if (rc2 != GSR_OK) return rc2;
-    c.last_near = R_host;
-    c.last_far = 0;
-  } else {
-    bool redo = false;
-    uint32_t R_near = 0, R_far = 0;
-    if (near_far) {
-      const uint32_t budget = (uint32_t)budget64;
-      const uint32_t capA = budget + (uint32_t)tiles_n;  // the run the budget falls into ends at most one rectangle later
-      uint32_t capB = 0;
-      const bool capB_forced = c.far_hint_override >= 0;  // (test hook: may be too small on purpose)
-      if (capB_forced) {
-        capB = (uint32_t)c.far_hint_override;
-        c.far_hint_override = -1;
-      } else if (h.have_far) {
-        for (int k = 0; k < 4; k++) capB = h.recent_far[k] > capB ? h.recent_far[k] : capB;
-        // (half again as much as the view's recent far chains held: an overflow bins the whole frame a second time, ~1 ms
-        // at 2 M Gaussians, the margin costs 53 bytes per instance -- a camera that comes round every eighth iteration of a
-        // scene that is being optimised outgrew a quarter, twice in 72 frames)
-        capB = (uint32_t)std::min<unsigned long long>(0x7fffffffull - capA, (unsigned long long)capB * 3 / 2 + 131072);
-        capB = std::min(round_capacity(capB), 0x7fffffffu - capA);
-      } else {
-        capB = hint > budget ? hint - budget : 0u;  // no history: room for every instance behind the budget
-      }
-      // Far-chain speculation.  In a dense scene the near chain finishes every quad, frame after frame, and the far
-      // chain's launches find nothing to do (~60 us at 1080p).  After two such frames in a row (or when the test hook
-      // asks) the thread's next split frame is
-      //   * ASYNCHRONOUS where the device has stream-side waits (async_far_ready): the far chain goes to the library's
-      //     own stream behind a wait for the near blend's decision, every kernel of it gated on "quads were left
-      //     unfinished"; the caller's stream waits for the frame's go word, which the near blend's last workgroup stores
-      //     itself when nothing is left to do (otherwise the far chain's last kernel does).  Nobody waits for the
-      //     decision on the host; with no host in the loop the far segment is sized for every instance behind the near
-      //     budget, so it cannot overflow;
-      //   * otherwise decided by the host: the near blend publishes the count of unfinished quads to the mailbox and the
-      //     far chain is enqueued only if there are any (one host round trip instead of eleven idle launches).
-      // The near blend parks the unfinished pixels' state in the same way in every variant: same result.
-      const bool async_far = speculate_far && !multi_thread && async_far_ready(c);
-      const bool skip_far = speculate_far && !async_far;
-      // (Measured and not kept: frames that enqueue their far chain outright sizing the far segment like the asynchronous
-      // ones and returning without waiting for the far count.  Eight views per iteration from one thread: 0.985 -> 0.994 ms
-      // per view -- that loop is bound by the GPU, not by the host's wait -- at 1.9 GB of binning blob per view in flight.)
-      const bool lazy_cap = async_far && !capB_forced;
-      const uint32_t far_expect = std::max<uint32_t>(capB, 1u << 20);  // (from history, before the capacity is widened)
-      if (lazy_cap) capB = std::max(capB, hint > budget ? hint - budget : 0u);
-      if (capB < 4096u) capB = 4096u;
-      if ((unsigned long long)capA + capB > 0x7fffffffull) capB = 0x7fffffffu - capA;
-      key = (int)(capA + capB);
-      char* bblob = binning_alloc(binning_ctx, gsr_binning_bytes(key));
-      if (!bblob) return fail(GSR_ERR_ALLOC, "binning allocator returned NULL");
-      BinningState b = BinningState::carve(bblob, (size_t)key);
-      AsyncWords aw;
-      if (async_far) {
-        if (c.async_seq >= 0x3FFFFFF0u) {  // (the decision word carries 2 seq + 1)
-          HIP_TRY(hipStreamSynchronize(stream));
-          HIP_TRY(hipStreamSynchronize(c.far_stream));
-          HIP_TRY(hipMemset(c.sig_decide, 0, 8));
-          HIP_TRY(hipMemset(c.sig_go, 0, 8));
-          HIP_TRY(hipMemset(c.done_counter + 2, 0, 8));
-          c.async_seq = 0;
-        }
-        aw.decide = c.sig_decide;
-        aw.go = c.sig_go;
-        aw.gate_dev = reinterpret_cast<uint32_t*>(c.done_counter + 2);
-        aw.seq = ++c.async_seq;
-      }
-      if (lazy_cap) {
-        c.w_live = 16 + 2 * (int)(++c.lazy_seq & 7u);  // this frame's own outcome slot (lazy_resolve)
-        c.w_far = c.w_live + 1;
-      }
-      int rc = enqueue_chain(fp, g, im, b, Chain{1, Count{g.total + 6, (int)capA}, budget, 0u}, c, dord, background, out_color,
-                             out_depth, out_acc, debug, stream, aw);
-      if (rc != GSR_OK) return rc;
-      Chain far_chain{2, Count{g.total + 8, (int)capB}, 0xFFFFFFFFu, capA, far_expect};
-      far_chain.cnt.bounded = lazy_cap;  // (a capacity that is rarely used: grid-stride over a bounded grid)
-      uint32_t live = 0;
-      c.last_far_skipped = false;
-      if (async_far) {
-        far_chain.cnt.gate = aw.gate_dev;
-        far_chain.cnt.gate_open = 2u * aw.seq + 1u;
-        // (quads left unfinished: the far chain is opened from behind the near blend's kernel boundary, render.hip)
-        HIP_TRY(launch_decide_far(g.total + 13, aw, stream));
-        HIP_TRY(hipStreamWaitValue32(c.far_stream, c.sig_decide, 2u * aw.seq, hipStreamWaitValueGte));
-        // (not timed by the event profiler: the chain waits on its stream for the decision and then, as a rule, only
-        // launches and leaves; its kernels run beside the other stream's and would be booked twice)
-        t_prof_suppress = true;
-        rc = enqueue_chain(fp, g, im, b, far_chain, c, dord, background, out_color, out_depth, out_acc, debug, c.far_stream);
-        t_prof_suppress = false;
-        if (rc != GSR_OK) return rc;
-        HIP_TRY(launch_release_go(far_chain.cnt, c.sig_go, aw.seq, c.far_stream));
-        HIP_TRY(hipStreamWaitValue32(stream, c.sig_go, aw.seq, hipStreamWaitValueGte));
-        HIP_TRY(launch_tile_order(fp, im, stream));  // (after the go word: the far chain may move quad_last)
-        order_remember(iblob);
-        ++g_async_frames;
-      } else if (skip_far) {
-        if (launch_tile_order(fp, im, stream) != hipSuccess) return fail(GSR_ERR_HIP, "k_tile_order launch failed");
-      } else {
-        rc = enqueue_chain(fp, g, im, b, far_chain, c, dord, background, out_color, out_depth, out_acc, debug, stream);
-        if (rc != GSR_OK) return rc;
-      }
-      const std::chrono::steady_clock::time_point tw = std::chrono::steady_clock::now();
-      if ((rc = wait_num_rendered(c, stream, &R_host)) != GSR_OK) return rc;
-      if ((rc = wait_num_rendered(c, stream, &R_near, 2)) != GSR_OK) return rc;
-      bool know_far = true;
-      if (lazy_cap && (unsigned long long)R_host - R_near <= (unsigned long long)capB) {
-        // the far segment holds whatever the far chain may emit: nothing left for the host to check or to wait for
-        know_far = false;
-        lazy_push(c, c.ticket, R_near, R_host, /*speculated=*/async_far);
-        R_far = 0;
-      } else {
-        if ((rc = wait_num_rendered(c, stream, &live, c.w_live)) != GSR_OK) return rc;
-        if (skip_far && live == 0u) {
-          ++g_far_skips;
-          c.last_far_skipped = true;
-          order_remember(iblob);
-          R_far = 0;
-        } else if (async_far && live == 0u) {  // (an asynchronous frame whose far capacity was forced: scored here)
-          ++g_far_skips;
-          R_far = 0;
-          c.last_far_skipped = true;
-        } else {
-          if (async_far) ++g_far_skip_misses;
-          if (skip_far) {  // unfinished quads after all
-            ++g_far_skip_misses;
-            rc = enqueue_chain(fp, g, im, b, far_chain, c, dord, background, out_color, out_depth, out_acc, debug, stream);
-            if (rc != GSR_OK) return rc;
-          }
-          if ((rc = wait_num_rendered(c, stream, &R_far, c.w_far)) != GSR_OK) return rc;
-        }
-        h.far_idle_streak = live == 0u ? h.far_idle_streak + 1 : 0;
-        budget_feedback(c, h, live, R_near, R_far, R_host);
-      }
-      if (host_trace)
-        fprintf(stderr, "[gsr] near/far forward: capacity %u + %u, near %u, far %u of %u instances, %u unfinished quads%s, "
-                        "enqueue %.1f us, then waited %.1f us\n", capA, capB, R_near, R_far, R_host, live,
-                async_far ? (know_far ? " (asynchronous far chain, checked by the host)" : " (asynchronous far chain)")
-                : skip_far ? (live ? " (far chain enqueued late)" : " (far chain not enqueued)")
-                : "",
-                std::chrono::duration<double, std::micro>(tw - t_enq).count(),
-                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count());
-      ++g_speculative_forwards;
-      ++g_near_far_forwards;
-      if (know_far) {
-        h.recent_far[h.recent_far_pos] = R_far;
-        h.recent_far_pos = (h.recent_far_pos + 1) & 3;
-        h.have_far = true;
-      }
-      c.last_was_near_far = true;
-      redo = R_far > capB;
-      if (!redo) frame_note(iblob, NOTE_SPLIT);
-    } else {
-      key = (int)hint;
-      char* bblob = binning_alloc(binning_ctx, gsr_binning_bytes(key));
-      if (!bblob) return fail(GSR_ERR_ALLOC, "binning allocator returned NULL");
-      BinningState b = BinningState::carve(bblob, (size_t)key);
-      int rc = enqueue_chain(fp, g, im, b, Chain{0, Count{g.total, key}, 0xFFFFFFFFu, 0u}, c, dord, background, out_color,
-                             out_depth, out_acc, debug, stream);
-      if (rc != GSR_OK) return rc;
-      const std::chrono::steady_clock::time_point tw = std::chrono::steady_clock::now();
-      rc = wait_num_rendered(c, stream, &R_host);
-      if (rc != GSR_OK) return rc;
-      if (host_trace)
-        fprintf(stderr, "[gsr] speculative forward: capacity %d, R=%u, enqueue %.1f us, then waited %.1f us\n", key,
-                R_host, std::chrono::duration<double, std::micro>(tw - t_enq).count(),
-                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count());
-      ++g_speculative_forwards;
-      redo = R_host > (uint32_t)key;
-      R_near = R_host;
-    }
-    if (R_host > 0x7fffffffu) return fail(GSR_ERR_UNSUPPORTED, "more than 2^31 splat instances");
-    if (redo) {  // misprediction: the clamped results are discarded and the frame is binned again, in one exact chain
-      ++g_speculation_overflows;
-      order_forget(iblob);
-      key = (int)R_host;
-      // the scans run a second time: their tile tickets, look-back status words and the near-budget marker (cleared by
-      // k_preprocess for the first run) must be zero again
-      const size_t nscan = ((size_t)P + SCAN_TILE - 1) / SCAN_TILE;
-      HIP_TRY(hipMemsetAsync(g.dsort.tickets() + 4, 0, 2 * sizeof(uint32_t), stream));
-      HIP_TRY(hipMemsetAsync(g.dsort.scan_status(), 0, sizeof(unsigned long long) * 2 * nscan, stream));  // both scans'
-      HIP_TRY(hipMemsetAsync(g.total + 11, 0, sizeof(uint32_t), stream));
-      char* bblob = binning_alloc(binning_ctx, gsr_binning_bytes(key));
-      if (!bblob) return fail(GSR_ERR_ALLOC, "binning allocator returned NULL");
-      BinningState b = BinningState::carve(bblob, (size_t)key);
-      const int rc = enqueue_chain(fp, g, im, b, Chain{0, Count{nullptr, key}, 0xFFFFFFFFu, 0u}, c, dord, background, out_color,
-                                   out_depth, out_acc, debug, stream);
-      if (rc != GSR_OK) return rc;
-      c.last_was_near_far = false;
-      R_near = R_host;
-      R_far = 0;
-    }
-    c.last_near = R_near;
-    c.last_far = R_far;
-  }
-  if (host_trace)
+  if ((rc = enqueue_depth_order(f, plan, ghist_acc)) != GSR_OK) return rc;
+  FrameResult r;
+  rc = !plan.speculate ? sync_frame(f, &r)
+       : plan.near_far ? near_far_frame(f, plan, multi_thread, &r)
+                       : one_chain_frame(f, plan.hint, &r);
+  if (rc != GSR_OK) return rc;
+  if (r.R > 0x7fffffffu) return fail(GSR_ERR_UNSUPPORTED, "more than 2^31 splat instances");
+  if (r.redo && (rc = redo_frame(f, &r)) != GSR_OK) return rc;
+  c.last_near = r.near;
+  c.last_far = r.far;
+  if (env.host_trace)
     fprintf(stderr, "[gsr] forward returns at %.1f us (process clock)\n",
             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count());
   frame_note(iblob, NOTE_PRESENT);  // (every completed forward leaves a note: a backward that finds none was evicted)
-  h.recent[h.recent_pos] = R_host;  // (all instances of the frame, emitted or not: what a one-chain frame needs)
-  h.recent_pos = (h.recent_pos + 1) & 3;
+  h.recent.push(r.R);  // (all instances of the frame, emitted or not: what a one-chain frame needs)
   c.last_R = c.last_near + c.last_far;  // the instances this forward emitted, sorted and ranged
-  return key;
+  return r.key;
 }
 
 int gsr_last_num_rendered(void) {
@@ -1285,7 +1367,7 @@ long long gsr_set_binning_capacity_hint(long long capacity) {
   const long long prev = g_ctx.hint_override;
   g_ctx.hint_override = capacity < 0 ? -1 : (capacity > 0x7fffffffll ? 0x7fffffffll : capacity);
   if (capacity == 0)  // (every view's: the thread's next forward is synchronous whatever it looks at)
-    for (auto& v : g_ctx.views) v.recent[0] = v.recent[1] = v.recent[2] = v.recent[3] = 0;
+    for (auto& v : g_ctx.views) v.recent.clear();
   return prev;
 }
 unsigned long long gsr_speculative_forwards(void) { return g_speculative_forwards.load(); }
