@@ -66,7 +66,7 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_mark_visible", "gsr_geometry_byte
            "gsr_last_far_skipped", "gsr_far_skips", "gsr_far_skip_misses", "gsr_async_far_frames",
            "gsr_near_budget_scale", "gsr_near_budget_feedback", "gsr_near_far_pause", "gsr_set_near_far_thread",
            "gsr_set_reference_rects_thread", "gsr_async_outcomes_pending", "gsr_async_outcomes_lost",
-           "gsr_frame_note_misses")
+           "gsr_frame_note_misses", "gsr_similarity_loss", "gsr_similarity_loss_workspace")
 
 
 def lib():
@@ -137,7 +137,7 @@ def lib():
     L.gsr_near_far_pause.restype = ci
     L.gsr_near_far_pause.argtypes = [ci]
     for n in ("gsr_far_skips", "gsr_far_skip_misses", "gsr_async_far_frames", "gsr_async_outcomes_lost",
-              "gsr_frame_note_misses"):
+              "gsr_frame_note_misses", "gsr_similarity_loss", "gsr_similarity_loss_workspace"):
         getattr(L, n).restype = C.c_ulonglong
         getattr(L, n).argtypes = []
     for n in ("gsr_set_near_far_thread", "gsr_set_reference_rects_thread"):
@@ -159,6 +159,10 @@ def lib():
     L.gsr_photometric_loss_workspace.argtypes = [ci, ci, ci]
     L.gsr_photometric_loss.restype = ci
     L.gsr_photometric_loss.argtypes = [ci, ci, ci, vp, vp, C.POINTER(cf), cf, vp, vp, vp, sz, vp]
+    L.gsr_similarity_loss_workspace.restype = sz
+    L.gsr_similarity_loss_workspace.argtypes = [ci, ci]
+    L.gsr_similarity_loss.restype = ci
+    L.gsr_similarity_loss.argtypes = [ci, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp, ci, vp, sz, vp]
     L.gsr_init_gaussians.restype = ci
     L.gsr_init_gaussians.argtypes = [ci, ci, vp, vp, vp, cf] + [vp] * 6 + [vp]
     L.gsr_ply_row_floats.restype = sz
@@ -522,6 +526,28 @@ def photometric_loss(img, gt, window11, lambda_dssim, want_grad=True):
     _check(lib().gsr_photometric_loss(Cn, H, W, _ptr(img), _ptr(gt), win, float(lambda_dssim), _ptr(out3), _ptr(grad),
                                       _ptr(ws), nbytes, _stream()))
     return out3, grad
+
+
+def similarity_loss(points, sel, xyz, scaling, lambda_, grad_xyz=None, grad_scaling=None, accumulate=False):
+    """lambda * mean_i max(min_j |p_i - xyz[sel_j]| - mean(scaling[sel]), 0) in three launches (include/gsraster.h,
+    gsr_similarity_loss).  points [m,3] f32, sel [n] int32 (ascending, unique, < P), xyz / scaling [P,3] f32, all on
+    the device.  grad_xyz / grad_scaling: [P,3] buffers whose selected rows are written (accumulate=False) or added to
+    (accumulate=True); None = not wanted.  Returns out3 = [loss, mean clamped distance, r] (device tensor)."""
+    P, m, n = int(xyz.size(0)), int(points.size(0)), int(sel.size(0))
+    assert xyz.is_cuda and xyz.shape == (P, 3) and scaling.shape == (P, 3) and points.shape == (m, 3)
+    assert sel.dtype == torch.int32 and sel.dim() == 1
+    for t in (points, xyz, scaling, grad_xyz, grad_scaling):
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32)
+    assert sel.is_cuda and sel.is_contiguous()
+    for g in (grad_xyz, grad_scaling):
+        assert g is None or g.shape == (P, 3)
+    nbytes = int(lib().gsr_similarity_loss_workspace(m, n))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=xyz.device)
+    out3 = torch.empty(3, dtype=torch.float32, device=xyz.device)
+    _check(lib().gsr_similarity_loss(P, m, n, _ptr(points), _ptr(sel), _ptr(xyz), _ptr(scaling), float(lambda_),
+                                     _ptr(out3), _ptr(grad_xyz), _ptr(grad_scaling), int(bool(accumulate)), _ptr(ws),
+                                     nbytes, _stream()))
+    return out3
 
 
 # ---- "next" row 4: map growth and PLY export (include/gsraster.h; csrc/growth.hip) ----

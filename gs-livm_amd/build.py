@@ -32,6 +32,7 @@ UNITS = {
     "optimizer.hip": [],
     "loss.hip": ["-fno-slp-vectorize"],  # (packing the 11-tap sums costs more moves than it saves: 944 -> 732 VALU in the backward)
     "growth.hip": [],
+    "simi.hip": [],
     "api.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "gsr_internal.hpp"), os.path.join(CSRC, "sort_core.hpp"),

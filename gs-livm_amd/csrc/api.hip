@@ -93,7 +93,8 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_sort_hist", "k_sort_scan_chunks", "k_sort_scan_top", "k_sort_scatter", "k_tile_ranges", "k_blend_forward",
     "k_blend_backward", "k_compact_touched", "k_gather_records", "k_gaussian_backward", "k_mark_visible", "k_sort_hist[depth]",
     "k_sort_scan_chunks[depth]", "k_sort_scan_top[depth]", "k_sort_scatter[depth]", "k_activate",
-    "k_activate_backward", "k_adam", "k_loss_forward", "k_loss_finalize", "k_loss_backward", "k_init_gaussians", "k_pack_ply_rows", "k_model_step", "k_tile_order", "k_live_sat", "k_compact_near"};
+    "k_activate_backward", "k_adam", "k_loss_forward", "k_loss_finalize", "k_loss_backward", "k_init_gaussians", "k_pack_ply_rows", "k_model_step", "k_tile_order", "k_live_sat", "k_compact_near",
+    "k_simi_nearest", "k_simi_points", "k_simi_grads"};
 
 extern "C" {
 
@@ -1516,6 +1517,29 @@ int gsr_photometric_loss(int channels, int height, int width, const float* img, 
                 loss_workspace_bytes(channels, height, width));
   HIP_TRY(launch_photometric_loss(channels, height, width, img, gt, window11_host, lambda_dssim, loss_out3, dL_dimg,
                                   workspace, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+size_t gsr_similarity_loss_workspace(int m, int n) {
+  if (m <= 0 || n <= 0 || n > 0x7fffffff - 1024) return 0;
+  return simi_workspace_bytes(m, n);
+}
+
+int gsr_similarity_loss(int P, int m, int n, const float* points, const int* sel, const float* xyz,
+                        const float* scaling, float lambda, float* out3, float* grad_xyz, float* grad_scaling,
+                        int accumulate, char* workspace, size_t workspace_bytes, void* stream_) {
+  g_err[0] = 0;
+  if (P < 0 || m < 0 || n < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/m/n");
+  if (n > P) return fail(GSR_ERR_INVALID_ARGUMENT, "n = %d selected rows of P = %d (the selection is unique)", n, P);
+  if (n > 0x7fffffff - 1024) return fail(GSR_ERR_INVALID_ARGUMENT, "n too large");
+  if (!out3) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (m > 0 && n > 0) {
+    if (!points || !sel || !xyz || !scaling || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+    if (workspace_bytes < simi_workspace_bytes(m, n))
+      return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes", simi_workspace_bytes(m, n));
+  }
+  HIP_TRY(launch_similarity_loss(P, m, n, points, sel, xyz, scaling, lambda, out3, grad_xyz, grad_scaling,
+                                 accumulate ? 1 : 0, workspace, (hipStream_t)stream_));
   return GSR_OK;
 }
 

@@ -407,6 +407,11 @@ hipError_t launch_activate_backward(int P, int M, const float* rotation_raw, con
 size_t loss_workspace_bytes(int C, int H, int W);
 hipError_t launch_photometric_loss(int C, int H, int W, const float* img, const float* gt, const float* window11,
                                    float lambda, float* loss_out3, float* dL_dimg, char* workspace, hipStream_t s);
+// simi.hip (the LiDAR similarity loss: nearest selected Gaussian per point, one clamp, deterministic gradients)
+size_t simi_workspace_bytes(int m, int n);
+hipError_t launch_similarity_loss(int P, int m, int n, const float* points, const int* sel, const float* xyz,
+                                  const float* scaling, float lambda, float* out3, float* grad_xyz,
+                                  float* grad_scaling, int accumulate, char* workspace, hipStream_t s);
 hipError_t launch_init_gaussians(int n, int M, const float* xyz, const float* covs, const float* rgbs, float scale_factor,
                                  float* xyz_out, float* fdc_out, float* frest_out, float* scaling_out,
                                  float* rotation_out, float* opacity_out, hipStream_t s);
@@ -430,7 +435,8 @@ enum KernelId {
   K_PREPROCESS = 0, K_POINT_OFFSETS, K_SCAN_OFFSETS, K_EMIT, K_SORT_HIST,
   K_SORT_SCAN_CHUNKS, K_SORT_SCAN_TOP, K_SORT_SCATTER, K_TILE_RANGES, K_BLEND_FWD, K_BLEND_BWD, K_COMPACT_TOUCHED,
   K_GATHER_RECORDS, K_GAUSSIAN_BWD, K_MARK_VISIBLE, K_DSORT_HIST, K_DSORT_SCAN_CHUNKS, K_DSORT_SCAN_TOP,
-  K_DSORT_SCATTER, K_ACTIVATE, K_ACTIVATE_BWD, K_ADAM, K_LOSS_FWD, K_LOSS_FINALIZE, K_LOSS_BWD, K_INIT_GAUSSIANS, K_PACK_PLY, K_MODEL_STEP, K_TILE_ORDER, K_LIVE_SAT, K_COMPACT_NEAR, K_COUNT
+  K_DSORT_SCATTER, K_ACTIVATE, K_ACTIVATE_BWD, K_ADAM, K_LOSS_FWD, K_LOSS_FINALIZE, K_LOSS_BWD, K_INIT_GAUSSIANS, K_PACK_PLY, K_MODEL_STEP, K_TILE_ORDER, K_LIVE_SAT, K_COMPACT_NEAR,
+  K_SIMI_NEAREST, K_SIMI_POINTS, K_SIMI_GRADS, K_COUNT
 };
 void prof_begin(int id, hipStream_t s);
 void prof_end(hipStream_t s);

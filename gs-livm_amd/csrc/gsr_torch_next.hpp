@@ -8,8 +8,12 @@
 #pragma once
 #include <torch/torch.h>
 
+#include <cstddef>
+#include <cstdint>
 #include <string>
 #include <tuple>
+#include <unordered_map>
+#include <utility>
 #include <vector>
 
 namespace gsr_torch {
@@ -28,6 +32,36 @@ torch::Tensor photometric_loss(const torch::Tensor& image, const torch::Tensor& 
 // [loss, l1, ssim] of the same evaluation, no graph (the reference logs PSNR / SSIM every 50 iterations)
 torch::Tensor photometric_loss_parts(const torch::Tensor& image, const torch::Tensor& gt, float lambda_dssim = 0.2f,
                                      const torch::Tensor& window1d = torch::Tensor());
+
+// ---- the LiDAR similarity loss (optimize_vis step 3) ---------------------------------------------------------------
+// lambda * compute_min_distance(points, Get_xyz()[sel], Get_scaling()[sel]) (src/gs/gaussian.cu:87-114, 230-237) as ONE
+// autograd node on the kernels of csrc/simi.hip: points [m,3] f32 and sel [n] int32 (ascending unique rows) on the
+// device, from VoxelIndex::select; xyz = the model's _xyz [P,3]; scaling = its ACTIVATED scales [P,3].  Gradients
+// w.r.t. xyz and scaling, dense and zero outside the selection.  Returns the 0-dim loss.
+torch::Tensor similarity_loss(const torch::Tensor& points, const torch::Tensor& sel, const torch::Tensor& xyz,
+                              const torch::Tensor& scaling, float lambda = 0.2f);
+
+// gs_hash_indexes_ (voxel key -> rows of its Gaussians, gaussian.cu:257-263) kept as ranges -- the reference's row
+// vectors are an iota from the running model size (src/liw/lioOptimization.cpp:1268-1279) -- and the selection of
+// calcSimiLoss (gaussian.cu:201-228) on them.
+class VoxelIndex {
+ public:
+  // The voxels `keys` contributed counts[i] consecutive rows each, from first_row on (pcd.hash_posi_s / pcd.indexes).
+  // Returns the row after the last.  A key that is known already, or given twice, throws and registers nothing (the
+  // reference ends the program there, gaussian.cu:258-262); a count of 0 registers a key without rows.
+  int64_t add(const std::vector<std::size_t>& keys, const std::vector<int64_t>& counts, int64_t first_row);
+  // Steps 1-2 of calcSimiLoss for GSLIVM::GsForLosses::_losses ({key: [k,3] f32 CPU}): the points of every known key
+  // (ascending key order), cut to exactly max_points by torch::randperm when there are that many or more
+  // (MAX_SIMI, include/gs/gp3d/gp_types.h:15), and the ascending unique rows of those keys as int32, both copied to
+  // `device` without waiting.  false where the reference returns false (no point left; also: no row to compare with).
+  bool select(const std::unordered_map<std::size_t, torch::Tensor>& losses, torch::Tensor& points, torch::Tensor& sel,
+              int64_t max_points = 500, torch::Device device = torch::kCUDA) const;
+  std::size_t size() const { return ranges_.size(); }
+  bool contains(std::size_t key) const { return ranges_.count(key) > 0; }
+
+ private:
+  std::unordered_map<std::size_t, std::pair<int64_t, int64_t>> ranges_;  // key -> (first_row, count)
+};
 
 // ---- row 1: activations + Adam ----------------------------------------------------------------------------------
 // The five getters of GaussianModel (include/gs/gs/gaussian.cuh:40-54) as one autograd node:

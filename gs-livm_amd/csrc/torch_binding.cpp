@@ -369,6 +369,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           return nx::photometric_loss_parts(image, gt, lambda_dssim, opt(window));
         },
         py::arg("image"), py::arg("gt"), py::arg("lambda_dssim") = 0.2f, py::arg("window1d") = py::none());
+  n.def("similarity_loss", &nx::similarity_loss, py::arg("points"), py::arg("sel"), py::arg("xyz"), py::arg("scaling"),
+        py::arg("lambda_") = 0.2f);
+  py::class_<nx::VoxelIndex>(n, "VoxelIndex")
+      .def(py::init<>())
+      .def("add", &nx::VoxelIndex::add, py::arg("keys"), py::arg("counts"), py::arg("first_row"))
+      .def("select",
+           [](const nx::VoxelIndex& self, const std::unordered_map<std::size_t, torch::Tensor>& losses,
+              int64_t max_points, const std::string& device) -> py::object {
+             torch::Tensor points, sel;
+             if (!self.select(losses, points, sel, max_points, torch::Device(device))) return py::none();
+             return py::make_tuple(points, sel);
+           },
+           py::arg("losses"), py::arg("max_points") = 500, py::arg("device") = "cuda")
+      .def("__len__", &nx::VoxelIndex::size)
+      .def("__contains__", &nx::VoxelIndex::contains);
   n.def("activate", [](torch::Tensor s, torch::Tensor r, torch::Tensor o, torch::Tensor dc, torch::Tensor rest) {
     const nx::Activated a = nx::activate(s, r, o, dc, rest);
     return std::make_tuple(a.scaling, a.rotation, a.opacity, a.features);

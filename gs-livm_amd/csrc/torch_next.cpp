@@ -10,13 +10,16 @@
 //   _optimizer->step() / zero_grad()                       src/gs/gaussian.cu:396-428, lioOptimization.cpp:1831-1832
 //   the tensor construction of addNewPointcloud            src/gs/gaussian.cu:241-313
 //   Save_ply / Write_output_ply                            src/gs/gaussian.cu:494-573
+//   compute_min_distance + the selection of calcSimiLoss   src/gs/gaussian.cu:87-114, 201-239
 #include "gsr_torch_next.hpp"
 
 #include <c10/hip/HIPStream.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <stdexcept>
+#include <unordered_set>
 
 #include "gsraster.h"
 
@@ -79,6 +82,38 @@ struct PhotometricLossFn : public torch::autograd::Function<PhotometricLossFn> {
   }
 };
 
+struct SimilarityLossFn : public torch::autograd::Function<SimilarityLossFn> {
+  static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor points, torch::Tensor sel,
+                               torch::Tensor xyz, torch::Tensor scaling, double lambda) {
+    const torch::Tensor p = dev_f32(points, "points"), x = dev_f32(xyz, "xyz"), s = dev_f32(scaling, "scaling");
+    if (!sel.defined() || !sel.is_cuda() || sel.scalar_type() != torch::kInt32 || sel.dim() != 1)
+      throw std::invalid_argument("similarity_loss: sel is a 1-d int32 tensor on the device");
+    if (p.dim() != 2 || p.size(1) != 3 || x.dim() != 2 || x.size(1) != 3 || s.sizes() != x.sizes())
+      throw std::invalid_argument("similarity_loss: points [m,3], xyz [P,3], scaling [P,3]");
+    const torch::Tensor rows = sel.contiguous();
+    const int P = x.size(0), m = p.size(0), n = rows.size(0);
+    torch::Tensor gx = xyz.requires_grad() ? torch::zeros_like(x) : torch::Tensor();
+    torch::Tensor gs = scaling.requires_grad() ? torch::zeros_like(s) : torch::Tensor();
+    const size_t nbytes = gsr_similarity_loss_workspace(m, n);
+    torch::Tensor ws = torch::empty({static_cast<long long>(nbytes ? nbytes : 1)}, x.options().dtype(torch::kByte));
+    torch::Tensor out3 = torch::empty({3}, x.options());
+    check(gsr_similarity_loss(P, m, n, fp(p), n ? rows.data_ptr<int>() : nullptr, fp(x), fp(s),
+                              static_cast<float>(lambda), out3.data_ptr<float>(), fp(gx), fp(gs), 0,
+                              reinterpret_cast<char*>(ws.data_ptr()), nbytes, current_stream()),
+          "gsr_similarity_loss");
+    ctx->save_for_backward({gx.defined() ? gx : torch::empty({0}, x.options()),
+                            gs.defined() ? gs : torch::empty({0}, x.options())});
+    return out3[0];
+  }
+  static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx,
+                                               torch::autograd::tensor_list grad_outputs) {
+    const auto saved = ctx->get_saved_variables();
+    const torch::Tensor gx = saved[0], gs = saved[1], g = grad_outputs[0];
+    return {torch::Tensor(), torch::Tensor(), gx.numel() ? gx * g : torch::Tensor(),
+            gs.numel() ? gs * g : torch::Tensor(), torch::Tensor()};
+  }
+};
+
 struct ActivateFn : public torch::autograd::Function<ActivateFn> {
   static torch::autograd::tensor_list forward(torch::autograd::AutogradContext* ctx, torch::Tensor scaling_raw,
                                               torch::Tensor rotation_raw, torch::Tensor opacity_raw,
@@ -135,6 +170,60 @@ torch::Tensor photometric_loss_parts(const torch::Tensor& image, const torch::Te
                                      const torch::Tensor& window1d) {
   torch::NoGradGuard no_grad;
   return run_loss(image, gt, lambda_dssim, window1d, false).first;
+}
+
+torch::Tensor similarity_loss(const torch::Tensor& points, const torch::Tensor& sel, const torch::Tensor& xyz,
+                              const torch::Tensor& scaling, float lambda) {
+  return SimilarityLossFn::apply(points, sel, xyz, scaling, static_cast<double>(lambda));
+}
+
+int64_t VoxelIndex::add(const std::vector<std::size_t>& keys, const std::vector<int64_t>& counts, int64_t first_row) {
+  if (keys.size() != counts.size()) throw std::invalid_argument("VoxelIndex::add: one count per key");
+  std::unordered_set<std::size_t> seen;
+  for (size_t i = 0; i < keys.size(); i++) {
+    if (counts[i] < 0) throw std::invalid_argument("VoxelIndex::add: negative count");
+    if (ranges_.count(keys[i]) || !seen.insert(keys[i]).second)
+      throw std::invalid_argument("VoxelIndex::add: voxel key " + std::to_string(keys[i]) + " duplicated");
+  }
+  int64_t row = first_row;
+  for (size_t i = 0; i < keys.size(); i++) {
+    ranges_.emplace(keys[i], std::make_pair(row, counts[i]));
+    row += counts[i];
+  }
+  return row;
+}
+
+bool VoxelIndex::select(const std::unordered_map<std::size_t, torch::Tensor>& losses, torch::Tensor& points,
+                        torch::Tensor& sel, int64_t max_points, torch::Device device) const {
+  std::vector<std::size_t> hit;
+  for (const auto& kv : losses)
+    if (ranges_.count(kv.first)) hit.push_back(kv.first);
+  if (hit.empty()) return false;
+  std::sort(hit.begin(), hit.end());
+  std::vector<torch::Tensor> pts;
+  std::vector<std::pair<int64_t, int64_t>> rng;
+  int64_t n = 0;
+  for (const std::size_t k : hit) {
+    pts.push_back(losses.at(k).to(torch::kCPU, torch::kFloat32).reshape({-1, 3}));
+    const auto r = ranges_.at(k);
+    if (r.second > 0) { rng.push_back(r); n += r.second; }
+  }
+  torch::Tensor p = torch::cat(pts, 0);
+  const int64_t m = p.size(0);
+  if (m == 0 || n == 0) return false;
+  std::sort(rng.begin(), rng.end());
+  torch::Tensor rows = torch::empty({n}, torch::kInt32);
+  int* out = rows.data_ptr<int>();
+  int64_t w = 0, next = -1;  // `next`: the first row no earlier range has written (ranges may overlap: rows stay unique)
+  for (const auto& r : rng)
+    for (int64_t row = std::max(r.first, next); row < r.first + r.second; row++) { out[w++] = static_cast<int>(row); next = row + 1; }
+  rows = rows.narrow(0, 0, w);
+  if (m >= max_points) p = p.index_select(0, torch::randperm(m).slice(0, 0, max_points));
+  p = p.contiguous();
+  if (device.is_cuda()) { p = p.pin_memory(); rows = rows.contiguous().pin_memory(); }
+  points = p.to(device, /*non_blocking=*/true);
+  sel = rows.to(device, /*non_blocking=*/true);
+  return true;
 }
 
 Activated activate(const torch::Tensor& scaling_raw, const torch::Tensor& rotation_raw, const torch::Tensor& opacity_raw,

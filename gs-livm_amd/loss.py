@@ -1,5 +1,6 @@
 """Host-side mirror of the reference's image loss (include/gs/gs/loss_utils.cuh) on the fused kernels of
-csrc/loss.hip (SURVEY.md section 8(f) "next" row 2)."""
+csrc/loss.hip (SURVEY.md section 8(f) "next" row 2), and of its LiDAR similarity loss
+(GaussianModel::compute_min_distance, src/gs/gaussian.cu:87-114) on those of csrc/simi.hip."""
 import math
 
 import torch
@@ -39,3 +40,35 @@ def photometric_loss(img, gt, lambda_dssim=0.2, window11=None):
     if window11 is None:
         window11 = reference_window_1d()
     return PhotometricLoss.apply(img, gt, window11, float(lambda_dssim))
+
+
+class SimilarityLoss(torch.autograd.Function):
+    """loss = lambda * compute_min_distance(points, xyz[sel], scaling[sel]) (src/gs/gaussian.cu:87-114, 230-237) as
+    one node; gradients w.r.t. xyz and the ACTIVATED scaling (points and sel are data).  The gradients are dense [P,3]
+    tensors that are zero outside the selection, so autograd adds them to whatever else flows into `xyz` and `scaling`:
+    the rasterizer's gradients, on either activation path of model.py (FusedActivations runs its chain rule on the
+    sum, the stashing tail parks the sum in `_act_grads`)."""
+
+    @staticmethod
+    def forward(ctx, points, sel, xyz, scaling, lambda_):
+        xyz_c, scaling_c = xyz.contiguous(), scaling.contiguous()
+        need_x, need_s = ctx.needs_input_grad[2], ctx.needs_input_grad[3]
+        gx = torch.zeros_like(xyz_c) if need_x else None
+        gs = torch.zeros_like(scaling_c) if need_s else None
+        out3 = _capi.similarity_loss(points.contiguous(), sel.contiguous(), xyz_c, scaling_c, lambda_, gx, gs)
+        ctx.grads = (gx, gs)
+        ctx.parts = out3  # [loss, mean clamped distance, r] for logging
+        return out3[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        gx, gs = ctx.grads
+        return None, None, (gx * g if gx is not None else None), (gs * g if gs is not None else None), None
+
+
+def similarity_loss(points, sel, xyz, scaling, lambda_=0.2):
+    """Drop-in for `lambda * compute_min_distance(selected_points, xyz_for_loss, scale_for_loss)`
+    (src/gs/gaussian.cu:237; lambda_depth_simi: config/basic_common.yaml:64) without the two index_select: points
+    [m,3] f32 and sel [n] int32 (ascending unique rows) come from `VoxelIndex.select` (model.py), xyz is the model's
+    _xyz and scaling its activated scales.  Returns the 0-dim loss."""
+    return SimilarityLoss.apply(points, sel, xyz, scaling, float(lambda_))

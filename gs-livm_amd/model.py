@@ -9,8 +9,11 @@ kernels of csrc/optimizer.hip (SURVEY.md section 8(f) "next" row 1):
     the gradients it consumed (step + zero_grad, src/liw/lioOptimization.cpp:1831-1832);
   * `GrowableGaussians` -- row 4: the model as capacity buffers that grow in place
     (GaussianModel::addNewPointcloud / densification_postfix / cat_tensors_to_optimizer,
-    src/gs/gaussian.cu:241-313, 451-472, 524-540).
+    src/gs/gaussian.cu:241-313, 451-472, 524-540);
+  * `VoxelIndex` -- gs_hash_indexes_ (voxel key -> rows of its Gaussians, gaussian.cu:257-263) and the selection
+    of calcSimiLoss (:201-228) on row RANGES, which feeds the fused similarity loss (csrc/simi.hip, loss.py).
 """
+import numpy as np
 import torch
 
 from . import _capi
@@ -185,6 +188,89 @@ class FusedAdam(torch.optim.Optimizer):
         model._xyz.grad = None
 
 
+class VoxelIndex:
+    """voxel key -> (first_row, count): the rows of the Gaussians a voxel contributed to the model.
+
+    The reference keeps one std::vector<int> of row numbers per key (gs_hash_indexes_, filled by addNewPointcloud,
+    src/gs/gaussian.cu:257-263), but those vectors are always an iota from the running model size
+    (src/liw/lioOptimization.cpp:1268-1279), so a range says the same.  A duplicate key is an error, as there
+    (:258-262, where it ends the program); a voxel whose sample was empty registers a key without rows (:1268-1273).
+    """
+
+    def __init__(self, device=None):
+        self.device = torch.device(device) if device is not None else torch.device("cpu")
+        self._ranges = {}
+
+    def __len__(self):
+        return len(self._ranges)
+
+    def __contains__(self, key):
+        return int(key) in self._ranges
+
+    def get(self, key):
+        """(first_row, count) of a key, or None."""
+        return self._ranges.get(int(key))
+
+    def add(self, keys, counts, first_row):
+        """Registers len(keys) voxels whose Gaussians lie one after another from `first_row`; returns the row after
+        the last.  Raises (and registers nothing) on a key that is already known or given twice."""
+        keys = [int(k) for k in keys]
+        counts = [int(c) for c in counts]
+        if len(keys) != len(counts):
+            raise ValueError("VoxelIndex.add: %d keys, %d counts" % (len(keys), len(counts)))
+        if any(c < 0 for c in counts):
+            raise ValueError("VoxelIndex.add: negative count")
+        seen = set()
+        for k in keys:
+            if k in self._ranges or k in seen:
+                raise KeyError("VoxelIndex.add: voxel key %d duplicated" % k)
+            seen.add(k)
+        row = int(first_row)
+        for k, c in zip(keys, counts):
+            self._ranges[k] = (row, c)
+            row += c
+        return row
+
+    def select(self, losses, max_points=500, generator=None):
+        """Steps 1-2 of GaussianModel::calcSimiLoss (src/gs/gaussian.cu:201-228) on the host.
+
+        losses: {voxel key: [k,3] f32 CPU tensor}, GsForLosses::_losses as processAndMergeLosses leaves it
+        (src/liw/lioOptimization.cpp:459-476).  Every key this index knows contributes its rows and its points (in
+        ascending key order, so that the result does not depend on the order of the map), the others neither.
+        `max_points` or more points are cut to exactly `max_points` by torch.randperm on the CPU (:226-228, MAX_SIMI).
+        Returns (points [m,3] f32, sel [n] int32 = the ascending unique rows, what loss_mask.nonzero() yields) on
+        `self.device` through non-blocking copies, or None where the reference returns false (no point left) and
+        where it has no Gaussian to compare with (every matched voxel empty)."""
+        ranges = self._ranges
+        hit = sorted(k for k in losses if k in ranges)
+        if not hit:
+            return None
+        pts = [losses[k] for k in hit]
+        if not all(type(t) is torch.Tensor and t.dtype == torch.float32 and t.dim() == 2 for t in pts):
+            pts = [torch.as_tensor(t, dtype=torch.float32).reshape(-1, 3) for t in pts]  # (arrays, lists, [3] rows)
+        points = torch.cat(pts, 0) if len(pts) > 1 else pts[0]
+        m = int(points.size(0))
+        rng = np.array([ranges[k] for k in hit], dtype=np.int64).reshape(-1, 2)
+        rng = rng[rng[:, 1] > 0]
+        if m == 0 or rng.shape[0] == 0:
+            return None
+        rng = rng[np.argsort(rng[:, 0], kind="stable")]
+        first, count = rng[:, 0], rng[:, 1]
+        # rows of all ranges, one after another: each range's own iota = global iota - (rows before it) + its first
+        before = np.cumsum(count) - count
+        rows = np.arange(int(count.sum()), dtype=np.int64) + np.repeat(first - before, count)
+        if np.any(first[1:] < first[:-1] + count[:-1]):  # overlapping ranges (not what add() lays out, but legal)
+            rows = np.unique(rows)
+        if m >= max_points:
+            keep = torch.randperm(m, generator=generator)[:max_points]
+            points = points.index_select(0, keep)
+        sel = torch.from_numpy(rows.astype(np.int32))
+        points = points.contiguous()
+        if self.device.type == "cuda":  # pinned staging: the copies are queued, the host does not wait for them
+            sel, points = sel.pin_memory(), points.pin_memory()
+        return points.to(self.device, non_blocking=True), sel.to(self.device, non_blocking=True)
+
+
 class GrowableGaussians(GaussianParameters):
     """The six leaves and their Adam moments as CAPACITY buffers; the leaves are views of the first P rows.
 
@@ -205,6 +291,7 @@ class GrowableGaussians(GaussianParameters):
         self.M, self.P, self.capacity, self.device = int(M), 0, 0, torch.device(device)
         self._buf, self._m, self._v = {}, {}, {}
         self._optimizer = None
+        self.voxel_index = VoxelIndex(self.device)  # gs_hash_indexes_
         self._reserve(max(1, int(capacity)))
         self._bind()
 
@@ -237,10 +324,21 @@ class GrowableGaussians(GaussianParameters):
         self._optimizer = optimizer
 
     @torch.no_grad()
-    def add_new_pointcloud(self, xyz, covs, rgbs, scale_factor=1.0):
+    def add_new_pointcloud(self, xyz, covs, rgbs, scale_factor=1.0, voxel_keys=None, voxel_counts=None):
         """GaussianModel::addNewPointcloud (src/gs/gaussian.cu:241-313): xyz [n,3], covs [n,3,3], rgbs [n,3] (0..255),
-        device f32.  Returns the row range of the new Gaussians."""
+        device f32.  Returns the row range of the new Gaussians.
+        voxel_keys / voxel_counts (optional, host sequences): the voxels the points came from, in the order of the
+        rows, and how many rows each contributed (pcd.hash_posi_s / pcd.indexes, :257-263); they are registered in
+        `self.voxel_index` at [P_old, ...).  A duplicate key or counts that do not sum to n raise before anything
+        changes."""
         n = int(xyz.size(0))
+        if (voxel_keys is None) != (voxel_counts is None):
+            raise ValueError("add_new_pointcloud: voxel_keys and voxel_counts go together")
+        if voxel_keys is not None:
+            if sum(int(c) for c in voxel_counts) != n:
+                raise ValueError("add_new_pointcloud: voxel_counts sum to %d, %d rows given"
+                                 % (sum(int(c) for c in voxel_counts), n))
+            self.voxel_index.add(voxel_keys, voxel_counts, self.P)
         if n == 0:
             return self.P, self.P
         if self.P + n > self.capacity:
@@ -253,6 +351,20 @@ class GrowableGaussians(GaussianParameters):
         self.P = hi
         self._bind()
         return lo, hi
+
+    def calc_simi_loss(self, losses, lambda_=0.2, scaling=None, max_points=500, generator=None):
+        """GaussianModel::calcSimiLoss (src/gs/gaussian.cu:201-239): the similarity loss of the LiDAR points in
+        `losses` ({voxel key: [k,3] CPU f32}) against the Gaussians of their voxels, or None where the reference
+        returns false.  scaling: the activated scales of this iteration's `activated()` call, so that the term shares
+        the rasterizer's node; None runs the getter, as the reference does."""
+        from .loss import similarity_loss
+        picked = self.voxel_index.select(losses, max_points=max_points, generator=generator)
+        if picked is None:
+            return None
+        points, sel = picked
+        if scaling is None:
+            scaling = self.Get_scaling()
+        return similarity_loss(points, sel, self._xyz, scaling, lambda_)
 
 
 class GrowableAdam(FusedAdam):

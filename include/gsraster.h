@@ -321,6 +321,28 @@ int gsr_photometric_loss(int channels, int height, int width, const float* img, 
                          const float* window11_host, float lambda_dssim, float* loss_out3, float* dL_dimg,
                          char* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the LiDAR similarity loss (step 3 of optimize_vis), fused ----
+ *   r = mean(scaling[sel]) (one scalar over the 3n selected elements),  d_ij = |points_i - xyz[sel_j]|,
+ *   L = lambda * mean_i min_j max(d_ij - r, 0) = lambda / m * sum_i max(min_j d_ij - r, 0)
+ * replaces GaussianModel::compute_min_distance (src/gs/gaussian.cu:87-114) as calcSimiLoss calls it (:201-239; call
+ * site src/liw/lioOptimization.cpp:1675, lambda_depth_simi of config/basic_common.yaml:64) and its autograd: the
+ * [m,n,3] expansions there, a nearest-neighbour search and one clamp per point here, in three launches.
+ * points [m,3] device f32: the LiDAR points that are left after selection and subsampling (the cap of MAX_SIMI = 500,
+ * include/gs/gp3d/gp_types.h:15, is the host's policy; m and n are bounded by int only).  sel [n] device int32: the
+ * rows of the selected voxels' Gaussians, ascending, unique, each < P (what loss_mask.nonzero() yields, :219-221).
+ * xyz [P,3]: the model's _xyz; scaling [P,3]: the ACTIVATED scales (Get_scaling()).
+ * out3 (device) = {L, mean clamped distance (L before lambda), r}.
+ * grad_xyz / grad_scaling (nullable, [P,3]) = dL/dxyz, dL/dscaling for upstream gradient 1: with accumulate = 0 the
+ * selected rows are WRITTEN and every other row is left untouched (the caller owns zero-filling), with accumulate = 1
+ * the selected rows are ADDED TO, so that the term lands in the buffers the rasterizer's backward already filled.
+ * A point with min_j d_ij <= r contributes nothing; of two centres at bit-equal distance the earlier in sel is taken
+ * (the reference leaves both cases to Torch's tie rules).  m == 0 or n == 0: returns 0 with out3 = {0, 0, 0}.
+ * Deterministic (no float atomics, fixed-order reductions), no host synchronisation; workspace sized by the query. */
+size_t gsr_similarity_loss_workspace(int m, int n);
+int gsr_similarity_loss(int P, int m, int n, const float* points, const int* sel, const float* xyz,
+                        const float* scaling, float lambda, float* out3, float* grad_xyz, float* grad_scaling,
+                        int accumulate, char* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- "next" row: the data formats either side of the path ----
  * gsr_init_gaussians: new map points -> leaf parameter rows, the arithmetic of GaussianModel::addNewPointcloud
  * (src/gs/gaussian.cu:241-313): _xyz = xyz; _scaling = log(sqrt(diag(cov) * scale_factor)) (decomposeSR keeps the
