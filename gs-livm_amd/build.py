@@ -13,7 +13,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
-# experiment hooks (A/B builds): extra flags for render.hip and a suffix for the library / object names
+# experiment hooks (A/B builds): GSR_EXTRA_FLAGS for every unit and a suffix for the library / object names
 SUFFIX = os.environ.get("GSR_LIB_SUFFIX", "")
 LIB = os.path.join(HERE, "libgsraster_hip%s.so" % SUFFIX)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -28,7 +28,7 @@ UNITS = {
     "radix_sort.hip": [],
     # SLP vectorisation packs the scalar f32 math into v_pk_* and splits the fused v_add_f32_dpp reductions
     # into mov_dpp + pk_add: measured 9 % slower on k_blend_backward, so it is off for the blend kernels.
-    "render.hip": ["-ffp-contract=fast", "-fno-slp-vectorize"] + os.environ.get("GSR_EXTRA_RENDER_FLAGS", "").split(),
+    "render.hip": ["-ffp-contract=fast", "-fno-slp-vectorize"],
     "optimizer.hip": [],
     "loss.hip": ["-fno-slp-vectorize"],  # (packing the 11-tap sums costs more moves than it saves: 944 -> 732 VALU in the backward)
     "growth.hip": [],

@@ -56,6 +56,41 @@ static int fail(int code, const char* fmt, ...) {
     if (debug) HIP_TRY(hipStreamSynchronize(stream));                                             \
   } while (0)
 
+// ---- environment switches (gsr_internal.hpp: struct Env) -----------------------------------------
+namespace gsr {
+const Env& env() {
+  static const Env e = [] {
+    const auto set = [](const char* v) { return v != nullptr; };
+    const auto not_zero = [](const char* v) { return !(v && v[0] == '0'); };
+    Env x;
+    const char* v = getenv("GSR_REFERENCE_RECTS");
+    x.reference_rects = v && v[0] && v[0] != '0';
+    x.near_far = not_zero(getenv("GSR_NEAR_FAR"));
+    x.async_far = not_zero(getenv("GSR_ASYNC_FAR"));
+    x.sync_forward = set(getenv("GSR_SYNC_FORWARD"));
+    v = getenv("GSR_NEAR_ENTRIES");
+    x.near_entries = v ? atol(v) : 320;
+    v = getenv("GSR_NEAR_FAR_MIN_RATIO_Q2");
+    x.near_far_min_ratio_q2 = v ? strtoull(v, nullptr, 10) : 12ull;
+    x.full_depth_sort = set(getenv("GSR_FULL_DEPTH_SORT"));
+    x.depth_hist_pass = set(getenv("GSR_DEPTH_HIST_PASS"));
+    v = getenv("GSR_PRE_HIST_MIN_P");
+    x.pre_hist_min_p = v ? std::max(0L, atol(v)) : -1;  // (a count of Gaussians: nothing lies below 0)
+    x.ranges_from_keys = set(getenv("GSR_RANGES_FROM_KEYS"));
+    x.tile_sort_lsd = set(getenv("GSR_TILE_SORT_LSD"));
+    x.sort_two_level_scan = set(getenv("GSR_SORT_TWO_LEVEL_SCAN"));
+    x.sort_ballot_rank = set(getenv("GSR_SORT_BALLOT_RANK"));
+    x.blend_backward_quads = set(getenv("GSR_BLEND_BACKWARD_QUADS"));
+    x.blend_backward_tiles = set(getenv("GSR_BLEND_BACKWARD_TILES"));
+    x.bwd_image_order = set(getenv("GSR_BWD_IMAGE_ORDER"));
+    x.gbwd_all = set(getenv("GSR_GBWD_ALL"));
+    x.host_trace = set(getenv("GSR_HOST_TRACE"));
+    return x;
+  }();
+  return e;
+}
+}  // namespace gsr
+
 // ---- optional event profiler -------------------------------------------------------------------
 namespace gsr {
 std::atomic<bool> g_prof_on{false};
@@ -189,10 +224,7 @@ size_t gsr_binning_bytes(int R) {
 
 // Binning mode (gsraster.h, gsr_set_reference_rects): process-wide, initialised once from GSR_REFERENCE_RECTS.
 static std::atomic<int>& reference_rects_flag() {
-  static std::atomic<int> flag([] {
-    const char* e = getenv("GSR_REFERENCE_RECTS");
-    return (e && e[0] && e[0] != '0') ? 1 : 0;
-  }());
+  static std::atomic<int> flag(env().reference_rects ? 1 : 0);
   return flag;
 }
 
@@ -409,7 +441,7 @@ static int wait_num_rendered(ThreadCtx& c, hipStream_t stream, uint32_t* R_out, 
         g_slow_last.count = (unsigned)(g_mailbox_slow_hits.load() + 1);
       }
       const unsigned long long hits = ++g_mailbox_slow_hits;
-      if (hits <= 3 || getenv("GSR_HOST_TRACE"))
+      if (hits <= 3 || env().host_trace)
         fprintf(stderr, "[gsr] mailbox slow path #%llu: ticket %u, seen %u before / %u right after hipStreamQuery (=%d), "
                         "%.1f us after the enqueue (%u queries, the longest took %.1f us; longest gap between two polls "
                         "%.1f us): %s\n", hits, c.ticket, (uint32_t)(v >> 32), (uint32_t)(v1 >> 32), (int)q,
@@ -507,8 +539,7 @@ ThreadCtx::~ThreadCtx() {
 static bool async_far_ready(ThreadCtx& c) {
   if (c.async_state) return c.async_state > 0;
   c.async_state = -1;
-  const char* e = getenv("GSR_ASYNC_FAR");
-  if (e && e[0] == '0') return false;
+  if (!env().async_far) return false;
   const void* none = nullptr;
   if (!g_async_owner.compare_exchange_strong(none, &c) && none != &c) return false;
   int can = 0;
@@ -766,24 +797,6 @@ struct DepthOrder {
   const uint32_t* ghist;       // k_preprocess's digit counts of all P keys (for that full sort), or null
 };
 
-// The environment variables a forward reads (gsraster.h), once per process (forward_env).
-struct ForwardEnv {
-  // GSR_ASYNC_FAR_MT=1, diagnostics: asynchronous frames although several threads render -- the combination that faulted
-  bool async_mt = getenv("GSR_ASYNC_FAR_MT") != nullptr;
-  bool depth_hist_pass = getenv("GSR_DEPTH_HIST_PASS") != nullptr;  // the depth sort's own histogram pass
-  bool sync_forward = getenv("GSR_SYNC_FORWARD") != nullptr;        // every forward synchronous
-  bool host_trace = getenv("GSR_HOST_TRACE") != nullptr;            // diagnostics: host-side waits
-  long near_entries = getenv("GSR_NEAR_ENTRIES") ? atol(getenv("GSR_NEAR_ENTRIES")) : 320;  // near budget per tile
-  unsigned long long near_far_min_ratio_q2 =
-      getenv("GSR_NEAR_FAR_MIN_RATIO_Q2") ? strtoull(getenv("GSR_NEAR_FAR_MIN_RATIO_Q2"), nullptr, 10) : 12ull;
-  bool full_depth_sort = getenv("GSR_FULL_DEPTH_SORT") != nullptr;    // diagnostics / fallback: no partial depth sort
-  bool ranges_from_keys = getenv("GSR_RANGES_FROM_KEYS") != nullptr;  // diagnostics / fallback (enqueue_chain)
-};
-static const ForwardEnv& forward_env() {
-  static const ForwardEnv env;
-  return env;
-}
-
 // One forward, as the functions that enqueue its parts see it.
 struct Forward {
   const FrameParams& fp;
@@ -791,7 +804,6 @@ struct Forward {
   ImageState& im;
   ThreadCtx& c;
   ViewHist& h;      // the view's history (view_hist)
-  const ForwardEnv& env;
   DepthOrder dord;  // (enqueue_depth_order)
   const float* background;
   float *out_color, *out_depth, *out_acc;
@@ -862,7 +874,7 @@ static int enqueue_chain(const Forward& f, BinningState& b, const Chain& ch, hip
   // 16-bit keys and at least two passes: the last pass counts the instances of every tile into the zeroed ranges
   // instead of writing the sorted keys, and a one-workgroup scan turns the counts into ranges; otherwise the range
   // kernel reads the sorted keys as the reference's identifyTileRanges does (GSR_RANGES_FROM_KEYS)
-  const bool count_ranges = key16 && sort_passes(tile_bits) >= 2 && !f.env.ranges_from_keys;
+  const bool count_ranges = key16 && sort_passes(tile_bits) >= 2 && !env().ranges_from_keys;
   const BucketPass bp = {ranges, tiles, ch.base};
   STAGE(launch_sort_pairs(b.tkeysA, point_list, b.tkeysB, b.ivalsB, b.tsort, cnt, tile_bits, start_in_A,
                           /*is_depth_sort=*/false, key16, /*first_hist_done=*/true, key16 ? &ef : nullptr,
@@ -901,7 +913,7 @@ static int enqueue_exact(const Forward& f, uint32_t R, bool sync_trace) {
   const std::chrono::steady_clock::time_point ta = std::chrono::steady_clock::now();
   BinningState b;
   const int rc = carve_binning(f, (int)R, &b);
-  if (sync_trace && f.env.host_trace)
+  if (sync_trace && env().host_trace)
     fprintf(stderr, "[gsr] synchronous forward: R=%u, waited %.1f us, binning alloc %.1f us\n", R,
             std::chrono::duration<double, std::micro>(ta - f.t_enq).count(),
             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - ta).count());
@@ -911,10 +923,7 @@ static int enqueue_exact(const Forward& f, uint32_t R, bool sync_trace) {
 
 // near/far frames (gsr_set_near_far): 1 = allowed (default), 0 = never
 static std::atomic<int>& near_far_flag() {
-  static std::atomic<int> flag([] {
-    const char* e = getenv("GSR_NEAR_FAR");
-    return (e && e[0] == '0') ? 0 : 1;
-  }());
+  static std::atomic<int> flag(env().near_far ? 1 : 0);
   return flag;
 }
 static std::atomic<unsigned long long> g_near_far_forwards{0};
@@ -929,7 +938,7 @@ struct FramePlan {
   bool speculate_far;           // a near/far frame that expects its far chain to stay idle
   bool partial_sort;            // only the near candidates are sorted by depth up front (enqueue_depth_order)
 };
-static FramePlan plan_frame(ThreadCtx& c, ViewHist& h, const FrameParams& fp, const ForwardEnv& env, int debug) {
+static FramePlan plan_frame(ThreadCtx& c, ViewHist& h, const FrameParams& fp, int debug) {
   FramePlan p;
   uint32_t hint = 0, pred = 0;  // capacity to allocate for / instance count predicted (the decisions below use the latter)
   if (c.hint_override >= 0) {
@@ -954,7 +963,7 @@ static FramePlan plan_frame(ThreadCtx& c, ViewHist& h, const FrameParams& fp, co
     }
   }
   p.hint = hint;
-  p.speculate = !debug && !env.sync_forward && hint > 0;
+  p.speculate = !debug && !env().sync_forward && hint > 0;
   // Near/far frame (speculative forwards in the default binning mode, when the predicted instance count is at least
   // three times the near budget): the tiles' lists are depth-ordered and a pixel stops reading its list once its
   // transmittance falls below 1e-4 (forward.cu:380-383) -- at 2 M Gaussians / 1080p every tile is finished after
@@ -967,7 +976,7 @@ static FramePlan plan_frame(ThreadCtx& c, ViewHist& h, const FrameParams& fp, co
   // are shorter.  gsr_set_reference_rects(1) frames are never split: their lists are the reference's, whole.
   const long long near_entries = c.near_entries_override >= 0
                                      ? c.near_entries_override
-                                     : (env.near_entries * (long long)h.near_scale_q8 + 255) / 256;  // (budget_feedback)
+                                     : (env().near_entries * (long long)h.near_scale_q8 + 255) / 256;  // (budget_feedback)
   p.budget64 = (unsigned long long)(fp.gx * fp.gy) * (unsigned long long)near_entries;
   bool split_paused = false;
   if (h.split_pause > 0 && c.near_entries_override < 0) {  // (budget_feedback: this view's splits kept missing)
@@ -980,7 +989,7 @@ static FramePlan plan_frame(ThreadCtx& c, ViewHist& h, const FrameParams& fp, co
   p.near_far = p.speculate && (t_near_far >= 0 ? t_near_far != 0 : near_far_flag().load() != 0) && !fp.ref_rects &&
                near_entries > 0 && p.budget64 < 0x20000000ull && !split_paused &&
                (c.near_entries_override >= 0 ||
-                4ull * (unsigned long long)pred >= env.near_far_min_ratio_q2 * p.budget64);  // (hook: always)
+                4ull * (unsigned long long)pred >= env().near_far_min_ratio_q2 * p.budget64);  // (hook: always)
   // Far-chain speculation (near_far_frame): after two split frames in a row that left no quad unfinished (or when the
   // test hook asks) the thread's next split frame expects its far chain to stay idle.
   p.speculate_far = p.near_far && (c.far_skip_override >= 0 ? c.far_skip_override == 1 : h.far_idle_streak >= 2);
@@ -989,7 +998,7 @@ static FramePlan plan_frame(ThreadCtx& c, ViewHist& h, const FrameParams& fp, co
   // (no partial depth sort while the candidates are more than a third of the scene -- the line is drawn at top-byte
   // granularity, a factor of four in depth: the last partial sort's count says so; every 64th frame tries again)
   if (h.near_list_too_long && (c.ticket & 63u) == 0u) h.near_list_too_long = false;
-  p.partial_sort = p.speculate_far && c.top_hist != nullptr && !env.full_depth_sort &&
+  p.partial_sort = p.speculate_far && c.top_hist != nullptr && !env().full_depth_sort &&
                    (!h.near_list_too_long || speculation_forced);
   return p;
 }
@@ -1041,7 +1050,7 @@ static int one_chain_frame(const Forward& f, uint32_t cap, FrameResult* r) {
     return rc;
   const std::chrono::steady_clock::time_point tw = std::chrono::steady_clock::now();
   if ((rc = wait_num_rendered(f.c, f.stream, &r->R)) != GSR_OK) return rc;
-  if (f.env.host_trace)
+  if (env().host_trace)
     fprintf(stderr, "[gsr] speculative forward: capacity %d, R=%u, enqueue %.1f us, then waited %.1f us\n", r->key,
             r->R, std::chrono::duration<double, std::micro>(tw - f.t_enq).count(),
             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tw).count());
@@ -1166,7 +1175,7 @@ static int near_far_frame(const Forward& f, const FramePlan& p, bool multi_threa
     }
     record_far_outcome(c, &f.h, live, r->near, r->far, r->R, /*speculated=*/p.speculate_far, /*latest=*/true);
   }
-  if (f.env.host_trace)
+  if (env().host_trace)
     fprintf(stderr, "[gsr] near/far forward: capacity %u + %u, near %u, far %u of %u instances, %u unfinished quads%s, "
                     "enqueue %.1f us, then waited %.1f us\n", capA, capB, r->near, r->far, r->R, live,
             async_far ? (know_far ? " (asynchronous far chain, checked by the host)" : " (asynchronous far chain)")
@@ -1258,8 +1267,7 @@ int gsr_forward(gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn bi
   //     waits for the host.  If R exceeds the capacity the kernels have clamped to it (in-bounds garbage); the
   //     host then allocates an exact blob and enqueues the binning chain again -- the only cost of a misprediction.
   ThreadCtx& c = g_ctx;
-  const ForwardEnv& env = forward_env();
-  const bool multi_thread = several_threads_render(&c) && !env.async_mt;
+  const bool multi_thread = several_threads_render(&c);
   lazy_resolve(c);  // (what the thread's earlier asynchronous frames left open, as far as the mailbox has it by now)
   c.w_live = 3;
   c.w_far = 1;
@@ -1277,7 +1285,7 @@ int gsr_forward(gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn bi
   // counter, used alternately -- a forward counts into one (zero on entry) and clears the other for the next
   // forward of this thread, so a call that ends early never leaves a dirty buffer in the way.
   // GSR_DEPTH_HIST_PASS=1 restores the sort's own histogram pass (k_sort_hist_all).
-  const bool own_hist_pass = env.depth_hist_pass || !preprocess_counts_depth_digits(fp, shs, colors_precomp);
+  const bool own_hist_pass = env().depth_hist_pass || !preprocess_counts_depth_digits(fp, shs, colors_precomp);
   uint32_t* const ghist2 = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(c.done_counter) + 64);
   if (!own_hist_pass) c.hist_flip ^= 1u;  // only a call that uses the pair advances it (the other buffer is clean)
   // (5 rows of 256: the four digit histograms + the tile counts summed by top byte, k_preprocess)
@@ -1289,8 +1297,8 @@ int gsr_forward(gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn bi
   c.top_hist = ghist_acc ? ghist_acc + 3 * 256 : nullptr;  // rows 3 (counts by top byte) and 4 (tile sums) are adjacent
   if (debug) STAGE(launch_point_offsets(fp, g, stream));  // the reference's array, for the views only
 
-  const FramePlan plan = plan_frame(c, h, fp, env, debug);
-  Forward f{fp, g, im, c, h, env, DepthOrder{}, background, out_color, out_depth, out_acc, debug, stream, iblob,
+  const FramePlan plan = plan_frame(c, h, fp, debug);
+  Forward f{fp, g, im, c, h, DepthOrder{}, background, out_color, out_depth, out_acc, debug, stream, iblob,
             binning_alloc, binning_ctx, std::chrono::steady_clock::now()};
   c.last_was_near_far = false;
   if ((rc = enqueue_depth_order(f, plan, ghist_acc)) != GSR_OK) return rc;
@@ -1303,7 +1311,7 @@ int gsr_forward(gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn bi
   if (r.redo && (rc = redo_frame(f, &r)) != GSR_OK) return rc;
   c.last_near = r.near;
   c.last_far = r.far;
-  if (env.host_trace)
+  if (env().host_trace)
     fprintf(stderr, "[gsr] forward returns at %.1f us (process clock)\n",
             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count());
   frame_note(iblob, NOTE_PRESENT);  // (every completed forward leaves a note: a backward that finds none was evicted)
@@ -1417,8 +1425,7 @@ int gsr_backward(int P, int D, int M, int R, const float* background, int width,
   if (!dL_dmean2D || !dL_dconic || !dL_dopacity || !dL_dcolor || !dL_dmean3D || (!dL_dcov3D && cov3D_precomp) ||
       !dL_dscale || !dL_drot || (M > 0 && !dL_dsh))
     return fail(GSR_ERR_INVALID_ARGUMENT, "null gradient output");
-  static const bool host_trace_b = getenv("GSR_HOST_TRACE") != nullptr;
-  if (host_trace_b)
+  if (env().host_trace)
     fprintf(stderr, "[gsr] backward entered at %.1f us (process clock)\n",
             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count());
   const FrameParams fp = make_params(P, D, M, width, height, tan_fovx, tan_fovy, scale_modifier);

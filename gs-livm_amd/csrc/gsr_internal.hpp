@@ -293,6 +293,30 @@ struct FrameParams {
   int ref_rects;  // 1 = emit the reference's full 3-sigma tile square (gsr_set_reference_rects), 0 = footprint-culled
 };
 
+// The library's environment switches (INTEGRATION.md has the table with their tests), read once per process by env()
+// (api.hip: the only place that asks the environment).  A bool is "the variable is set" unless its line says otherwise.
+struct Env {
+  bool reference_rects;       // GSR_REFERENCE_RECTS set and not "0": initial value of gsr_set_reference_rects
+  bool near_far;              // GSR_NEAR_FAR not "0": initial value of gsr_set_near_far
+  bool async_far;             // GSR_ASYNC_FAR not "0": asynchronous far chains allowed (else always host-decided)
+  bool sync_forward;          // GSR_SYNC_FORWARD: every forward synchronous
+  long near_entries;          // GSR_NEAR_ENTRIES: near budget in list entries per tile (320)
+  unsigned long long near_far_min_ratio_q2;  // GSR_NEAR_FAR_MIN_RATIO_Q2: quarters of a near budget that make a split worth it (12)
+  bool full_depth_sort;       // GSR_FULL_DEPTH_SORT: diagnostics / fallback, no partial depth sort
+  bool depth_hist_pass;       // GSR_DEPTH_HIST_PASS: the depth sort counts its digits in a pass of its own
+  long pre_hist_min_p;        // GSR_PRE_HIST_MIN_P: k_preprocess counts the depth digits above this many Gaussians (-1: not given)
+  bool ranges_from_keys;      // GSR_RANGES_FROM_KEYS: diagnostics / fallback, tile ranges from the sorted keys
+  bool tile_sort_lsd;         // GSR_TILE_SORT_LSD: diagnostics / fallback, always the two LSD passes
+  bool sort_two_level_scan;   // GSR_SORT_TWO_LEVEL_SCAN: diagnostics / fallback, the digit counts scanned in two launches
+  bool sort_ballot_rank;      // GSR_SORT_BALLOT_RANK: the scatter ranks by ballot matching, no probe of the LDS atomics
+  bool blend_backward_quads;  // GSR_BLEND_BACKWARD_QUADS: k_blend_backward whatever the frame size
+  bool blend_backward_tiles;  // GSR_BLEND_BACKWARD_TILES: k_blend_backward_tile whatever the frame size
+  bool bwd_image_order;       // GSR_BWD_IMAGE_ORDER: the backward takes the tiles in image order (no k_tile_order)
+  bool gbwd_all;              // GSR_GBWD_ALL: diagnostics, k_gaussian_backward computes Gaussians without records too
+  bool host_trace;            // GSR_HOST_TRACE: diagnostics, host-side waits and timestamps to stderr
+};
+const Env& env();
+
 // ---- stage launchers (each enqueues on `s`; returns hipGetLastError()) ----
 bool preprocess_counts_depth_digits(const FrameParams& fp, const float* shs, const float* colors_precomp);
 hipError_t launch_preprocess(const FrameParams& fp, const float* means3D, const float* scales, const float* rotations,

@@ -20,7 +20,6 @@
 // evaluation order of the reference (GLM column-major products, accumulated left to right) so the
 // rounding matches the unfused CPU oracle bit for bit.  Divisions and sqrt are IEEE (hipcc default
 // -fhip-fp32-correctly-rounded-divide-sqrt).
-#include <cstdlib>
 
 #include "gsr_internal.hpp"
 #include "sort_core.hpp"
@@ -1356,9 +1355,6 @@ __device__ __forceinline__ void swap_add16_(float& a, float& b) {
 }
 
 // (the register allocator settles on 102 VGPRs = four waves per SIMD for k_gather_records; asked for 96 it finds 86 without a spill)
-#ifndef GSR_GATHER_ATTR
-#define GSR_GATHER_ATTR __attribute__((amdgpu_num_vgpr(96)))
-#endif
 // the nine sums of one Gaussian's records, per lane (lane = slot mod 64)
 struct RecordSums {
   float v0 = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0, v5 = 0, v6 = 0, v7 = 0, v8 = 0;
@@ -1431,7 +1427,7 @@ __device__ __forceinline__ void gather_finish(RecordSums r, const uint32_t id, c
   if (lane == 63) dL_dopacity[id] = v8;
 }
 
-__global__ __launch_bounds__(PRE_BLOCK) GSR_GATHER_ATTR void k_gather_records(
+__global__ __launch_bounds__(PRE_BLOCK) __attribute__((amdgpu_num_vgpr(96))) void k_gather_records(
     GeomState g, const float4* __restrict__ grad_inst, uint8_t* __restrict__ inst_flag,
     float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic, float* __restrict__ dL_dopacity,
     float* __restrict__ dL_dcolor, const float ddelx_dx, const float ddely_dy, const int P, const bool from_descriptors) {
@@ -1840,12 +1836,11 @@ bool preprocess_counts_depth_digits(const FrameParams& fp, const float* shs, con
   // on small scenes)
   // From 128 k Gaussians (with one workgroup per CU up to 1 M, so that a workgroup walks several blocks between its ~770
   // flush atomics: 640x512 / 300 k: k_preprocess +2.5 us, k_sort_hist_all's 8.6 us launch gone; 500 k: +4.8 / -9.6).
-  static const long min_p = getenv("GSR_PRE_HIST_MIN_P") ? atol(getenv("GSR_PRE_HIST_MIN_P")) : (1 << 17);
+  const long given = env().pre_hist_min_p;  // (-1: not given)
   // (with SH rows staged through LDS the kernel keeps three workgroups per CU -- it has no prefetch to cover a lone
   // workgroup's loads --, so the digits are counted there only where a workgroup still walks several blocks: > 1 M)
-  static const bool min_p_given = getenv("GSR_PRE_HIST_MIN_P") != nullptr;
   const bool staged = shs && !colors_precomp && sh_stage_bytes(fp.M) != 0;
-  return fp.P > (staged && !min_p_given ? (1L << 20) : min_p);
+  return fp.P > (given >= 0 ? given : staged ? (1L << 20) : (1L << 17));
 }
 
 hipError_t launch_preprocess(const FrameParams& fp, const float* means3D, const float* scales, const float* rotations,
@@ -1863,21 +1858,20 @@ hipError_t launch_preprocess(const FrameParams& fp, const float* means3D, const 
   // 64, 67, 70 us; with the arithmetic compiled out it still takes 56 us for its 252 MB: it is bound by the memory
   // path, not by latency or VALU), and every workgroup ends with ~770 histogram flush atomics and one same-address count
   // atomic, so fewer and longer-lived workgroups win
-  static const int wg_per_cu = getenv("GSR_PRE_WG_PER_CU") ? atoi(getenv("GSR_PRE_WG_PER_CU")) : 3;  // experiment knob
   // (up to 1 M Gaussians a single workgroup per CU when the digits are counted here: see preprocess_counts_depth_digits)
-  static const bool wg_forced = getenv("GSR_PRE_WG_PER_CU") != nullptr;
-  const bool few_wg = ghist_acc != nullptr && fp.P <= (1 << 20) && !wg_forced;
-  const int max_wg = (stage ? 3 : few_wg ? 1 : wg_per_cu) * 256, rounds = (nb + max_wg - 1) / max_wg;
+  const bool few_wg = ghist_acc != nullptr && fp.P <= (1 << 20);
+  const int max_wg = (few_wg && !stage ? 1 : 3) * 256, rounds = (nb + max_wg - 1) / max_wg;
   const dim3 grid(rounds ? (nb + rounds - 1) / rounds : 1);
   // (the staged variants: SH degree 1 and 3 with plain inputs pipeline their rows per wave, see the kernel's header)
   const bool plain_in = shs && scales && rotations && !cov3D_precomp && !colors_precomp && !write_cov3D;
   const bool rows16 = plain_in && (reinterpret_cast<uintptr_t>(shs) & 15u) == 0;
-  static const bool env_block_rows = getenv("GSR_PRE_BLOCK_ROWS") != nullptr;  // diagnostics: the block-wide copy
-  if (stage && rows16 && fp.M == 16 && !env_block_rows)
+  // (the block-wide copy, k_preprocess<true>, takes what is left: rows that are not 16-byte aligned, M = 9, the inputs
+  // that are not plain)
+  if (stage && rows16 && fp.M == 16)
     hipLaunchKernelGGL((k_preprocess<true, false, true, 12>), grid, dim3(PRE_BLOCK), stage, s, fp, means3D, scales, rotations,
                        opacities, shs, cov3D_precomp, colors_precomp, view, proj, campos, g, radii_out, write_cov3D,
                        done_word, publish, ticket, ghist_acc, ghist_clear);
-  else if (stage && rows16 && fp.M == 4 && !env_block_rows)
+  else if (stage && rows16 && fp.M == 4)
     hipLaunchKernelGGL((k_preprocess<true, false, true, 3>), grid, dim3(PRE_BLOCK), stage, s, fp, means3D, scales, rotations,
                        opacities, shs, cov3D_precomp, colors_precomp, view, proj, campos, g, radii_out, write_cov3D,
                        done_word, publish, ticket, ghist_acc, ghist_clear);
@@ -1997,7 +1991,7 @@ hipError_t launch_gaussian_backward(const FrameParams& fp, GeomState g, BinningS
   const int nb = (fp.P + PRE_BLOCK - 1) / PRE_BLOCK;
   ProfScope ps_k_gaussian_bwd(K_GAUSSIAN_BWD, s);
   const size_t stage = (shs && !colors_precomp) ? sh_stage_bytes(fp.M) : 0;  // M > 1: SH / dL_dsh rows go through LDS
-  static const bool skip_recordless = getenv("GSR_GBWD_ALL") == nullptr;  // (GSR_GBWD_ALL=1: diagnostics)
+  const bool skip_recordless = !env().gbwd_all;  // (GSR_GBWD_ALL=1: diagnostics)
   if (stage)
     hipLaunchKernelGGL(k_gaussian_backward<true>, dim3(nb), dim3(PRE_BLOCK), stage, s, fp, g, radii,
                        means3D, scales, rotations, shs, cov3D_precomp, view, proj, campos, 0,

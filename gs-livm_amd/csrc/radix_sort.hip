@@ -25,7 +25,6 @@
 //   right after the key load.  For the 10^7-pair sort the look-back measured slower than the helper kernels
 //   (DESIGN.md "Tried and rejected"), for the 10^6-pair sort it replaces 16 launches by 5.
 // Every step is order-preserving (stable); no float atomics.
-#include <cstdlib>
 #include <mutex>
 
 #include "gsr_internal.hpp"
@@ -214,7 +213,7 @@ static bool lds_atomic_rank_ok(hipStream_t s) {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
   if (state[dev] >= 0) return state[dev] == 1;
   state[dev] = 0;
-  if (getenv("GSR_SORT_BALLOT_RANK")) return false;
+  if (env().sort_ballot_rank) return false;
   uint32_t* d = nullptr;
   uint32_t h = 0;
   if (hipMalloc(reinterpret_cast<void**>(&d), sizeof(uint32_t)) != hipSuccess) return false;
@@ -400,8 +399,7 @@ __global__ __launch_bounds__(BUCKET_THREADS) void k_bucket_sort(const uint16_t* 
 }
 
 bool tile_sort_buckets(int tile_bits, bool key16, int capacity) {
-  static const bool lsd = getenv("GSR_TILE_SORT_LSD") != nullptr;  // diagnostics / fallback: always the two LSD passes
-  return key16 && !lsd && tile_bits > 8 && sort_passes(tile_bits) == 2 && capacity <= TILE_SORT_BUCKETS_MAX;
+  return key16 && !env().tile_sort_lsd && tile_bits > 8 && sort_passes(tile_bits) == 2 && capacity <= TILE_SORT_BUCKETS_MAX;
 }
 
 // The pairs start in (keysA, valsA) when start_in_A, else in (keysB, valsB); passes alternate.  The caller
@@ -421,7 +419,7 @@ static hipError_t sort_pairs_impl(K* keysA, uint32_t* valsA, K* keysB, uint32_t*
   const int passes = sort_passes(end_bit);
   const int nbits = sort_digit_bits(end_bit);
   const bool arank = lds_atomic_rank_ok(s);
-  static const bool two_level_scan = getenv("GSR_SORT_TWO_LEVEL_SCAN") != nullptr;  // diagnostics / fallback
+  const bool two_level_scan = env().sort_two_level_scan;
   bool inA = start_in_A;
   if (buckets && sizeof(K) == 2 && ef && first_hist_done) {
     // bucket form: first pass = the fused emit-scatter on the TOP eight bits (its counts came from the emitter), second

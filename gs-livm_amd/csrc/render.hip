@@ -6,8 +6,8 @@
 // Shapes (NOT the reference's 16x16-thread / 32-lane-warp structure; details at each kernel):
 //   * forward, k_blend_forward: ONE WAVE PER 8x8 PIXEL QUAD, no workgroup barrier in the blending; a wave streams its
 //     tile's depth-sorted list 64 entries at a time -- one 48-B splat record per lane, exact ellipse-vs-quad test, one
-//     ballot, records published to a wave-private LDS image -- and walks only the set bits (scalar bit scan, LDS
-//     broadcast), so a splat that cannot touch the quad costs it nothing.  Skipping is exact: a skipped pair has
+//     ballot, the hits' records published compacted to a wave-private LDS image -- and walks only the hits (a counted
+//     loop, LDS broadcast), so a splat that cannot touch the quad costs it nothing.  Skipping is exact: a skipped pair has
 //     alpha < 1/255 for every pixel, which the reference discards as well.  A wave stops when its 64 pixels have.
 //     Near/far frames (api.hip) run it as phase 1 (near segment; unfinished quads park their state; the launch's last
 //     workgroup counts them and, in an asynchronous frame, opens the far chain or releases the caller's stream) and
@@ -21,8 +21,6 @@
 //   (pixel, splat) instead (backward.cu:565, 591-600) and is run-to-run non-deterministic; this path is bitwise
 //   reproducible.
 // Also here: k_live_sat (which tiles the near chain left unfinished), k_release_go (end of an asynchronous far chain).
-#include <cstdlib>
-
 #include "gsr_internal.hpp"
 
 namespace gsr {
@@ -189,31 +187,8 @@ __device__ __forceinline__ uint32_t quad_hits(float x, float y, float hx, float 
 // those of a single launch over the concatenated list.
 constexpr uint32_t STOPPED_BIT = 0x80000000u;
 
-// Lane select by an explicit 64-bit lane mask held in scalar registers: bit set -> a, else b (one v_cndmask_b32).  The
-// forward blend keeps its per-pixel predicates (done, take, stop, ok) as such masks and combines them with a handful of
-// scalar ALU instructions; as loop-carried `bool`s the compiler turned every wave-wide test of them into a
-// v_cndmask 0/1 + v_cmp + s_cmp round trip and every `!x` of a float compare into a second compare.
-__device__ __forceinline__ float sel_f(uint64_t m, float a, float b) {
-  float d;
-  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(d) : "v"(b), "v"(a), "s"(m));
-  return d;
-}
-__device__ __forceinline__ float sel_f0(uint64_t m, float a) {  // bit set -> a, else 0
-  float d;
-  asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(d) : "v"(a), "s"(m));
-  return d;
-}
-__device__ __forceinline__ uint32_t sel_u(uint64_t m, uint32_t a, uint32_t b) {
-  uint32_t d;
-  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(d) : "v"(b), "v"(a), "s"(m));
-  return d;
-}
-
-#ifndef GSR_FWD_ASM_VISIT
-#define GSR_FWD_ASM_VISIT 1
-#endif
 // slots of a wave's LDS image: 64 hits, +1 null entry padding an odd count, +1 read ahead by the walk
-constexpr int FWD_SLOTS = GSR_FWD_ASM_VISIT ? 66 : 64;
+constexpr int FWD_SLOTS = 66;
 
 template <int FW, int PHASE>  // FW quads (= waves) per workgroup: the waves never synchronise, FW only sets how many share a slot
 __global__ __launch_bounds__(64 * FW) void k_blend_forward(const FrameParams fp, const uint2* __restrict__ ranges,
@@ -240,19 +215,9 @@ __global__ __launch_bounds__(64 * FW) void k_blend_forward(const FrameParams fp,
     if (threadIdx.x == 0) s_done = 0u;
     __syncthreads();  // the only barrier: at the start, where no wave waits for a slower one
   }
-  // (wave-uniform by construction; made scalars by hand, see k_blend_backward_tile)
-#ifndef GSR_FWD_EXEC_MASK
-#define GSR_FWD_EXEC_MASK 1
-#endif
-#ifndef GSR_FWD_SCALAR
-#define GSR_FWD_SCALAR 0  // (scalarising the range / wave index by hand measured +3 %: more SALU on the walk's critical path)
-#endif
-#if GSR_FWD_SCALAR
-#define GSR_FWD_UNIFORM(x) __builtin_amdgcn_readfirstlane(x)
-#else
-#define GSR_FWD_UNIFORM(x) (x)
-#endif
-  const int lane = threadIdx.x & 63, wq = GSR_FWD_UNIFORM(threadIdx.x >> 6);
+  // (the wave index and the tile's range are wave-uniform by construction and left to the compiler: scalarising them by
+  // hand, as k_blend_backward_tile does, measured +3 % here -- more scalar instructions on the walk's critical path)
+  const int lane = threadIdx.x & 63, wq = threadIdx.x >> 6;
   float4* sA = sAll[wq][0];
   float4* sB = sAll[wq][1];
   float4* sC = sAll[wq][2];
@@ -268,13 +233,12 @@ __global__ __launch_bounds__(64 * FW) void k_blend_forward(const FrameParams fp,
   const float pfx = (float)px, pfy = (float)py;
   const float qx0 = (float)qx, qy0 = (float)qy;
   if (PHASE == 2 && quad_done[quad]) return;  // finished by the near phase
-  const uint2 range_v = PHASE == 2 ? rangesB[tile] : ranges[tile];
-  const uint2 range = make_uint2(GSR_FWD_UNIFORM(range_v.x), GSR_FWD_UNIFORM(range_v.y));
+  const uint2 range = PHASE == 2 ? rangesB[tile] : ranges[tile];
   const int n = (int)(range.y - range.x);
   uint32_t pos0 = 0;  // list position of this segment's first entry
   if (PHASE == 2) {
     const uint2 rn = ranges[tile];
-    pos0 = GSR_FWD_UNIFORM(rn.y - rn.x);
+    pos0 = rn.y - rn.x;
   }
   const size_t pid = (size_t)fp.W * py + px;
   const size_t N = (size_t)fp.W * fp.H;
@@ -291,7 +255,8 @@ __global__ __launch_bounds__(64 * FW) void k_blend_forward(const FrameParams fp,
     Dp = out_depth[pid];
     A = out_acc[pid];
   }
-  // (from here on the pixels' "done" flags live in one scalar lane mask)
+  // (from here on the pixels' "done" flags live in one scalar lane mask: as a loop-carried `bool` the compiler turned
+  // every wave-wide test of it into a v_cndmask 0/1 + v_cmp + s_cmp round trip)
   uint64_t done_m = __builtin_amdgcn_ballot_w64(done);
   bool wave_done = done_m == ~0ull;
 
@@ -333,14 +298,24 @@ __global__ __launch_bounds__(64 * FW) void k_blend_forward(const FrameParams fp,
       c = splats[(size_t)id * SPLAT_F4 + 2];
       hit = splat_hits_quad(a, b, c, qx0, qy0);
     }
-#if GSR_FWD_ASM_VISIT
-    // One visit = one block of assembly: 23 vector and 4 scalar instructions.  The skip / stop rules of forward.cu:367-383
-    // narrow the execution mask step by step -- not-yet-stopped pixels (s_andn1_saveexec), power <= 0 and alpha >= 1/255
-    // (two v_cmpx), then T (1 - alpha) >= 1e-4 (the pixels that fail it are added to the `done` mask and leave) -- and the
-    // pixels still active take the splat.  As C++ the same rules cost 13 scalar instructions per visit (lane masks
-    // combined with s_and / s_or / s_andn2, loop flags through s_cselect and vcc branches): 43 M per frame at 2 M Gaussians /
-    // 1080p on the ONE scalar unit the CU's waves share, which was as busy as the vector units (profiles/r03e_sq_probe.txt).
-    // Same arithmetic, same order of roundings as the C++ visit (`blend`, below): images and n_contrib are bit-identical.
+    // One visit of one splat by the quad's 64 pixels = one block of assembly, 23 vector and 4 scalar instructions.  This
+    // block is the only statement of the forward's per-pixel arithmetic and of the reference's skip / stop rules
+    // (forward.cu:367-383):
+    //   power = A' dx^2 + dy (C' dy + B' dx), the roundings of splat_power: the backward takes bit-identical decisions
+    //   alpha = min(0.99, opacity * exp2(power))
+    //   a pixel that has stopped, power > 0, or alpha < 1/255: the pixel skips the splat
+    //   test_T = T (1 - alpha) < 1e-4: the pixel stops BEFORE this splat (it joins the `done` mask) and skips it
+    //   otherwise, with weight = alpha T: C += colour * weight, Dp += depth * weight, A += weight, T = test_T,
+    //   last = the splat's list position
+    // The rules narrow the execution mask step by step -- not-yet-stopped pixels (s_andn1_saveexec), !(power > 0) and
+    // !(alpha < 1/255) (two v_cmpx), then test_T -- and the pixels still active take the splat with eight plain
+    // instructions; the wave's execution mask is restored before anything else runs.  Why assembly: the compiler cannot
+    // use a scalar lane mask as a branch condition without deriving a per-lane flag from it first.  Written as C++ on
+    // lane masks the rules cost 13 scalar instructions per visit instead of 4 (s_and / s_or / s_andn2, loop flags through
+    // s_cselect and vcc branches): 43 M per frame at 2 M Gaussians / 1080p on the ONE scalar unit the CU's waves share,
+    // which was as busy as the vector units (profiles/r03e_sq_probe.txt).  Updating by selects instead of under the mask (weight or 0, new or old T,
+    // new or old position) takes nine instructions, three of them v_cndmask_b32 at 1.6 times the issue cost of a
+    // multiply-add (tools/microbench/valu_probe.hip).
     auto visit = [&](const float4 ra, const float4 rb, const float4 rc) {
       float t0, t1, dx, dy;
       uint64_t sv;
@@ -408,74 +383,6 @@ __global__ __launch_bounds__(64 * FW) void k_blend_forward(const FrameParams fp,
         }
       }
     }
-#else
-    // Visit loop, software-pipelined by hand: the LDS broadcast reads of the NEXT hit are issued before the
-    // current hit is blended (two register sets, no copies), so their latency hides behind ~30 VALU ops.
-    auto blend = [&](const float4 ra, const float4 rb, const float4 rc) {
-      const float dx = ra.x - pfx, dy = ra.y - pfy;
-      const float power = splat_power(ra.z, ra.w, rb.x, dx, dy);  // = log2(e) x the reference's power
-      const float alpha = fminf(0.99f, rb.y * __builtin_amdgcn_exp2f(power));
-      // forward.cu:367-383: skip on power > 0 and alpha < 1/255; a pixel whose T would fall below 1e-4 stops BEFORE taking
-      // the splat.  Three compares straight into lane masks, the rest is scalar mask arithmetic.
-      const uint64_t take = __builtin_amdgcn_ballot_w64(!(power > 0.0f)) &
-                            __builtin_amdgcn_ballot_w64(!(alpha < 1.0f / 255.0f)) & ~done_m;
-      const float test_T = T * (1.0f - alpha);
-      const uint64_t low = __builtin_amdgcn_ballot_w64(test_T < 0.0001f);
-      done_m |= take & low;
-      const uint64_t ok = take & ~low;
-#if GSR_FWD_EXEC_MASK
-      // The pixels that take the splat update their sums, T and last contributor under the execution mask `ok`: eight
-      // plain instructions.  (With selects -- weight or 0, new or old T, new or old position -- it is nine, three of
-      // them v_cndmask_b32 at 1.6 times the issue cost of a multiply-add: tools/microbench/valu_probe.hip.)  The compiler cannot
-      // be told to use a scalar lane mask as a branch condition without deriving a per-lane flag from it first, hence
-      // the assembly; the wave's execution mask is restored before anything else runs.
-      uint64_t exec_save;
-      float wgt;
-      asm volatile(
-          "s_and_saveexec_b64 %[sv], %[ok]\n\t"
-          "v_mul_f32_e32 %[w], %[al], %[T]\n\t"
-          "v_fmac_f32_e32 %[C0], %[cr], %[w]\n\t"
-          "v_fmac_f32_e32 %[C1], %[cg], %[w]\n\t"
-          "v_fmac_f32_e32 %[C2], %[cb], %[w]\n\t"
-          "v_fmac_f32_e32 %[Dp], %[dz], %[w]\n\t"
-          "v_add_f32_e32 %[A], %[A], %[w]\n\t"
-          "v_mov_b32_e32 %[T], %[tT]\n\t"
-          "v_mov_b32_e32 %[last], %[pos]\n\t"
-          "s_mov_b64 exec, %[sv]"
-          : [sv] "=&s"(exec_save), [w] "=&v"(wgt), [C0] "+v"(C0), [C1] "+v"(C1), [C2] "+v"(C2), [Dp] "+v"(Dp), [A] "+v"(A),
-            [T] "+v"(T), [last] "+v"(last)
-          : [ok] "s"(ok), [al] "v"(alpha), [cr] "v"(rb.z), [cg] "v"(rb.w), [cb] "v"(rc.x), [dz] "v"(rc.y), [tT] "v"(test_T),
-            [pos] "v"(rc.z)
-          : "scc");
-#else
-      const float wgt = sel_f0(ok, alpha * T);
-      C0 += rb.z * wgt;
-      C1 += rb.w * wgt;
-      C2 += rc.x * wgt;
-      Dp += rc.y * wgt;
-      A += wgt;
-      T = sel_f(ok, test_T, T);
-      last = sel_u(ok, __float_as_uint(rc.z), last);
-#endif
-    };
-    if (nh) {
-      float4 a0 = sA[0], b0 = sB[0], c0 = sC[0], a1, b1, c1;
-      for (int r = 0;; r += 2) {
-        const bool has1 = r + 1 < nh;
-        if (has1) { a1 = sA[r + 1]; b1 = sB[r + 1]; c1 = sC[r + 1]; }
-        blend(a0, b0, c0);
-        if (!has1) {
-          wave_done = done_m == ~0ull;
-          break;
-        }
-        const bool has2 = r + 2 < nh;
-        if (has2) { a0 = sA[r + 2]; b0 = sB[r + 2]; c0 = sC[r + 2]; }
-        blend(a1, b1, c1);
-        wave_done = done_m == ~0ull;  // checked once per pair of visits: a visit after saturation changes nothing
-        if (wave_done || !has2) break;
-      }
-    }
-#endif
   }
 
   done = ((done_m >> lane) & 1ull) != 0ull;  // (back to a per-lane flag for the epilogue)
@@ -795,18 +702,8 @@ __global__ __launch_bounds__(1024) void k_tile_order(const uint32_t* __restrict_
   for (int t = tid + 8192; t < T; t += 1024) order[atomicAdd(&bins[walk(t)], 1u)] = (uint32_t)t;
 }
 
-// experiment knobs (A/B builds: GSR_EXTRA_RENDER_FLAGS=-DGSR_BWD_...=..)
-#ifndef GSR_BWD_STRIP_BRANCH
-#define GSR_BWD_STRIP_BRANCH 1
-#endif
-#ifndef GSR_BWD_MIN_WAVES
-#define GSR_BWD_MIN_WAVES 1
-#endif
-#ifndef GSR_BWD_EXEC_MASK
-#define GSR_BWD_EXEC_MASK 1
-#endif
 template <int TW>  // tiles (= waves) per workgroup; the waves never synchronise
-__global__ __launch_bounds__(64 * TW, GSR_BWD_MIN_WAVES) void k_blend_backward_tile(
+__global__ __launch_bounds__(64 * TW, 1) void k_blend_backward_tile(
     const FrameParams fp, const uint2* __restrict__ ranges, const uint32_t* __restrict__ quad_last_in,
     const uint32_t* __restrict__ point_list, const float4* __restrict__ splats, const uint2* __restrict__ slotinfo,
     const float* __restrict__ bg, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
@@ -902,11 +799,7 @@ __global__ __launch_bounds__(64 * TW, GSR_BWD_MIN_WAVES) void k_blend_backward_t
       // lane-local sums over the lane's four pixels: colour (3), dLG, dLG dy, dLG dy^2 (accumulated as fused
       // multiply-adds: combining the four pixels costs no instruction of its own)
       float c0 = 0.f, c1 = 0.f, c2 = 0.f, sG = 0.f, sGy = 0.f, sGyy = 0.f;
-#if GSR_BWD_EXEC_MASK
       uint64_t anym = 0ull;  // lanes one of whose four pixels takes the splat
-#else
-      uint32_t abits = 0u;  // OR of the lane's four alphas: non-zero iff one of its pixels takes the splat
-#endif
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         const float dy = ea.y - pfy[k];
@@ -914,50 +807,20 @@ __global__ __launch_bounds__(64 * TW, GSR_BWD_MIN_WAVES) void k_blend_backward_t
         const float Graw = __builtin_amdgcn_exp2f(power);
         const float araw = fminf(0.99f, eb.y * Graw);
         const bool ok = (pos < lastc[k]) && !(power > 0.0f) && !(araw < 1.0f / 255.0f);
-#if GSR_BWD_EXEC_MASK
         // The pixels that take this splat run the update under the execution mask; the others keep their recurrence
         // state and add nothing -- no select instructions (a v_cndmask / v_cmp / v_min costs 1.6 plain multiply-adds on
         // this chip, tools/microbench/valu_probe.hip), and a strip no pixel of which takes the splat costs the test only.
         // (a ballot of the conjunction would be materialised as a select and a compare: and the three masks instead)
         anym |= __builtin_amdgcn_ballot_w64(pos < lastc[k]) & __builtin_amdgcn_ballot_w64(!(power > 0.0f)) &
                 __builtin_amdgcn_ballot_w64(!(araw < 1.0f / 255.0f));
-        {
-          if (ok) {
-            const float rom = __builtin_amdgcn_rcpf(1.0f - araw);
-            const float Tn = T[k] * rom;  // T / (1 - alpha)
-            const float D =
-                __builtin_fmaf(eb.z, dp0[k], __builtin_fmaf(eb.w, dp1[k], __builtin_fmaf(blue, dp2[k], dacc[k]))) - S[k];
-            const float dch = araw * Tn;
-            const float dL_dalpha = Tn * D;
-            const float dLG = Graw * dL_dalpha;  // dL/dG up to the opacity factor; also the opacity partial itself
-            const float sy = dLG * dy;
-            c0 = __builtin_fmaf(dch, dp0[k], c0);
-            c1 = __builtin_fmaf(dch, dp1[k], c1);
-            c2 = __builtin_fmaf(dch, dp2[k], c2);
-            sG += dLG;
-            sGy += sy;
-            sGyy = __builtin_fmaf(sy, dy, sGyy);
-            // Fold this splat into the "everything behind the next one" accumulators (the reference does it at the top
-            // of its next iteration from saved (last_alpha, last_color), backward.cu:533-543): accum + alpha (c - accum)
-            T[k] = Tn;
-            S[k] = __builtin_fmaf(araw, D, S[k]);
-          }
-        }
-      }
-#else
-        // Branch-free per lane: a pixel that does not take this splat runs with alpha = 0 and G = 0 -- exact zero
-        // partials, recurrence state untouched bit for bit (see k_blend_backward)
-        const float alpha = ok ? araw : 0.0f;
-        const float oma = 1.0f - alpha;
-        const float rom = __builtin_amdgcn_rcpf(oma);
-        const float Tn = T[k] * rom;  // T / (1 - alpha)
-        const float D =
-            __builtin_fmaf(eb.z, dp0[k], __builtin_fmaf(eb.w, dp1[k], __builtin_fmaf(blue, dp2[k], dacc[k]))) - S[k];
-        if (!GSR_BWD_STRIP_BRANCH || __ballot(ok) != 0ull) {  // some pixel of this 16 x 4 strip takes the splat
-          const float G = ok ? Graw : 0.0f;
-          const float dch = alpha * Tn;
+        if (ok) {
+          const float rom = __builtin_amdgcn_rcpf(1.0f - araw);
+          const float Tn = T[k] * rom;  // T / (1 - alpha)
+          const float D =
+              __builtin_fmaf(eb.z, dp0[k], __builtin_fmaf(eb.w, dp1[k], __builtin_fmaf(blue, dp2[k], dacc[k]))) - S[k];
+          const float dch = araw * Tn;
           const float dL_dalpha = Tn * D;
-          const float dLG = G * dL_dalpha;  // dL/dG up to the opacity factor; also the opacity partial itself
+          const float dLG = Graw * dL_dalpha;  // dL/dG up to the opacity factor; also the opacity partial itself
           const float sy = dLG * dy;
           c0 = __builtin_fmaf(dch, dp0[k], c0);
           c1 = __builtin_fmaf(dch, dp1[k], c1);
@@ -965,15 +828,12 @@ __global__ __launch_bounds__(64 * TW, GSR_BWD_MIN_WAVES) void k_blend_backward_t
           sG += dLG;
           sGy += sy;
           sGyy = __builtin_fmaf(sy, dy, sGyy);
+          // Fold this splat into the "everything behind the next one" accumulators (the reference does it at the top
+          // of its next iteration from saved (last_alpha, last_color), backward.cu:533-543): accum + alpha (c - accum)
+          T[k] = Tn;
+          S[k] = __builtin_fmaf(araw, D, S[k]);
         }
-        abits |= __float_as_uint(alpha);
-        // Fold this splat into the "everything behind the next one" accumulators (the reference does it at the top of
-        // its next iteration from saved (last_alpha, last_color), backward.cu:533-543): accum + alpha (c - accum)
-        T[k] = Tn;
-        S[k] = __builtin_fmaf(alpha, D, S[k]);
       }
-      const uint64_t anym = __ballot(abits != 0u);
-#endif
       if (anym != 0ull) {
         // the lane's pixels share dx: sum dLG dx = dx sum dLG, sum dLG dx^2 = dx^2 sum dLG, sum dLG dx dy = dx sum dLG dy
         float v0 = c0, v1 = c1, v2 = c2, v3 = dx * sG, v4 = sGy, v5 = dx2 * sG, v6 = dx * sGy, v7 = sGyy, g8 = sG;
@@ -1130,12 +990,8 @@ hipError_t launch_blend_forward(const FrameParams& fp, GeomState g, BinningState
 
 // Tile order of the backward (k_tile_order) as a launch of its own: a forward that has nothing else left to enqueue
 // computes it at its end (api.hip), where it fills the gap until the host has enqueued the next kernels.
-static bool backward_image_order() {
-  static const bool image_order = getenv("GSR_BWD_IMAGE_ORDER") != nullptr;  // experiment knob
-  return image_order;
-}
 hipError_t launch_tile_order(const FrameParams& fp, ImageState im, hipStream_t s) {
-  if (backward_image_order()) return hipSuccess;
+  if (env().bwd_image_order) return hipSuccess;
   ProfScope ps(K_TILE_ORDER, s);
   hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, im.quad_last, fp.gx * fp.gy, im.tile_order);
   return hipGetLastError();
@@ -1153,11 +1009,9 @@ hipError_t launch_blend_backward(const FrameParams& fp, GeomState g, BinningStat
   // (1080p: 0.21 vs 0.28 ms; 1280x720: 0.141 vs 0.162); on the small frames of the product (640x512 = 1280 tiles) four
   // waves per tile keep four times as many waves in flight (0.121 vs 0.327 ms).  Both take the tiles longest walk
   // first.  GSR_BLEND_BACKWARD_QUADS=1 / GSR_BLEND_BACKWARD_TILES=1 force one of them (diagnostics, tests).
-  static const bool force_quad = getenv("GSR_BLEND_BACKWARD_QUADS") != nullptr;
-  static const bool force_tile = getenv("GSR_BLEND_BACKWARD_TILES") != nullptr;
   const int tiles = fp.gx * fp.gy;
-  const bool per_quad = force_quad || (!force_tile && tiles < 3072);
-  const uint32_t* order = backward_image_order() ? nullptr : im.tile_order;
+  const bool per_quad = env().blend_backward_quads || (!env().blend_backward_tiles && tiles < 3072);
+  const uint32_t* order = env().bwd_image_order ? nullptr : im.tile_order;
   if (per_quad) {
     // chunks of 128 list entries (64 and 128 measured equal, 256 slower: LDS footprint)
     hipLaunchKernelGGL(k_blend_backward<128>, dim3(tiles), dim3(256), 0, s, fp, im.ranges, im.quad_last, b.point_list,

@@ -316,8 +316,9 @@ def test_near_far_frames_equal_one_chain_frames(gpu_device):
 
 
 @pytest.mark.parametrize("env", [dict(GSR_ASYNC_FAR="0"), dict(GSR_PRE_HIST_MIN_P="0"),
-                                 dict(GSR_ASYNC_FAR="0", GSR_PRE_HIST_MIN_P="0")],
-                         ids=["host-decided", "partial-sort", "host-decided+partial-sort"])
+                                 dict(GSR_ASYNC_FAR="0", GSR_PRE_HIST_MIN_P="0"),
+                                 dict(GSR_PRE_HIST_MIN_P="0", GSR_FULL_DEPTH_SORT="1")],
+                         ids=["host-decided", "partial-sort", "host-decided+partial-sort", "full-depth-sort"])
 def test_far_speculation_variants(env, gpu_device):
     """The same hit / miss / redo / automatic cases as above through the other paths of the far-chain speculation, each
     chosen by a knob that is read once per process (child process):
@@ -325,7 +326,9 @@ def test_far_speculation_variants(env, gpu_device):
     the host enqueues the far chain only if it is non-zero;
     GSR_PRE_HIST_MIN_P=0 -- k_preprocess counts the depth keys' digits on these small scenes too (as it does from 128 k
     Gaussians), so the frames that expect an idle far chain take the PARTIAL depth sort: near candidates compacted and
-    sorted on their own, the full sort left to the far chain -- which runs it in the miss cases here."""
+    sorted on their own, the full sort left to the far chain -- which runs it in the miss cases here;
+    GSR_FULL_DEPTH_SORT=1 -- with those counted histograms at hand (GSR_PRE_HIST_MIN_P=0 again: without them there is
+    no partial depth sort to switch off) every frame still sorts all Gaussians by depth up front."""
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
@@ -747,13 +750,14 @@ def test_sort_fallback_paths(knob, gpu_device):
 
 
 @pytest.mark.parametrize("knob", ["GSR_BLEND_BACKWARD_TILES", "GSR_BLEND_BACKWARD_QUADS", "GSR_BWD_IMAGE_ORDER",
-                                  "GSR_SYNC_FORWARD"])
+                                  "GSR_SYNC_FORWARD", "GSR_GBWD_ALL"])
 def test_blend_backward_kernel_variants(knob, gpu_device):
     """The blend backward has two kernels -- one wave per tile (four pixels per lane) for frames of >= 3072 tiles, one
     wave per 8x8 quad below -- and takes the tiles longest walk first.  The size rule alone would leave the tile
     kernel untested on the small scenes the oracle can check in full and the quad kernel untested on large frames, so
     each variant is forced on both (the knobs are read once per process: child process), gradients against the oracle;
-    GSR_SYNC_FORWARD=1 = every forward synchronous."""
+    GSR_SYNC_FORWARD=1 = every forward synchronous; GSR_GBWD_ALL=1 = the per-Gaussian backward walks its chain for
+    every visible Gaussian, not only for those the blend backward left records for."""
     import subprocess
     import sys
     code = (
