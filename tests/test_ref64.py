@@ -53,7 +53,11 @@ def test_autograd_matches_finite_differences_in_f64():
     """gradcheck of the whole restated forward (per-Gaussian stage + blend, one graph) in f64, away from every cut
     and every departure: ref64's gradients are the derivative of ref64's forward.  Then the split evaluation the other
     tests use (per-tile blend graphs + one per-Gaussian VJP, ref64.render) equals the one-graph gradient."""
-    sc = _gradcheck_scene()
+    _gradcheck_and_split_chain_rule(_gradcheck_scene())
+
+
+def _gradcheck_and_split_chain_rule(sc):
+    """(also run on a posed camera by tests/test_poses.py)"""
     O.set_threads(1)
     fr = O.forward(sc)
     vis = np.flatnonzero(fr.radii > 0)
