@@ -54,7 +54,7 @@ def _key(R):
 
 _lib = None
 
-EXPORTS = ("gsr_forward", "gsr_backward", "gsr_mark_visible", "gsr_geometry_bytes", "gsr_image_bytes",
+EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visible", "gsr_geometry_bytes", "gsr_image_bytes",
            "gsr_binning_bytes", "gsr_geometry_view_of", "gsr_binning_view_of", "gsr_image_view_of",
            "gsr_higher_msb", "gsr_last_error", "gsr_abi_version", "gsr_kernel_count", "gsr_kernel_name",
            "gsr_profile_enable", "gsr_profile_enable_only", "gsr_profile_read", "gsr_mailbox_slow_path_hits", "gsr_activate", "gsr_activate_backward", "gsr_adam_step",
@@ -86,6 +86,9 @@ def lib():
     L.gsr_backward.restype = ci
     L.gsr_backward.argtypes = [ci, ci, ci, ci, vp, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp, vp, vp, cf, cf, vp, vp, vp,
                                vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+    # gsr_backward's arguments + dL_ddepth (after dL_dacc) and dL_ddepths (after dL_drot)
+    L.gsr_backward_depth.restype = ci
+    L.gsr_backward_depth.argtypes = L.gsr_backward.argtypes[:25] + [vp] + L.gsr_backward.argtypes[25:34] + [vp, ci, vp]
     L.gsr_mark_visible.restype = ci
     L.gsr_mark_visible.argtypes = [ci, vp, vp, vp, vp, vp]
     for n in ("gsr_geometry_bytes", "gsr_binning_bytes"):
@@ -247,11 +250,14 @@ def rasterize_forward(background, means3D, colors, opacity, scales, rotations, s
 
 def rasterize_backward(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                        viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_acc, sh, degree, campos,
-                       geomBuffer, R, binningBuffer, imageBuffer, debug=False, return_conic=False, want_cov3D=True):
+                       geomBuffer, R, binningBuffer, imageBuffer, debug=False, return_conic=False, want_cov3D=True,
+                       grad_depth=None):
     """Mirror of RasterizeGaussiansBackwardCUDA (src/gs/rasterize_points.cu:132-224).
     Returns (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
     [+ dL_dconic when return_conic].  want_cov3D=False (only without cov3D_precomp): dL_dcov3D -- then an intermediate
-    nobody reads -- is neither allocated nor written and comes back as None."""
+    nobody reads -- is neither allocated nor written and comes back as None.
+    grad_depth ([1,H,W] or [H,W], the gradient w.r.t. the rendered depth; an extension, the reference has none):
+    gsr_backward_depth is called instead of gsr_backward and dL_ddepths [P] is appended to the result."""
     dev = means3D.device
     P = int(means3D.size(0))
     H, W = int(dL_dout_color.size(1)), int(dL_dout_color.size(2))
@@ -269,7 +275,22 @@ def rasterize_backward(background, means3D, radii, colors, scales, rotations, sc
     dL_dsh = mk((P, M, 3), **f32)
     dL_dscales = mk((P, 3), **f32)
     dL_drotations = mk((P, 4), **f32)
-    if P != 0:
+    dL_ddepths = mk((P,), **f32) if grad_depth is not None else None
+    if P != 0 and grad_depth is not None:
+        dpix = dL_dout_color.contiguous()
+        dacc = dL_dout_acc.contiguous()
+        if grad_depth.dtype != torch.float32 or grad_depth.device != dev or grad_depth.numel() != H * W:
+            raise ValueError("grad_depth must be a float32 tensor of H*W elements on the device of means3D")
+        ddep = grad_depth.contiguous()
+        _check(lib().gsr_backward_depth(P, int(degree), M, _key(R), _ptr(background), W, H, _ptr(means3D), _ptr(sh),
+                                        _ptr(colors), _ptr(scales), float(scale_modifier), _ptr(rotations),
+                                        _ptr(cov3D_precomp), _ptr(viewmatrix), _ptr(projmatrix), _ptr(campos),
+                                        float(tan_fovx), float(tan_fovy), _ptr(radii), _ptr(geomBuffer),
+                                        _ptr(binningBuffer), _ptr(imageBuffer), _ptr(dpix), _ptr(dacc), _ptr(ddep),
+                                        _ptr(dL_dmeans2D), _ptr(dL_dconic), _ptr(dL_dopacity), _ptr(dL_dcolors),
+                                        _ptr(dL_dmeans3D), _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales),
+                                        _ptr(dL_drotations), _ptr(dL_ddepths), int(bool(debug)), _stream()))
+    elif P != 0:
         dpix = dL_dout_color.contiguous()
         dacc = dL_dout_acc.contiguous()
         _check(lib().gsr_backward(P, int(degree), M, _key(R), _ptr(background), W, H, _ptr(means3D), _ptr(sh),
@@ -281,7 +302,9 @@ def rasterize_backward(background, means3D, radii, colors, scales, rotations, sc
                                   _ptr(dL_dcov3D), _ptr(dL_dsh), _ptr(dL_dscales), _ptr(dL_drotations),
                                   int(bool(debug)), _stream()))
     out = (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations)
-    return out + (dL_dconic,) if return_conic else out
+    if return_conic:
+        out = out + (dL_dconic,)
+    return out + (dL_ddepths,) if grad_depth is not None else out
 
 
 def last_num_rendered():

@@ -1405,14 +1405,17 @@ int gsr_async_outcomes_pending(void) {
 
 unsigned long long gsr_mailbox_slow_path_hits(void) { return g_mailbox_slow_hits.load(); }
 
-int gsr_backward(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
-                 const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
-                 const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
-                 const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
-                 char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
-                 const float* dL_dacc, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
-                 float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug,
-                 void* stream_) {
+// gsr_backward and gsr_backward_depth: with_depth selects the depth variants of the three kernels (dL_ddepth in,
+// dL_ddepths out); everything else is shared.
+static int backward_impl(bool with_depth, int P, int D, int M, int R, const float* background, int width, int height,
+                         const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                         float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                         const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                         float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                         const float* dL_dpix, const float* dL_dacc, const float* dL_ddepth, float* dL_dmean2D,
+                         float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                         float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_ddepths, int debug,
+                         void* stream_) {
   hipStream_t stream = (hipStream_t)stream_;
   g_err[0] = 0;
   if (P < 0 || R < 0 || width <= 0 || height <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/R/width/height");
@@ -1425,6 +1428,8 @@ int gsr_backward(int P, int D, int M, int R, const float* background, int width,
   if (!dL_dmean2D || !dL_dconic || !dL_dopacity || !dL_dcolor || !dL_dmean3D || (!dL_dcov3D && cov3D_precomp) ||
       !dL_dscale || !dL_drot || (M > 0 && !dL_dsh))
     return fail(GSR_ERR_INVALID_ARGUMENT, "null gradient output");
+  if (with_depth && !dL_ddepth) return fail(GSR_ERR_INVALID_ARGUMENT, "null dL_ddepth");
+  if (with_depth && !dL_ddepths) return fail(GSR_ERR_INVALID_ARGUMENT, "null dL_ddepths");
   if (env().host_trace)
     fprintf(stderr, "[gsr] backward entered at %.1f us (process clock)\n",
             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count());
@@ -1438,15 +1443,44 @@ int gsr_backward(int P, int D, int M, int R, const float* background, int width,
     // inst_flag, touched and total[2] are zero here: the forward initialises them and the gather kernels
     // below clear what the blend backward sets, so the same blobs can be differentiated again.
     const unsigned notes = frame_notes(image_buffer);
-    STAGE(launch_blend_backward(fp, g, b, im, background, dL_dpix, dL_dacc, (notes & NOTE_ORDER) != 0u, stream));
-    STAGE(launch_gather_records(fp, g, b, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, (notes & NOTE_SPLIT) != 0u,
+    STAGE(launch_blend_backward(fp, g, b, im, background, dL_dpix, dL_dacc, dL_ddepth, (notes & NOTE_ORDER) != 0u,
                                 stream));
+    STAGE(launch_gather_records(fp, g, b, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_ddepths,
+                                (notes & NOTE_SPLIT) != 0u, stream));
   }
   STAGE(launch_gaussian_backward(fp, g, b, radii, means3D, scales, rotations, colors_precomp ? nullptr : shs,
                                  cov3D_precomp, viewmatrix, projmatrix, campos, colors_precomp != nullptr, dL_dmean2D,
                                  dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
-                                 stream));
+                                 dL_ddepths, stream));
   return GSR_OK;
+}
+
+int gsr_backward(int P, int D, int M, int R, const float* background, int width, int height, const float* means3D,
+                 const float* shs, const float* colors_precomp, const float* scales, float scale_modifier,
+                 const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                 const float* projmatrix, const float* campos, float tan_fovx, float tan_fovy, const int* radii,
+                 char* geom_buffer, char* binning_buffer, char* image_buffer, const float* dL_dpix,
+                 const float* dL_dacc, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                 float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug,
+                 void* stream_) {
+  return backward_impl(false, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales,
+                       scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii,
+                       geom_buffer, binning_buffer, image_buffer, dL_dpix, dL_dacc, nullptr, dL_dmean2D, dL_dconic,
+                       dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, nullptr, debug, stream_);
+}
+
+int gsr_backward_depth(int P, int D, int M, int R, const float* background, int width, int height,
+                       const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                       float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                       float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                       const float* dL_dpix, const float* dL_dacc, const float* dL_ddepth, float* dL_dmean2D,
+                       float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                       float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_ddepths, int debug, void* stream_) {
+  return backward_impl(true, P, D, M, R, background, width, height, means3D, shs, colors_precomp, scales, scale_modifier,
+                       rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer,
+                       binning_buffer, image_buffer, dL_dpix, dL_dacc, dL_ddepth, dL_dmean2D, dL_dconic, dL_dopacity,
+                       dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_ddepths, debug, stream_);
 }
 
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

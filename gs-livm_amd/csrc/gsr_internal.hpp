@@ -372,9 +372,10 @@ struct BucketPass {
   uint32_t list_base;   // first list position of the chain (a far chain's lists start behind the near capacity)
 };
 // (split_frame: a near/far frame -- the Gaussians with records are looked for among the emitted ones' descriptors)
+// (dL_ddepths / dL_ddepth non-null: gsr_backward_depth -- the depth variants of the kernels, plus the tenth sum)
 hipError_t launch_gather_records(const FrameParams& fp, GeomState g, BinningState b, float* dL_dmean2D,
-                                 float* dL_dconic, float* dL_dopacity, float* dL_dcolor, bool split_frame,
-                                 hipStream_t s);
+                                 float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_ddepths,
+                                 bool split_frame, hipStream_t s);
 // Stable LSD radix sort of n (u32, u32) pairs on key bits [0, end_bit); buffers ping-pong between
 // (keysA, valsA) and (keysB, valsB), starting in A when start_in_A.
 hipError_t launch_sort_pairs(uint32_t* keysA, uint32_t* valsA, uint32_t* keysB, uint32_t* valsB, SortScratch sc,
@@ -410,13 +411,15 @@ hipError_t launch_release_go(Count gate, uint32_t* go, uint32_t seq, hipStream_t
 hipError_t launch_decide_far(const uint32_t* live_quads, AsyncWords aw, hipStream_t s);
 hipError_t launch_tile_order(const FrameParams& fp, ImageState im, hipStream_t s);
 hipError_t launch_blend_backward(const FrameParams& fp, GeomState g, BinningState b, ImageState im, const float* bg,
-                                 const float* dL_dpix, const float* dL_dacc, bool have_tile_order, hipStream_t s);
+                                 const float* dL_dpix, const float* dL_dacc, const float* dL_ddepth, bool have_tile_order,
+                                 hipStream_t s);
 hipError_t launch_gaussian_backward(const FrameParams& fp, GeomState g, BinningState b, const int* radii,
                                     const float* means3D, const float* scales, const float* rotations,
                                     const float* shs, const float* cov3D_precomp, const float* view, const float* proj,
                                     const float* campos, bool colors_precomp, float* dL_dmean2D, float* dL_dconic,
                                     float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
-                                    float* dL_dsh, float* dL_dscale, float* dL_drot, hipStream_t s);
+                                    float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_ddepths,
+                                    hipStream_t s);
 hipError_t launch_mark_visible(int P, const float* means3D, const float* view, unsigned char* present, hipStream_t s);
 // optimizer.hip ("next" row: fused activations + Adam)
 hipError_t launch_activate(int P, int M, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,

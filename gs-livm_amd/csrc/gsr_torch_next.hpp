@@ -125,4 +125,27 @@ size_t write_ply(const std::string& file_path, const torch::Tensor& xyz, const t
                  const torch::Tensor& rotation);
 std::vector<std::string> ply_attribute_names(int M);  // construct_list_of_attributes
 
+// ---- depth gradient (torch_binding.cpp; an extension, the reference's backward ignores the depth output's gradient) ----
+// The reference's GaussianRasterizationSettings cannot grow a field (torch_binding.cpp is compiled against the
+// reference's own header too), so the opt-in is a switch of the calling thread: a forward of _RasterizeGaussians
+// captures it, and that render's backward then uses the gradient of its depth output when one arrives (a depth L1
+// against a LiDAR depth image, the delta-depth term of lioOptimization.cpp:1780-1814, depth regularisers).
+// Off by default.  Returns the previous value.
+bool set_depth_gradient(bool on);
+
 }  // namespace gsr_torch
+
+// RasterizeGaussiansBackwardCUDA with the gradient of the depth output (gsr_backward_depth): the same arguments plus
+// dL_dout_depth ([1,H,W]) after dL_dout_acc; the same eight gradients plus dL_ddepths [P] (dL/d view-space depth).
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor, torch::Tensor>
+RasterizeGaussiansBackwardDepthCUDA(const torch::Tensor& background, const torch::Tensor& means3D,
+                                    const torch::Tensor& radii, const torch::Tensor& colors, const torch::Tensor& scales,
+                                    const torch::Tensor& rotations, const float scale_modifier,
+                                    const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
+                                    const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+                                    const torch::Tensor& dL_dout_color, const torch::Tensor& dL_dout_acc,
+                                    const torch::Tensor& dL_dout_depth, const torch::Tensor& sh, const int degree,
+                                    const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
+                                    const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
+                                    const bool debug);

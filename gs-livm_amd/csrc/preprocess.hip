@@ -1357,16 +1357,25 @@ __device__ __forceinline__ void swap_add16_(float& a, float& b) {
 // (the register allocator settles on 102 VGPRs = four waves per SIMD for k_gather_records; asked for 96 it finds 86 without a spill)
 // the nine sums of one Gaussian's records, per lane (lane = slot mod 64)
 struct RecordSums {
+  static constexpr bool depth = false;
   float v0 = 0, v1 = 0, v2 = 0, v3 = 0, v4 = 0, v5 = 0, v6 = 0, v7 = 0, v8 = 0;
+};
+// gsr_backward_depth: a tenth sum, dL/dz = sum alpha T dL/ddepth.  The depth variants of the blend kernels leave
+// floats 8..11 of a record as (dLG, dLG', dz, dz') -- the quad kernel (sum, 0, sum, 0), the tile kernel the sums of the
+// wave's rows 0+1 and 2+3 -- so v8 += c.x + c.y completes the association (r0 + r1) + (r2 + r3) of the plain path.
+struct RecordSumsDepth : RecordSums {
+  static constexpr bool depth = true;
+  float v9 = 0;
 };
 // Slots [base, base + 512) of the run [first, first + n): the eight flags of a lane are requested at once, then its
 // flagged records in two groups of four, summed in slot order (three round trips for 512 slots; 1024 slots at a time
 // with sixteen flags measured slower: registers).
 constexpr uint32_t GATHER_CHUNK = 512;
 constexpr uint32_t GATHER_SHARED_FROM = 2048;  // runs longer than this are shared by the workgroup's waves
+template <class Sums>
 __device__ __forceinline__ void gather_chunk(const size_t first, const uint32_t n, const uint32_t base, const int lane,
                                              const float4* __restrict__ grad_inst, uint8_t* __restrict__ inst_flag,
-                                             RecordSums& r) {
+                                             Sums& r) {
   uint8_t f[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) {
@@ -1392,7 +1401,12 @@ __device__ __forceinline__ void gather_chunk(const size_t first, const uint32_t 
       if (f[4 * q + j]) {
         r.v0 += a[j].x; r.v1 += a[j].y; r.v2 += a[j].z; r.v3 += a[j].w;
         r.v4 += b[j].x; r.v5 += b[j].y; r.v6 += b[j].z; r.v7 += b[j].w;
-        r.v8 += (c[j].x + c[j].y) + (c[j].z + c[j].w);  // the four 16-lane-row sums of dLG the tile kernel leaves
+        if constexpr (Sums::depth) {
+          r.v8 += c[j].x + c[j].y;
+          r.v9 += c[j].z + c[j].w;
+        } else {
+          r.v8 += (c[j].x + c[j].y) + (c[j].z + c[j].w);  // the four 16-lane-row sums of dLG the tile kernel leaves
+        }
       }
     }
   }
@@ -1402,10 +1416,12 @@ __device__ __forceinline__ void gather_chunk(const size_t first, const uint32_t 
 // dLG = G dL/dalpha.  The factors every pixel and every instance of the Gaussian share are applied here, ONCE per
 // Gaussian (backward.cu:561-562, 583-597):
 //   dL/dmean2D = -(conic (S3, S4)) * opacity * (W/2, H/2),  dL/dconic = -1/2 opacity (S5, S6, S7),  dL/dopacity = sum dLG
-__device__ __forceinline__ void gather_finish(RecordSums r, const uint32_t id, const int lane, const float cx, const float cy,
+template <class Sums>
+__device__ __forceinline__ void gather_finish(Sums r, const uint32_t id, const int lane, const float cx, const float cy,
                                               const float cz, const float op, const float ddelx_dx, const float ddely_dy,
                                               float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic,
-                                              float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolor) {
+                                              float* __restrict__ dL_dopacity, float* __restrict__ dL_dcolor,
+                                              float* __restrict__ dL_ddepths) {
   // (v0,v4) (v1,v5) (v2,v6) (v3,v7) across half-waves, then rows, then inside rows
   swap_add32_(r.v0, r.v4);
   swap_add32_(r.v1, r.v5);
@@ -1425,16 +1441,27 @@ __device__ __forceinline__ void gather_finish(RecordSums r, const uint32_t id, c
   if (lane == 32) { dL_dmean2D[3 * id + 1] = -(cz * S4 + cy * S3) * (op * ddely_dy); dL_dconic[4 * id] = w1 * mc; }
   if (lane == 48) { dL_dconic[4 * id + 1] = w0 * mc; dL_dconic[4 * id + 3] = w1 * mc; }
   if (lane == 63) dL_dopacity[id] = v8;
+  if constexpr (Sums::depth) {
+    float v9 = row_allsum_(r.v9);
+    v9 += dpp_get_<0x142, 0xA>(v9);  // row_bcast:15
+    v9 += dpp_get_<0x143, 0xC>(v9);  // row_bcast:31 -> total in lane 63
+    if (lane == 63) dL_ddepths[id] = v9;
+  }
 }
 
+// Sums = RecordSumsDepth (gsr_backward_depth): also writes dL_ddepths [P] for the Gaussians it gathers
+// (k_gaussian_backward zeroes the others); with RecordSums, dL_ddepths (null) is never touched
+template <class Sums = RecordSums>
 __global__ __launch_bounds__(PRE_BLOCK) __attribute__((amdgpu_num_vgpr(96))) void k_gather_records(
     GeomState g, const float4* __restrict__ grad_inst, uint8_t* __restrict__ inst_flag,
     float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic, float* __restrict__ dL_dopacity,
-    float* __restrict__ dL_dcolor, const float ddelx_dx, const float ddely_dy, const int P, const bool from_descriptors) {
+    float* __restrict__ dL_dcolor, const float ddelx_dx, const float ddely_dy, const int P, const bool from_descriptors,
+    float* __restrict__ dL_ddepths) {
   constexpr int NW = PRE_BLOCK / 64;
+  constexpr int NS = Sums::depth ? 10 : 9;
   __shared__ uint32_t s_long[PRE_BLOCK];  // Gaussians of this round whose runs the workgroup's waves share
   __shared__ uint32_t s_nlong;
-  __shared__ float s_part[NW][9][64];
+  __shared__ float s_part[NW][NS][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const uint32_t nwaves = gridDim.x * NW;
   // Which Gaussians have records: the list k_compact_touched made of the flagged ones -- or, in a near/far frame, simply
@@ -1481,13 +1508,13 @@ __global__ __launch_bounds__(PRE_BLOCK) __attribute__((amdgpu_num_vgpr(96))) voi
       const uint32_t id = (uint32_t)__builtin_amdgcn_readlane((int)cand, src);
       const size_t first = (uint32_t)__builtin_amdgcn_readlane((int)my_first, src);
       const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)my_n, src);
-      RecordSums r;
+      Sums r;
       for (uint32_t cb = 0; cb < n; cb += GATHER_CHUNK) gather_chunk(first, n, cb, lane, grad_inst, inst_flag, r);
       gather_finish(r, id, lane, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_ra.z), src)),
                     __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_ra.w), src)),
                     __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_rb.x), src)),
                     __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_rb.y), src)), ddelx_dx, ddely_dy, dL_dmean2D,
-                    dL_dconic, dL_dopacity, dL_dcolor);
+                    dL_dconic, dL_dopacity, dL_dcolor, dL_ddepths);
     }
     __syncthreads();
     const uint32_t nlong = s_nlong;
@@ -1495,15 +1522,16 @@ __global__ __launch_bounds__(PRE_BLOCK) __attribute__((amdgpu_num_vgpr(96))) voi
       const uint32_t id = s_long[i];
       const size_t first = g.slotinfo[id].x;
       const uint32_t n = g.gpack[id].x;
-      RecordSums r;
+      Sums r;
       for (uint32_t cb = (uint32_t)w * GATHER_CHUNK; cb < n; cb += NW * GATHER_CHUNK)
         gather_chunk(first, n, cb, lane, grad_inst, inst_flag, r);
       s_part[w][0][lane] = r.v0; s_part[w][1][lane] = r.v1; s_part[w][2][lane] = r.v2;
       s_part[w][3][lane] = r.v3; s_part[w][4][lane] = r.v4; s_part[w][5][lane] = r.v5;
       s_part[w][6][lane] = r.v6; s_part[w][7][lane] = r.v7; s_part[w][8][lane] = r.v8;
+      if constexpr (Sums::depth) s_part[w][9][lane] = r.v9;
       __syncthreads();
       if (w == 0) {
-        RecordSums t;
+        Sums t;
         float* tv[9] = {&t.v0, &t.v1, &t.v2, &t.v3, &t.v4, &t.v5, &t.v6, &t.v7, &t.v8};
 #pragma unroll
         for (int k = 0; k < 9; k++) {
@@ -1512,9 +1540,16 @@ __global__ __launch_bounds__(PRE_BLOCK) __attribute__((amdgpu_num_vgpr(96))) voi
           for (int ww = 1; ww < NW; ww++) acc += s_part[ww][k][lane];
           *tv[k] = acc;
         }
+        if constexpr (Sums::depth) {
+          float acc = s_part[0][9][lane];
+#pragma unroll
+          for (int ww = 1; ww < NW; ww++) acc += s_part[ww][9][lane];
+          t.v9 = acc;
+        }
         const float4 ra = g.splats[(size_t)id * SPLAT_F4 + 0];
         const float4 rb = g.splats[(size_t)id * SPLAT_F4 + 1];
-        gather_finish(t, id, lane, ra.z, ra.w, rb.x, rb.y, ddelx_dx, ddely_dy, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor);
+        gather_finish(t, id, lane, ra.z, ra.w, rb.x, rb.y, ddelx_dx, ddely_dy, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor,
+                      dL_ddepths);
       }
       __syncthreads();
     }
@@ -1533,6 +1568,10 @@ __global__ __launch_bounds__(PRE_BLOCK) __attribute__((amdgpu_num_vgpr(96))) voi
 // ------------------------------------------------------------------------------------------------
 // `row`: null = the Gaussian's SH row is read from shs and its gradient row written to dL_dsh directly (M == 1);
 // else the LDS row that holds the SH coefficients on entry and the gradient on exit (staged variant, M > 1).
+// DEPTH (gsr_backward_depth): dL_ddepths[idx] = dL/dz of the Gaussian's view-space depth, left by k_gather_records<RecordSumsDepth>;
+// z = V[2] x + V[6] y + V[10] z_world + V[14] (the view matrix is column-major: its third ROW), so the mean gets
+// dL/dz (V[2], V[6], V[10]) on top.  Every element of dL_ddepths is written (0 without a record).
+template <bool DEPTH>
 __device__ __forceinline__ void gaussian_backward_one(
     const int idx, float* row,
     const FrameParams& fp, GeomState& g, const int* __restrict__ radii, const float* __restrict__ means3D, const float* __restrict__ scales,
@@ -1541,7 +1580,7 @@ __device__ __forceinline__ void gaussian_backward_one(
     const int colors_are_precomp, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
     float* __restrict__ dL_dmean3D,
     float* __restrict__ dL_dcov3D, float* __restrict__ dL_dsh, float* __restrict__ dL_dscale,
-    float* __restrict__ dL_drot, const bool skip_recordless) {
+    float* __restrict__ dL_drot, float* dL_ddepths, const bool skip_recordless) {
   // Two round trips: the Gaussian's radius and "touched" flag first -- a Gaussian without a gradient record (culled, or
   // visible but taken by no pixel: 97 % of the scene in a dense near/far frame) gets its zeros written and reads nothing
   // else -- then, for the others, every remaining input at once (record sums, mean, covariance inputs, clamp bits)
@@ -1560,6 +1599,7 @@ __device__ __forceinline__ void gaussian_backward_one(
     dL_dmean2D[3 * idx] = 0.f; dL_dmean2D[3 * idx + 1] = 0.f; dL_dmean2D[3 * idx + 2] = 0.f;
     dL_dconic[4 * idx] = 0.f; dL_dconic[4 * idx + 1] = 0.f; dL_dconic[4 * idx + 2] = 0.f; dL_dconic[4 * idx + 3] = 0.f;
     dL_dopacity[idx] = 0.f;
+    if constexpr (DEPTH) dL_ddepths[idx] = 0.f;
     dL_dcolor[3 * idx] = 0.f; dL_dcolor[3 * idx + 1] = 0.f; dL_dcolor[3 * idx + 2] = 0.f;
     dL_dmean3D[3 * idx] = 0.f; dL_dmean3D[3 * idx + 1] = 0.f; dL_dmean3D[3 * idx + 2] = 0.f;
     if (dL_dcov3D) {  // (null: the 3-D covariance is not an input of the caller's graph, nobody reads its gradient)
@@ -1575,6 +1615,11 @@ __device__ __forceinline__ void gaussian_backward_one(
   const float gcol0 = rec ? dL_dcolor[3 * idx] : 0.f, gcol1 = rec ? dL_dcolor[3 * idx + 1] : 0.f, gcol2 = rec ? dL_dcolor[3 * idx + 2] : 0.f;
   const float gmx = rec ? dL_dmean2D[3 * idx] : 0.f, gmy = rec ? dL_dmean2D[3 * idx + 1] : 0.f;
   const float gca = rec ? dL_dconic[4 * idx] : 0.f, gcb = rec ? dL_dconic[4 * idx + 1] : 0.f, gcc = rec ? dL_dconic[4 * idx + 3] : 0.f;
+  float gz = 0.f;
+  if constexpr (DEPTH) {
+    if (rec) gz = dL_ddepths[idx];
+    else dL_ddepths[idx] = 0.f;
+  }
   if (!rec) {
     dL_dmean2D[3 * idx] = 0.f; dL_dmean2D[3 * idx + 1] = 0.f;
     dL_dconic[4 * idx] = 0.f; dL_dconic[4 * idx + 1] = 0.f; dL_dconic[4 * idx + 3] = 0.f;
@@ -1734,6 +1779,9 @@ __device__ __forceinline__ void gaussian_backward_one(
   } else {
     for (int k = 0; k < M * 3; k++) gs[k] = 0.f;
   }
+  if constexpr (DEPTH) {
+    dm0 += V[2] * gz; dm1 += V[6] * gz; dm2 += V[10] * gz;
+  }
   dL_dmean3D[3 * idx] = dm0; dL_dmean3D[3 * idx + 1] = dm1; dL_dmean3D[3 * idx + 2] = dm2;
   // ---- covariance -> scale / rotation (backward.cu:279-366) ----
   if (scales) {
@@ -1783,7 +1831,7 @@ __device__ __forceinline__ void gaussian_backward_one(
   }
 }
 
-template <bool STAGED>
+template <bool STAGED, bool DEPTH = false>
 __global__ __launch_bounds__(PRE_BLOCK) void k_gaussian_backward(
     const FrameParams fp, GeomState g, const int* __restrict__ radii, const float* __restrict__ means3D, const float* __restrict__ scales,
     const float* __restrict__ rotations, const float* __restrict__ shs, const float* __restrict__ cov3D_precomp,
@@ -1791,7 +1839,7 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_gaussian_backward(
     const int colors_are_precomp, float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
     float* __restrict__ dL_dmean3D,
     float* __restrict__ dL_dcov3D, float* __restrict__ dL_dsh, float* __restrict__ dL_dscale,
-    float* __restrict__ dL_drot, const bool skip_recordless) {
+    float* __restrict__ dL_drot, const bool skip_recordless, float* dL_ddepths) {
   extern __shared__ float sh_rows[];  // STAGED: SH rows in, dL_dsh rows out (listed_rows_to_lds / lds_to_rows)
   __shared__ uint32_t s_rec[PRE_BLOCK];  // STAGED: block-local rows of the Gaussians with a gradient record
   __shared__ uint32_t s_nrec;
@@ -1807,9 +1855,10 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_gaussian_backward(
     __syncthreads();
   }
   if (idx < fp.P)
-    gaussian_backward_one(idx, STAGED ? sh_rows + threadIdx.x * sh_row_stride(C) : nullptr, fp, g, radii, means3D, scales,
-                          rotations, shs, cov3D_precomp, V, Pm, campos, colors_are_precomp, dL_dmean2D, dL_dconic,
-                          dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, skip_recordless);
+    gaussian_backward_one<DEPTH>(idx, STAGED ? sh_rows + threadIdx.x * sh_row_stride(C) : nullptr, fp, g, radii, means3D,
+                                 scales, rotations, shs, cov3D_precomp, V, Pm, campos, colors_are_precomp, dL_dmean2D,
+                                 dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                                 dL_ddepths, skip_recordless);
   if (STAGED) {
     __syncthreads();
     lds_to_rows(dL_dsh + (size_t)row0 * C, sh_rows, nrows, C);
@@ -1962,8 +2011,8 @@ hipError_t launch_emit_scatter(const EmitFusion& ef, uint16_t* keys_out, uint32_
 }
 
 hipError_t launch_gather_records(const FrameParams& fp, GeomState g, BinningState b, float* dL_dmean2D,
-                                 float* dL_dconic, float* dL_dopacity, float* dL_dcolor, bool split_frame,
-                                 hipStream_t s) {
+                                 float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_ddepths,
+                                 bool split_frame, hipStream_t s) {
   const int nb = (fp.P + PRE_BLOCK - 1) / PRE_BLOCK;
   if (!split_frame) {
     ProfScope ps(K_COMPACT_TOUCHED, s);
@@ -1976,8 +2025,14 @@ hipError_t launch_gather_records(const FrameParams& fp, GeomState g, BinningStat
     // length is only known on the device), capped where the chip is full several times over
     const int want = (fp.P + PRE_BLOCK / 64 - 1) / (PRE_BLOCK / 64);
     const int grid = want < 4096 ? want : 4096;
-    hipLaunchKernelGGL(k_gather_records, dim3(grid), dim3(PRE_BLOCK), 0, s, g, b.grad_inst, b.inst_flag, dL_dmean2D,
-                       dL_dconic, dL_dopacity, dL_dcolor, 0.5f * (float)fp.W, 0.5f * (float)fp.H, fp.P, split_frame);
+    if (dL_ddepths)
+      hipLaunchKernelGGL(k_gather_records<RecordSumsDepth>, dim3(grid), dim3(PRE_BLOCK), 0, s, g, b.grad_inst,
+                         b.inst_flag, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, 0.5f * (float)fp.W,
+                         0.5f * (float)fp.H, fp.P, split_frame, dL_ddepths);
+    else
+      hipLaunchKernelGGL(k_gather_records<>, dim3(grid), dim3(PRE_BLOCK), 0, s, g, b.grad_inst, b.inst_flag, dL_dmean2D,
+                         dL_dconic, dL_dopacity, dL_dcolor, 0.5f * (float)fp.W, 0.5f * (float)fp.H, fp.P, split_frame,
+                         nullptr);
   }
   return hipGetLastError();
 }
@@ -1987,21 +2042,32 @@ hipError_t launch_gaussian_backward(const FrameParams& fp, GeomState g, BinningS
                                     const float* shs, const float* cov3D_precomp, const float* view, const float* proj,
                                     const float* campos, bool colors_precomp, float* dL_dmean2D, float* dL_dconic,
                                     float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
-                                    float* dL_dsh, float* dL_dscale, float* dL_drot, hipStream_t s) {
+                                    float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_ddepths,
+                                    hipStream_t s) {
   const int nb = (fp.P + PRE_BLOCK - 1) / PRE_BLOCK;
   ProfScope ps_k_gaussian_bwd(K_GAUSSIAN_BWD, s);
   const size_t stage = (shs && !colors_precomp) ? sh_stage_bytes(fp.M) : 0;  // M > 1: SH / dL_dsh rows go through LDS
   const bool skip_recordless = !env().gbwd_all;  // (GSR_GBWD_ALL=1: diagnostics)
-  if (stage)
+  if (dL_ddepths) {  // gsr_backward_depth
+    if (stage)
+      hipLaunchKernelGGL((k_gaussian_backward<true, true>), dim3(nb), dim3(PRE_BLOCK), stage, s, fp, g, radii, means3D,
+                         scales, rotations, shs, cov3D_precomp, view, proj, campos, 0, dL_dmean2D, dL_dconic, dL_dopacity,
+                         dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, skip_recordless, dL_ddepths);
+    else
+      hipLaunchKernelGGL((k_gaussian_backward<false, true>), dim3(nb), dim3(PRE_BLOCK), 0, s, fp, g, radii, means3D,
+                         scales, rotations, shs, cov3D_precomp, view, proj, campos, colors_precomp ? 1 : 0, dL_dmean2D,
+                         dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
+                         skip_recordless, dL_ddepths);
+  } else if (stage)
     hipLaunchKernelGGL(k_gaussian_backward<true>, dim3(nb), dim3(PRE_BLOCK), stage, s, fp, g, radii,
                        means3D, scales, rotations, shs, cov3D_precomp, view, proj, campos, 0,
                        dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
-                       skip_recordless);
+                       skip_recordless, nullptr);
   else
     hipLaunchKernelGGL(k_gaussian_backward<false>, dim3(nb), dim3(PRE_BLOCK), 0, s, fp, g, radii,
                        means3D, scales, rotations, shs, cov3D_precomp, view, proj, campos, colors_precomp ? 1 : 0,
                        dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot,
-                       skip_recordless);
+                       skip_recordless, nullptr);
   return hipGetLastError();
 }
 

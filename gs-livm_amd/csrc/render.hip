@@ -446,15 +446,23 @@ __global__ __launch_bounds__(64 * FW) void k_blend_forward(const FrameParams fp,
 // BCHUNK = list entries staged per round (one per thread of the first BCHUNK/64 waves).  128 instead of 256
 // halves the LDS footprint (the per-quad partial sums dominate it), doubling the resident workgroups per CU:
 // the kernel is latency-bound at 3 waves/SIMD (SQ counters: VALU issue active 36 % of wave cycles).
-template <int BCHUNK>
+//
+// DEPTH (gsr_backward_depth): the rendered depth sum_i z_i alpha_i T_i carries a gradient g_d = dL/ddepth of its own.  z is
+// one more "colour" of the splat as far as alpha is concerned -- q gains z g_d, the recurrence is otherwise the same and
+// its seed too (the depth image has no background term) -- and, like a colour, it has a direct term
+// dL/dz = sum alpha T g_d (the weight dch below): a tenth per-instance sum.  Without DEPTH, dL_ddepth (null) is never
+// read and the kernel is the code it was before the depth gradient existed (if constexpr removes every trace).
+template <int BCHUNK, bool DEPTH = false>
 __global__ __launch_bounds__(256) void k_blend_backward(
     const FrameParams fp, const uint2* __restrict__ ranges, const uint32_t* __restrict__ quad_last_in,
     const uint32_t* __restrict__ point_list, const float4* __restrict__ splats, const uint2* __restrict__ slotinfo,
     const float* __restrict__ bg, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
     const float* __restrict__ dL_dpix, const float* __restrict__ dL_dacc, float4* __restrict__ grad_inst,
     uint8_t* __restrict__ inst_flag, uint8_t* __restrict__ touched, const uint32_t* __restrict__ tile_order,
-    const uint2* __restrict__ rangesB) {
+    const uint2* __restrict__ rangesB, const float* __restrict__ dL_ddepth) {
   constexpr int LW = BCHUNK / 64;  // loader waves
+  // floats per (quad, entry) partial: DEPTH gives every row a fourth value, its share of the tenth sum
+  constexpr int PF = DEPTH ? 16 : 12, RF = PF / 4;
   // one 48-byte image per staged entry -- (x, y, conic.x', conic.y' | conic.z', opacity, r, g | b, conic) with the
   // primed terms pre-scaled for exp2 -- so a visit
   // addresses all of it from ONE register (base + 48 jj) with immediate offsets
@@ -464,7 +472,7 @@ __global__ __launch_bounds__(256) void k_blend_backward(
   // per (quad, entry): four (pair of wave totals, 16-lane-row partial of the ninth value) triples, one per row of the
   // wave: the row partials are added in the combine step (once per instance) instead of two more cross-lane steps
   // per visit
-  __shared__ __attribute__((aligned(16))) float sPart[4][BCHUNK][12];
+  __shared__ __attribute__((aligned(16))) float sPart[4][BCHUNK][PF];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int tile = tile_order ? (int)tile_order[blockIdx.x] : (int)blockIdx.x;  // longest walk first (k_tile_order)
   const int tile_x = tile % fp.gx, tile_y = tile / fp.gx;
@@ -488,6 +496,8 @@ __global__ __launch_bounds__(256) void k_blend_backward(
   const float dp0 = inside ? dL_dpix[pid] : 0.f, dp1 = inside ? dL_dpix[N + pid] : 0.f,
               dp2 = inside ? dL_dpix[2 * N + pid] : 0.f;
   const float dacc = inside ? dL_dacc[pid] : 0.f;  // the reference reads this unguarded (backward.cu:497)
+  float ddep = 0.f;
+  if constexpr (DEPTH) ddep = inside ? dL_ddepth[pid] : 0.f;
   float T = T_final;
   // ONE recurrence instead of the reference's four (accum_rec[3], accum_acc_rec; backward.cu:533-571).  dL/dalpha of a
   // splat is T (q - S) with q = colour . dL/dpixel + 1 * dL/dacc of THIS splat and S = the same dot product of what lies
@@ -502,7 +512,7 @@ __global__ __launch_bounds__(256) void k_blend_backward(
   // this lane's pair slot (first 8 floats) and row slot (last 4) inside an entry's 12 floats
   // (row r of the wave owns floats [3r, 3r + 2]: its pair of wave totals and its share of the ninth value -- one
   // 12-byte store per visit from one address register)
-  float* const my_part = &sPart[w][0][0] + 3 * (lane >> 4);
+  float* const my_part = &sPart[w][0][0] + RF * (lane >> 4);
   for (int base = 0; base < n; base += BCHUNK) {
     const int k = base + tid;  // k-th entry counted from the back of [0, n)
     const bool stager = tid < BCHUNK;
@@ -520,7 +530,8 @@ __global__ __launch_bounds__(256) void k_blend_backward(
       constexpr float L2E = 1.4426950408889634f;
       sE[tid][0] = make_float4(a.x, a.y, a.z * (-0.5f * L2E), a.w * (-L2E));
       sE[tid][1] = make_float4(b.x * (-0.5f * L2E), b.y, b.z, b.w);
-      sE[tid][2] = make_float4(c.x, a.z, a.w, b.x);
+      if constexpr (DEPTH) sE[tid][2] = make_float4(c.x, c.y, a.w, b.x);  // (blue, view-space depth z, -, -)
+      else sE[tid][2] = make_float4(c.x, a.z, a.w, b.x);
       sId[tid] = id;
       sSlot[tid] = si.x + (uint32_t)((tile_y - y0) * rw + (tile_x - x0));
       hits = quad_hits(a.x, a.y, c.z, c.w, tx0, ty0);
@@ -554,6 +565,8 @@ __global__ __launch_bounds__(256) void k_blend_backward(
         const float4 a = sE[jj][0];
         const float4 b = sE[jj][1];
         const float blue = sE[jj][2].x;
+        float dacc_z = dacc;  // DEPTH: dL/dacc + z dL/ddepth (g_d = 0 leaves dacc as it is, bit for bit)
+        if constexpr (DEPTH) dacc_z = __builtin_fmaf(sE[jj][2].y, ddep, dacc);
         const float dx = a.x - pfx, dy = a.y - pfy;
         const float power = splat_power(a.z, a.w, b.x, dx, dy);  // = log2(e) x the reference's power
         const float Graw = __builtin_amdgcn_exp2f(power);
@@ -570,7 +583,7 @@ __global__ __launch_bounds__(256) void k_blend_backward(
         const float oma = 1.0f - alpha;
         const float rom = __builtin_amdgcn_rcpf(oma);
         const float Tn = T * rom;  // T / (1 - alpha)
-        const float D = __builtin_fmaf(b.z, dp0, __builtin_fmaf(b.w, dp1, __builtin_fmaf(blue, dp2, dacc))) - S;
+        const float D = __builtin_fmaf(b.z, dp0, __builtin_fmaf(b.w, dp1, __builtin_fmaf(blue, dp2, dacc_z))) - S;
         if (__ballot(ok) != 0ull) {
           const float G = ok ? Graw : 0.0f;
           const float dch = alpha * Tn;
@@ -591,13 +604,17 @@ __global__ __launch_bounds__(256) void k_blend_backward(
           // pin the sums here: otherwise the compiler sinks the last add of each tree into the 4-lane store block
           // below and leaves a v_mov_dpp + v_add pair where one v_add_dpp does (3 instructions per visit)
           asm volatile("" : "+v"(w0), "+v"(w1), "+v"(g8));
+          float g9 = 0.f;  // DEPTH: this row's share of dL/dz = sum alpha T g_d
+          if constexpr (DEPTH) g9 = row_allsum(dch * ddep);
           if ((lane & 15) == 0) {  // lanes 0,16,32,48 hold the totals of (g0,g1),(g2,g3),(g4,g5),(g6,g7)
-            float* const dst = my_part + 12u * (uint32_t)jj;  // (w0, w1, this row's share of the opacity partial)
+            float* const dst = my_part + (uint32_t)PF * (uint32_t)jj;  // (w0, w1, this row's share of the opacity partial)
             dst[0] = w0; dst[1] = w1; dst[2] = g8;
+            if constexpr (DEPTH) dst[3] = g9;
           }
         } else if ((lane & 15) == 0) {
-          float* const dst = my_part + 12u * (uint32_t)jj;
+          float* const dst = my_part + (uint32_t)PF * (uint32_t)jj;
           dst[0] = 0.f; dst[1] = 0.f; dst[2] = 0.f;
+          if constexpr (DEPTH) dst[3] = 0.f;
         }
         // Fold this splat into the "everything behind the next one" accumulators NOW (the reference does it at the
         // top of its next iteration from saved (last_alpha, last_color), backward.cu:533-543), in the form
@@ -612,6 +629,7 @@ __global__ __launch_bounds__(256) void k_blend_backward(
       // hit bits of entry `tid`, quad order 0..3 fixed => reproducible sums
       const int lw = tid >> 6;
       float s[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      float s9 = 0.f;
       bool any = false;
 #pragma unroll
       for (int q = 0; q < 4; q++) {
@@ -619,10 +637,12 @@ __global__ __launch_bounds__(256) void k_blend_backward(
           any = true;
 #pragma unroll
           for (int r = 0; r < 4; r++) {  // row r carries the wave totals of values 2r, 2r + 1
-            s[2 * r] += sPart[q][tid][3 * r];
-            s[2 * r + 1] += sPart[q][tid][3 * r + 1];
+            s[2 * r] += sPart[q][tid][RF * r];
+            s[2 * r + 1] += sPart[q][tid][RF * r + 1];
           }
-          s[8] += (sPart[q][tid][2] + sPart[q][tid][5]) + (sPart[q][tid][8] + sPart[q][tid][11]);
+          s[8] += (sPart[q][tid][2] + sPart[q][tid][RF + 2]) + (sPart[q][tid][2 * RF + 2] + sPart[q][tid][3 * RF + 2]);
+          if constexpr (DEPTH)
+            s9 += (sPart[q][tid][3] + sPart[q][tid][RF + 3]) + (sPart[q][tid][2 * RF + 3] + sPart[q][tid][3 * RF + 3]);
         }
       }
       if (any) {
@@ -631,7 +651,8 @@ __global__ __launch_bounds__(256) void k_blend_backward(
         // k_gather_records, after its instances have been summed
         grad_inst[slot * GRAD_F4 + 0] = make_float4(s[0], s[1], s[2], s[3]);
         grad_inst[slot * GRAD_F4 + 1] = make_float4(s[4], s[5], s[6], s[7]);
-        grad_inst[slot * GRAD_F4 + 2] = make_float4(s[8], 0.f, 0.f, 0.f);
+        // (DEPTH: float 10 carries the tenth sum; the depth gather adds floats 8 + 9 and 10 + 11, see k_gather_records)
+        grad_inst[slot * GRAD_F4 + 2] = make_float4(s[8], 0.f, DEPTH ? s9 : 0.f, 0.f);
         inst_flag[slot] = 1;
         touched[sId[tid]] = 1;  // same value from every writer: a benign race
       }
@@ -702,14 +723,17 @@ __global__ __launch_bounds__(1024) void k_tile_order(const uint32_t* __restrict_
   for (int t = tid + 8192; t < T; t += 1024) order[atomicAdd(&bins[walk(t)], 1u)] = (uint32_t)t;
 }
 
-template <int TW>  // tiles (= waves) per workgroup; the waves never synchronise
+// DEPTH: as in k_blend_backward.  The record has no room for four more row sums, so the depth variant adds the
+// rows in pairs itself (one v_permlane16_swap serves both values): floats 8..11 = (dLG rows 0+1, dLG rows 2+3,
+// dz rows 0+1, dz rows 2+3), and the depth gather finishes (r0 + r1) + (r2 + r3) -- the association the plain path has.
+template <int TW, bool DEPTH = false>  // TW tiles (= waves) per workgroup; the waves never synchronise
 __global__ __launch_bounds__(64 * TW, 1) void k_blend_backward_tile(
     const FrameParams fp, const uint2* __restrict__ ranges, const uint32_t* __restrict__ quad_last_in,
     const uint32_t* __restrict__ point_list, const float4* __restrict__ splats, const uint2* __restrict__ slotinfo,
     const float* __restrict__ bg, const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
     const float* __restrict__ dL_dpix, const float* __restrict__ dL_dacc, float* __restrict__ grad_inst,
     uint8_t* __restrict__ inst_flag, uint8_t* __restrict__ touched, const uint32_t* __restrict__ tile_order,
-    const uint2* __restrict__ rangesB) {
+    const uint2* __restrict__ rangesB, const float* __restrict__ dL_ddepth) {
   __shared__ float4 sE[TW][64][3];  // (x, y, A', B' | C', opacity, r, g | b, -, -, -) per staged entry
   __shared__ uint32_t sSlot[TW][64], sId[TW][64];
   // (wave-uniform values are made scalars by hand -- the compiler cannot know that a loaded value is the same in every
@@ -736,6 +760,7 @@ __global__ __launch_bounds__(64 * TW, 1) void k_blend_backward_tile(
 
   // per-pixel state, k = 0..3 (fully unrolled: registers)
   float pfy[4], T[4], S[4], dp0[4], dp1[4], dp2[4], dacc[4];
+  float ddep[4] = {0.f, 0.f, 0.f, 0.f};
   int lastc[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
@@ -749,6 +774,7 @@ __global__ __launch_bounds__(64 * TW, 1) void k_blend_backward_tile(
     dp1[k] = inside ? dL_dpix[N + pid] : 0.f;
     dp2[k] = inside ? dL_dpix[2 * N + pid] : 0.f;
     dacc[k] = inside ? dL_dacc[pid] : 0.f;  // the reference reads this unguarded (backward.cu:497)
+    if constexpr (DEPTH) ddep[k] = inside ? dL_ddepth[pid] : 0.f;
     // the one recurrence of k_blend_backward (see there): what lies behind the last contributor is the background
     S[k] = bg0 * dp0[k] + bg1 * dp1[k] + bg2 * dp2[k];
   }
@@ -781,7 +807,7 @@ __global__ __launch_bounds__(64 * TW, 1) void k_blend_backward_tile(
     constexpr float L2E = 1.4426950408889634f;
     sE[wq][lane][0] = make_float4(a.x, a.y, a.z * (-0.5f * L2E), a.w * (-L2E));
     sE[wq][lane][1] = make_float4(b.x * (-0.5f * L2E), b.y, b.z, b.w);
-    sE[wq][lane][2] = make_float4(c.x, 0.f, 0.f, 0.f);
+    sE[wq][lane][2] = make_float4(c.x, DEPTH ? c.y : 0.f, 0.f, 0.f);  // (blue, DEPTH: view-space depth z)
     sSlot[wq][lane] = eslot;
     sId[wq][lane] = eid;
     uint64_t m = __ballot(hit);
@@ -793,12 +819,15 @@ __global__ __launch_bounds__(64 * TW, 1) void k_blend_backward_tile(
       const float4 ea = sE[wq][jj][0];
       const float4 eb = sE[wq][jj][1];
       const float blue = sE[wq][jj][2].x;
+      float ez = 0.f;
+      if constexpr (DEPTH) ez = sE[wq][jj][2].y;
       const float dx = ea.x - pfx;
       const float dx2 = dx * dx;
       const float Adx2 = ea.z * dx2;
       // lane-local sums over the lane's four pixels: colour (3), dLG, dLG dy, dLG dy^2 (accumulated as fused
       // multiply-adds: combining the four pixels costs no instruction of its own)
       float c0 = 0.f, c1 = 0.f, c2 = 0.f, sG = 0.f, sGy = 0.f, sGyy = 0.f;
+      float sZ = 0.f;  // DEPTH: sum alpha T g_d
       uint64_t anym = 0ull;  // lanes one of whose four pixels takes the splat
 #pragma unroll
       for (int k = 0; k < 4; k++) {
@@ -816,8 +845,10 @@ __global__ __launch_bounds__(64 * TW, 1) void k_blend_backward_tile(
         if (ok) {
           const float rom = __builtin_amdgcn_rcpf(1.0f - araw);
           const float Tn = T[k] * rom;  // T / (1 - alpha)
+          float dacc_z = dacc[k];  // DEPTH: dL/dacc + z dL/ddepth (g_d = 0 leaves dacc as it is, bit for bit)
+          if constexpr (DEPTH) dacc_z = __builtin_fmaf(ez, ddep[k], dacc[k]);
           const float D =
-              __builtin_fmaf(eb.z, dp0[k], __builtin_fmaf(eb.w, dp1[k], __builtin_fmaf(blue, dp2[k], dacc[k]))) - S[k];
+              __builtin_fmaf(eb.z, dp0[k], __builtin_fmaf(eb.w, dp1[k], __builtin_fmaf(blue, dp2[k], dacc_z))) - S[k];
           const float dch = araw * Tn;
           const float dL_dalpha = Tn * D;
           const float dLG = Graw * dL_dalpha;  // dL/dG up to the opacity factor; also the opacity partial itself
@@ -825,6 +856,7 @@ __global__ __launch_bounds__(64 * TW, 1) void k_blend_backward_tile(
           c0 = __builtin_fmaf(dch, dp0[k], c0);
           c1 = __builtin_fmaf(dch, dp1[k], c1);
           c2 = __builtin_fmaf(dch, dp2[k], c2);
+          if constexpr (DEPTH) sZ = __builtin_fmaf(dch, ddep[k], sZ);
           sG += dLG;
           sGy += sy;
           sGyy = __builtin_fmaf(sy, dy, sGyy);
@@ -845,13 +877,18 @@ __global__ __launch_bounds__(64 * TW, 1) void k_blend_backward_tile(
         swap_add16(v1, v3);  // ... of v1, v3, v5, v7
         row_allsum3(v0, v1, g8);
         asm volatile("" : "+v"(v0), "+v"(v1), "+v"(g8));
+        if constexpr (DEPTH) {
+          float g9 = row_allsum(sZ);
+          swap_add16(g8, g9);  // rows 0, 2: dLG rows 0+1, 2+3; rows 1, 3: dz rows 0+1, 2+3
+        }
         const size_t slot = sSlot[wq][jj];
         // record = the RAW pixel sums: floats 0..7 = colour r g b | dLG dx, dLG dy | dLG dx^2, dLG dx dy, dLG dy^2 (row r
         // of the wave holds the wave totals of values 2r, 2r + 1), floats 8..11 = the four 16-lane-row sums of dLG
         // (k_gather_records adds them: two cross-row steps fewer here, once per instance)
         if ((lane & 15) == 0) {
           *reinterpret_cast<float2*>(rec_lane + slot * (GRAD_F4 * 4)) = make_float2(v0, v1);
-          grad_inst[slot * (GRAD_F4 * 4) + 8 + (lane >> 4)] = g8;
+          if constexpr (DEPTH) grad_inst[slot * (GRAD_F4 * 4) + 8 + (lane >> 5) + 2 * ((lane >> 4) & 1)] = g8;
+          else grad_inst[slot * (GRAD_F4 * 4) + 8 + (lane >> 4)] = g8;
         }
         if (lane == 63) {
           inst_flag[slot] = 1;
@@ -998,7 +1035,8 @@ hipError_t launch_tile_order(const FrameParams& fp, ImageState im, hipStream_t s
 }
 
 hipError_t launch_blend_backward(const FrameParams& fp, GeomState g, BinningState b, ImageState im, const float* bg,
-                                 const float* dL_dpix, const float* dL_dacc, bool have_tile_order, hipStream_t s) {
+                                 const float* dL_dpix, const float* dL_dacc, const float* dL_ddepth, bool have_tile_order,
+                                 hipStream_t s) {
   if (!have_tile_order) {
     const hipError_t e = launch_tile_order(fp, im, s);
     if (e != hipSuccess) return e;
@@ -1012,16 +1050,26 @@ hipError_t launch_blend_backward(const FrameParams& fp, GeomState g, BinningStat
   const int tiles = fp.gx * fp.gy;
   const bool per_quad = env().blend_backward_quads || (!env().blend_backward_tiles && tiles < 3072);
   const uint32_t* order = env().bwd_image_order ? nullptr : im.tile_order;
-  if (per_quad) {
+  constexpr int TW = 4;  // (1, 2 and 4 tiles per workgroup measured equal)
+  if (dL_ddepth) {  // gsr_backward_depth: the depth variants of the same two kernels, chosen by the same rule
+    if (per_quad)
+      hipLaunchKernelGGL((k_blend_backward<128, true>), dim3(tiles), dim3(256), 0, s, fp, im.ranges, im.quad_last,
+                         b.point_list, g.splats, g.slotinfo, bg, im.final_T, im.n_contrib, dL_dpix, dL_dacc, b.grad_inst,
+                         b.inst_flag, g.touched, order, im.rangesB, dL_ddepth);
+    else
+      hipLaunchKernelGGL((k_blend_backward_tile<TW, true>), dim3((tiles + TW - 1) / TW), dim3(64 * TW), 0, s, fp,
+                         im.ranges, im.quad_last, b.point_list, g.splats, g.slotinfo, bg, im.final_T, im.n_contrib, dL_dpix,
+                         dL_dacc, reinterpret_cast<float*>(b.grad_inst), b.inst_flag, g.touched, order, im.rangesB,
+                         dL_ddepth);
+  } else if (per_quad) {
     // chunks of 128 list entries (64 and 128 measured equal, 256 slower: LDS footprint)
     hipLaunchKernelGGL(k_blend_backward<128>, dim3(tiles), dim3(256), 0, s, fp, im.ranges, im.quad_last, b.point_list,
                        g.splats, g.slotinfo, bg, im.final_T, im.n_contrib, dL_dpix, dL_dacc, b.grad_inst, b.inst_flag,
-                       g.touched, order, im.rangesB);
+                       g.touched, order, im.rangesB, nullptr);
   } else {
-    constexpr int TW = 4;  // (1, 2 and 4 tiles per workgroup measured equal)
     hipLaunchKernelGGL(k_blend_backward_tile<TW>, dim3((tiles + TW - 1) / TW), dim3(64 * TW), 0, s, fp, im.ranges,
                        im.quad_last, b.point_list, g.splats, g.slotinfo, bg, im.final_T, im.n_contrib, dL_dpix, dL_dacc,
-                       reinterpret_cast<float*>(b.grad_inst), b.inst_flag, g.touched, order, im.rangesB);
+                       reinterpret_cast<float*>(b.grad_inst), b.inst_flag, g.touched, order, im.rangesB, nullptr);
   }
   return hipGetLastError();
 }

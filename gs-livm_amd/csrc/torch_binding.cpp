@@ -63,7 +63,15 @@ char* resize_blob(void* ctx, size_t bytes) {
   return reinterpret_cast<char*>(t->data_ptr());
 }
 
+thread_local bool t_depth_gradient = false;  // gsr_torch::set_depth_gradient
+
 }  // namespace
+
+bool gsr_torch::set_depth_gradient(bool on) {
+  const bool prev = t_depth_gradient;
+  t_depth_gradient = on;
+  return prev;
+}
 
 std::tuple<int, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor>
 RasterizeGaussiansCUDA(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& colors,
@@ -108,8 +116,10 @@ RasterizeGaussiansCUDA(const torch::Tensor& background, const torch::Tensor& mea
 // want_cov3D = false (the autograd node, when the covariance comes from scales and rotations): dL_dcov3D is an
 // intermediate nobody reads -- it is neither allocated nor written (24 of the 218 bytes per Gaussian the per-Gaussian
 // backward moves) and comes back undefined.  The public entry point always returns it, as the reference does.
+// dL_dout_depth defined: gsr_backward_depth instead of gsr_backward, and dL_ddepths [P] comes back as the ninth tensor
+// (undefined otherwise).
 static std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
-                  torch::Tensor>
+                  torch::Tensor, torch::Tensor>
 rasterize_backward_impl(const torch::Tensor& background, const torch::Tensor& means3D, const torch::Tensor& radii,
                         const torch::Tensor& colors, const torch::Tensor& scales, const torch::Tensor& rotations,
                         const float scale_modifier, const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
@@ -117,7 +127,7 @@ rasterize_backward_impl(const torch::Tensor& background, const torch::Tensor& me
                         const torch::Tensor& dL_dout_color, const torch::Tensor& dL_dout_acc, const torch::Tensor& sh,
                         const int degree, const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
                         const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const bool debug,
-                        const bool want_cov3D) {
+                        const bool want_cov3D, const torch::Tensor& dL_dout_depth = torch::Tensor()) {
   const int P = means3D.size(0);
   const int H = dL_dout_color.size(1);
   const int W = dL_dout_color.size(2);
@@ -134,11 +144,32 @@ rasterize_backward_impl(const torch::Tensor& background, const torch::Tensor& me
   torch::Tensor dL_dsh = mk({P, M, 3});
   torch::Tensor dL_dscales = mk({P, 3});
   torch::Tensor dL_drotations = mk({P, 4});
+  const bool with_depth = dL_dout_depth.defined();
+  torch::Tensor dL_ddepths = with_depth ? mk({P}) : torch::Tensor();
+  if (with_depth && dL_dout_depth.numel() != static_cast<int64_t>(H) * W) {
+    AT_ERROR("dL_dout_depth must have H*W elements");
+  }
   if (P != 0) {
     auto bg = background.contiguous(), m3 = means3D.contiguous(), shc = sh.contiguous(), col = colors.contiguous(),
          sc = scales.contiguous(), rot = rotations.contiguous(), cov = cov3D_precomp.contiguous(),
          view = viewmatrix.contiguous(), proj = projmatrix.contiguous(), cam = campos.contiguous(),
          dpix = dL_dout_color.contiguous(), dacc = dL_dout_acc.contiguous(), rad = radii.contiguous();
+    if (with_depth) {
+      auto ddep = dL_dout_depth.contiguous();
+      check(gsr_backward_depth(P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc), scale_modifier,
+                               fptr(rot), fptr(cov), fptr(view), fptr(proj), fptr(cam), tan_fovx, tan_fovy,
+                               rad.data_ptr<int>(), reinterpret_cast<char*>(geomBuffer.data_ptr()),
+                               reinterpret_cast<char*>(binningBuffer.data_ptr()),
+                               reinterpret_cast<char*>(imageBuffer.data_ptr()), fptr(dpix), fptr(dacc), fptr(ddep),
+                               dL_dmeans2D.data_ptr<float>(), dL_dconic.data_ptr<float>(),
+                               dL_dopacity.data_ptr<float>(), dL_dcolors.data_ptr<float>(),
+                               dL_dmeans3D.data_ptr<float>(),
+                               dL_dcov3D.defined() ? dL_dcov3D.data_ptr<float>() : nullptr,
+                               M ? dL_dsh.data_ptr<float>() : nullptr, dL_dscales.data_ptr<float>(),
+                               dL_drotations.data_ptr<float>(), dL_ddepths.data_ptr<float>(), debug ? 1 : 0,
+                               current_stream()),
+            "gsr_backward_depth");
+    } else
     check(gsr_backward(P, degree, M, R, fptr(bg), W, H, fptr(m3), fptr(shc), fptr(col), fptr(sc), scale_modifier,
                        fptr(rot), fptr(cov), fptr(view), fptr(proj), fptr(cam), tan_fovx, tan_fovy,
                        rad.data_ptr<int>(), reinterpret_cast<char*>(geomBuffer.data_ptr()),
@@ -152,7 +183,7 @@ rasterize_backward_impl(const torch::Tensor& background, const torch::Tensor& me
           "gsr_backward");
   }
   return std::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
-                         dL_drotations);
+                         dL_drotations, dL_ddepths);
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
@@ -165,9 +196,30 @@ RasterizeGaussiansBackwardCUDA(const torch::Tensor& background, const torch::Ten
                                const torch::Tensor& dL_dout_acc, const torch::Tensor& sh, const int degree,
                                const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
                                const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const bool debug) {
+  auto [g0, g1, g2, g3, g4, g5, g6, g7, unused] =
+      rasterize_backward_impl(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                              viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_acc, sh, degree, campos,
+                              geomBuffer, R, binningBuffer, imageBuffer, debug, /*want_cov3D=*/true);
+  (void)unused;
+  return std::make_tuple(g0, g1, g2, g3, g4, g5, g6, g7);
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor, torch::Tensor>
+RasterizeGaussiansBackwardDepthCUDA(const torch::Tensor& background, const torch::Tensor& means3D,
+                                    const torch::Tensor& radii, const torch::Tensor& colors, const torch::Tensor& scales,
+                                    const torch::Tensor& rotations, const float scale_modifier,
+                                    const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
+                                    const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+                                    const torch::Tensor& dL_dout_color, const torch::Tensor& dL_dout_acc,
+                                    const torch::Tensor& dL_dout_depth, const torch::Tensor& sh, const int degree,
+                                    const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
+                                    const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
+                                    const bool debug) {
+  if (!dL_dout_depth.defined()) AT_ERROR("dL_dout_depth must be defined");
   return rasterize_backward_impl(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_acc, sh, degree, campos,
-                                 geomBuffer, R, binningBuffer, imageBuffer, debug, /*want_cov3D=*/true);
+                                 geomBuffer, R, binningBuffer, imageBuffer, debug, /*want_cov3D=*/true, dL_dout_depth);
 }
 
 torch::Tensor markVisible(torch::Tensor& means3D, torch::Tensor& viewmatrix, torch::Tensor& projmatrix) {
@@ -217,6 +269,7 @@ torch::autograd::tensor_list _RasterizeGaussians::forward(
   ctx->saved_data["sh_degree"] = sh_degree_val;
   ctx->saved_data["camera_center"] = camera_center;
   ctx->saved_data["prefiltered"] = prefiltered_val;
+  ctx->saved_data["depth_gradient"] = t_depth_gradient;  // gsr_torch::set_depth_gradient, as it stands at forward time
   ctx->mark_non_differentiable({radii});
   ctx->set_materialize_grads(false);  // no zero images for the outputs nobody differentiates (depth)
   return {color, radii, out_depth, out_acc};
@@ -225,8 +278,10 @@ torch::autograd::tensor_list _RasterizeGaussians::forward(
 torch::autograd::tensor_list _RasterizeGaussians::backward(torch::autograd::AutogradContext* ctx,
                                                            torch::autograd::tensor_list grad_outputs) {
   auto grad_out_color = grad_outputs[0];
-  // grad_outputs[1] (radii) and [2] (depth) are ignored, exactly as the reference (rasterizer.cu:78-79)
+  // grad_outputs[1] (radii) and [2] (depth) are ignored, exactly as the reference (rasterizer.cu:78-79) -- the depth
+  // gradient unless the forward ran under gsr_torch::set_depth_gradient(true) and one arrives
   auto grad_acc = grad_outputs[3];
+  const torch::Tensor grad_depth = ctx->saved_data["depth_gradient"].toBool() ? grad_outputs[2] : torch::Tensor();
   const int num_rendered = ctx->saved_data["num_rendered"].to<int>();
   auto saved = ctx->get_saved_variables();
   auto colors_precomp = saved[0], means3D = saved[1], scales = saved[2], rotations = saved[3],
@@ -236,14 +291,16 @@ torch::autograd::tensor_list _RasterizeGaussians::backward(torch::autograd::Auto
   if (!grad_out_color.defined()) grad_out_color = torch::zeros({3, H, W}, means3D.options());
   if (!grad_acc.defined()) grad_acc = torch::zeros({1, H, W}, means3D.options());
   auto [grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_scales,
-        grad_rotations] =
+        grad_rotations, grad_depths] =
       rasterize_backward_impl(
           ctx->saved_data["background"].to<torch::Tensor>(), means3D, radii, colors_precomp, scales, rotations,
           ctx->saved_data["scale_modifier"].to<double>(), cov3Ds_precomp,
           ctx->saved_data["viewmatrix"].to<torch::Tensor>(), ctx->saved_data["projmatrix"].to<torch::Tensor>(),
           ctx->saved_data["tanfovx"].to<double>(), ctx->saved_data["tanfovy"].to<double>(), grad_out_color, grad_acc,
           sh, ctx->saved_data["sh_degree"].to<int>(), ctx->saved_data["camera_center"].to<torch::Tensor>(),
-          geomBuffer, num_rendered, binningBuffer, imgBuffer, false, /*want_cov3D=*/cov3Ds_precomp.numel() != 0);
+          geomBuffer, num_rendered, binningBuffer, imgBuffer, false, /*want_cov3D=*/cov3Ds_precomp.numel() != 0,
+          grad_depth);
+  (void)grad_depths;  // dL/d view-space depth: already carried into grad_means3D
   auto opt = [](const torch::Tensor& g, const torch::Tensor& x) { return x.numel() ? g : torch::Tensor(); };
   return {grad_means3D,
           grad_means2D,
@@ -318,6 +375,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "C++/LibTorch operator surface of gs_livm_amd (mirror of GS-LIVM's src/gs/rasterizer.cu)";
   m.def("RasterizeGaussiansCUDA", &RasterizeGaussiansCUDA);
   m.def("RasterizeGaussiansBackwardCUDA", &RasterizeGaussiansBackwardCUDA);
+  m.def("RasterizeGaussiansBackwardDepthCUDA", &RasterizeGaussiansBackwardDepthCUDA);
+  m.def("set_depth_gradient", &gsr_torch::set_depth_gradient, py::arg("on"));
   m.def("markVisible", [](torch::Tensor a, torch::Tensor b, torch::Tensor c) { return markVisible(a, b, c); });
   // exact instance count of this thread's last forward (RasterizeGaussiansCUDA's first element is the binning key:
   // the capacity the binning blob was carved for -- equal to the count after a synchronous forward)

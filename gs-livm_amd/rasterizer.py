@@ -22,6 +22,8 @@ class GaussianRasterizationSettings(NamedTuple):
     sh_degree: int
     camera_center: torch.Tensor
     prefiltered: bool = False
+    # extension (the reference has no such field): let the gradient of the depth output reach the Gaussians
+    depth_gradient: bool = False
 
 
 def _empty(device):
@@ -49,8 +51,10 @@ class _RasterizeGaussians(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_color, _grad_radii, _grad_depth, grad_acc):
-        # the depth gradient is ignored, exactly as in the reference (rasterizer.cu:78-79, 117-118)
+        # the depth gradient is ignored, exactly as in the reference (rasterizer.cu:78-79, 117-118), unless the settings
+        # ask for it (depth_gradient) AND one arrives: a loss that does not use the depth output takes the plain path
         s = ctx.settings
+        grad_depth = _grad_depth if s.depth_gradient else None
         colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geom, binning, img = ctx.saved_tensors
         if grad_color is None:
             grad_color = torch.zeros((3, s.image_height, s.image_width), device=means3D.device)
@@ -61,7 +65,7 @@ class _RasterizeGaussians(torch.autograd.Function):
             rotations.contiguous(), s.scale_modifier, cov3Ds_precomp.contiguous(), s.viewmatrix.contiguous(),
             s.projmatrix.contiguous(), s.tanfovx, s.tanfovy, grad_color, grad_acc, sh.contiguous(), s.sh_degree,
             s.camera_center.contiguous(), geom, ctx.num_rendered, binning, img, False,
-            want_cov3D=cov3Ds_precomp.numel() != 0)
+            want_cov3D=cov3Ds_precomp.numel() != 0, grad_depth=grad_depth)[:8]
         none_if_empty = lambda g, x: g if x.numel() else None  # noqa: E731
         return (g_means3D, g_means2D, none_if_empty(g_sh, sh), none_if_empty(g_colors, colors_precomp), g_opac,
                 none_if_empty(g_scales, scales), none_if_empty(g_rot, rotations),

@@ -57,8 +57,10 @@ class Camera:
     def Get_camera_center(self): return self._camera_center
 
 
-def render(viewpoint_camera, gaussian_model, bg_color, scaling_modifier=1.0, override_color=None):
-    """-> (color [3,H,W], depth [1,H,W], depth_acc [1,H,W]); render_utils.cuh:13-56."""
+def render(viewpoint_camera, gaussian_model, bg_color, scaling_modifier=1.0, override_color=None, depth_gradient=False):
+    """-> (color [3,H,W], depth [1,H,W], depth_acc [1,H,W]); render_utils.cuh:13-56.
+    depth_gradient=True (an extension): a loss on `depth` trains the Gaussians; by default its gradient stops at the
+    rasterizer, as in the reference."""
     cam = viewpoint_camera
     dev = gaussian_model.Get_xyz().device
     settings = GaussianRasterizationSettings(
@@ -66,7 +68,8 @@ def render(viewpoint_camera, gaussian_model, bg_color, scaling_modifier=1.0, ove
         tanfovx=math.tan(cam.Get_FoVx() * 0.5), tanfovy=math.tan(cam.Get_FoVy() * 0.5),
         bg=bg_color.to(dev), scale_modifier=float(scaling_modifier),
         viewmatrix=cam.Get_world_view_transform(), projmatrix=cam.Get_full_proj_transform(),
-        sh_degree=int(gaussian_model.Get_max_sh_degree()), camera_center=cam.Get_camera_center(), prefiltered=False)
+        sh_degree=int(gaussian_model.Get_max_sh_degree()), camera_center=cam.Get_camera_center(), prefiltered=False,
+        depth_gradient=bool(depth_gradient))
     rasterizer = GaussianRasterizer(settings)
     if hasattr(gaussian_model, "activated"):  # one fused launch for all five getters
         means3D, opacity, scales, rotations, shs = gaussian_model.activated()

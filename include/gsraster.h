@@ -201,6 +201,25 @@ int gsr_backward(int P, int D, int M, int R, const float* background, int width,
                  float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale, float* dL_drot, int debug,
                  void* stream);
 
+/* gsr_backward with a gradient w.r.t. the rendered depth (out_depth = sum_i z_i alpha_i T_i, z the view-space depth):
+ * an extension, the reference has no such path.  Same arguments, same validation and same nine outputs as
+ * gsr_backward, plus
+ *   dL_ddepth  [H][W]  in:  dL/d out_depth,
+ *   dL_ddepths [P]     out: dL/dz_i = sum over the pixels that take the Gaussian of alpha T dL_ddepth; an intermediate
+ *                           like dL_dconic, fully overwritten (0 for radii <= 0 and for Gaussians no pixel took).
+ * dL_ddepth reaches alpha (z_i dL_ddepth joins colour . dL_dpix + dL_dacc of every splat) and, through dL_ddepths and the
+ * third row of the view matrix, dL_dmean3D.  A null dL_ddepth or dL_ddepths is GSR_ERR_INVALID_ARGUMENT (nothing is
+ * launched or written).  With dL_ddepth all zero the nine outputs are bit-equal to gsr_backward's.  Either entry point
+ * leaves the blobs ready for the other. */
+int gsr_backward_depth(int P, int D, int M, int R, const float* background, int width, int height,
+                       const float* means3D, const float* shs, const float* colors_precomp, const float* scales,
+                       float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                       const float* viewmatrix, const float* projmatrix, const float* campos, float tan_fovx,
+                       float tan_fovy, const int* radii, char* geom_buffer, char* binning_buffer, char* image_buffer,
+                       const float* dL_dpix, const float* dL_dacc, const float* dL_ddepth, float* dL_dmean2D,
+                       float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
+                       float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_ddepths, int debug, void* stream);
+
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:21,
  * rasterizer_impl.cu:128-135): present[i] = z_view > 0.2 (1-byte bool). */
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
