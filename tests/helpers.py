@@ -209,11 +209,13 @@ REF64_SCENES = [(300, 70, 50, 11, 3), (1, 64, 64, 2, 0), (7, 33, 17, 3, 1), (250
 REF64_PATHS = ("colors_precomp", "cov3D_precomp", "scale_modifier", "opaque", "jacobian_clamp", "sh_clamp")
 
 
-def ref64_path_scene(kind):
-    """(scene, seed) of one path of REF64_PATHS."""
+def ref64_path_scene(kind, base=None):
+    """(scene, seed) of one path of REF64_PATHS.  base(P, W, H, seed, D) builds the scene the path is laid over
+    (default: S.make_scene; tests/intrinsics.py passes one with fx != fy)."""
     seed = {"colors_precomp": 13, "cov3D_precomp": 13, "scale_modifier": 14, "opaque": 15, "jacobian_clamp": 17,
             "sh_clamp": 18}[kind]
-    sc = S.make_scene(1500, 200, 120, seed, sh_degree=3 if kind == "sh_clamp" else 1)
+    D = 3 if kind == "sh_clamp" else 1
+    sc = S.make_scene(1500, 200, 120, seed, sh_degree=D) if base is None else base(1500, 200, 120, seed, D)
     rng = np.random.default_rng(seed)
     if kind == "colors_precomp":
         sc["colors_precomp"] = rng.uniform(0, 1, (1500, 3)).astype(np.float32)
