@@ -201,6 +201,15 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _rot16(t):
+    """`rotations` is the one caller tensor the library reads with 16-byte loads whatever its address
+    (include/gsraster.h): a misaligned one -- a view into a larger buffer -- is handed over as an aligned copy."""
+    if t is not None and t.numel() and t.data_ptr() & 15:
+        t = t.clone(memory_format=torch.contiguous_format)
+        assert t.data_ptr() & 15 == 0
+    return t
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -237,6 +246,7 @@ def rasterize_forward(background, means3D, colors, opacity, scales, rotations, s
     radii = torch.empty((P,), dtype=torch.int32, device=dev)  # the library writes every entry
     gb, bb, ib = _Blob(dev), _Blob(dev), _Blob(dev)
     M = int(sh.size(1)) if (sh is not None and sh.numel() != 0) else 0
+    rotations = _rot16(rotations)
     L = lib()
     R = _check(L.gsr_forward(gb.fn, None, bb.fn, None, ib.fn, None, P, int(degree), M, _ptr(background), W, H,
                              _ptr(means3D), _ptr(sh), _ptr(colors), _ptr(opacity), _ptr(scales),
@@ -276,6 +286,7 @@ def rasterize_backward(background, means3D, radii, colors, scales, rotations, sc
     dL_dscales = mk((P, 3), **f32)
     dL_drotations = mk((P, 4), **f32)
     dL_ddepths = mk((P,), **f32) if grad_depth is not None else None
+    rotations = _rot16(rotations)
     if P != 0 and grad_depth is not None:
         dpix = dL_dout_color.contiguous()
         dacc = dL_dout_acc.contiguous()

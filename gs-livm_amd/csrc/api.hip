@@ -1212,6 +1212,14 @@ static int redo_frame(const Forward& f, FrameResult* r) {
   return GSR_OK;
 }
 
+// Caller tensors need the alignment of their element only (include/gsraster.h) -- except `rotations`, which the
+// per-Gaussian kernels read as one float4 per Gaussian, unconditionally (k_preprocess's fetch(), gaussian_backward_one):
+// a misaligned one is refused here, before anything is enqueued, rather than put behind a run-time branch there.
+static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
+static int fail_rotations(const void* p) {
+  return fail(GSR_ERR_INVALID_ARGUMENT, "rotations (%p) must be 16-byte aligned: it is read as one float4 per Gaussian", p);
+}
+
 int gsr_forward(gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn binning_alloc, void* binning_ctx,
                 gsr_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background, int width,
                 int height, const float* means3D, const float* shs, const float* colors_precomp,
@@ -1242,6 +1250,7 @@ int gsr_forward(gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn bi
     return fail(GSR_ERR_INVALID_ARGUMENT, "provide scales+rotations or a precomputed 3D covariance");
   if (!colors_precomp && (D < 0 || D > 3 || M < (D + 1) * (D + 1) || M > 16))
     return fail(GSR_ERR_UNSUPPORTED, "SH degree %d with %d coefficients is not supported (D<=3, (D+1)^2<=M<=16)", D, M);
+  if (!cov3D_precomp && misaligned16(rotations)) return fail_rotations(rotations);
   if (width > 1023 * TILE || height > 1023 * TILE) return fail(GSR_ERR_UNSUPPORTED, "image larger than 16368 px");
   if (P >= (1 << 30)) return fail(GSR_ERR_UNSUPPORTED, "2^30 or more Gaussians");
   if (!(tan_fovx > 0.f) || !(tan_fovy > 0.f)) return fail(GSR_ERR_INVALID_ARGUMENT, "tan_fov must be > 0");
@@ -1430,6 +1439,13 @@ static int backward_impl(bool with_depth, int P, int D, int M, int R, const floa
     return fail(GSR_ERR_INVALID_ARGUMENT, "null gradient output");
   if (with_depth && !dL_ddepth) return fail(GSR_ERR_INVALID_ARGUMENT, "null dL_ddepth");
   if (with_depth && !dL_ddepths) return fail(GSR_ERR_INVALID_ARGUMENT, "null dL_ddepths");
+  // the forward's rules: the kernel dereferences `rotations` under `if (scales)`, reads it as float4, and stores
+  // gradient rows of (D + 1)^2 coefficients into rows of M
+  if (!cov3D_precomp && (!scales || !rotations))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "provide scales+rotations or a precomputed 3D covariance");
+  if (!colors_precomp && (D < 0 || D > 3 || M < (D + 1) * (D + 1) || M > 16))
+    return fail(GSR_ERR_UNSUPPORTED, "SH degree %d with %d coefficients is not supported (D<=3, (D+1)^2<=M<=16)", D, M);
+  if (!cov3D_precomp && misaligned16(rotations)) return fail_rotations(rotations);
   if (env().host_trace)
     fprintf(stderr, "[gsr] backward entered at %.1f us (process clock)\n",
             std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count());

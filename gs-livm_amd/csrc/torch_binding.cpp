@@ -23,6 +23,7 @@
 
 #include <c10/hip/HIPStream.h>
 
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -63,6 +64,13 @@ char* resize_blob(void* ctx, size_t bytes) {
   return reinterpret_cast<char*>(t->data_ptr());
 }
 
+// `rotations` is the one caller tensor the library reads with 16-byte loads whatever its address (include/gsraster.h):
+// a misaligned one -- a view into a larger buffer -- is handed over as an aligned copy.
+torch::Tensor aligned16(const torch::Tensor& t) {
+  if (t.defined() && t.numel() != 0 && (reinterpret_cast<uintptr_t>(t.data_ptr()) & 15u) != 0) return t.clone();
+  return t;
+}
+
 thread_local bool t_depth_gradient = false;  // gsr_torch::set_depth_gradient
 
 }  // namespace
@@ -101,7 +109,7 @@ RasterizeGaussiansCUDA(const torch::Tensor& background, const torch::Tensor& mea
   int M = 0;
   if (sh.defined() && sh.numel() != 0) M = sh.size(1);
   auto bg = background.contiguous(), m3 = means3D.contiguous(), shc = sh.contiguous(), col = colors.contiguous(),
-       op = opacity.contiguous(), sc = scales.contiguous(), rot = rotations.contiguous(),
+       op = opacity.contiguous(), sc = scales.contiguous(), rot = aligned16(rotations.contiguous()),
        cov = cov3D_precomp.contiguous(), view = viewmatrix.contiguous(), proj = projmatrix.contiguous(),
        cam = campos.contiguous();
   const int rendered = gsr_forward(
@@ -151,7 +159,7 @@ rasterize_backward_impl(const torch::Tensor& background, const torch::Tensor& me
   }
   if (P != 0) {
     auto bg = background.contiguous(), m3 = means3D.contiguous(), shc = sh.contiguous(), col = colors.contiguous(),
-         sc = scales.contiguous(), rot = rotations.contiguous(), cov = cov3D_precomp.contiguous(),
+         sc = scales.contiguous(), rot = aligned16(rotations.contiguous()), cov = cov3D_precomp.contiguous(),
          view = viewmatrix.contiguous(), proj = projmatrix.contiguous(), cam = campos.contiguous(),
          dpix = dL_dout_color.contiguous(), dacc = dL_dout_acc.contiguous(), rad = radii.contiguous();
     if (with_depth) {

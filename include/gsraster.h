@@ -43,6 +43,15 @@ typedef enum gsr_status {
  * stays valid until the matching gsr_backward has completed on the stream. */
 typedef char* (*gsr_alloc_fn)(void* ctx, size_t bytes);
 
+/* Alignment of caller tensors (every input and output array of gsr_forward, gsr_backward and gsr_backward_depth):
+ * they are contiguous and need only the alignment of their element, 4 bytes -- the library takes its 16-byte copy
+ * branches only where the pointer it is handed allows them.  ONE EXCEPTION: `rotations` is read as one 16-byte
+ * quaternion per Gaussian and must be 16-byte aligned whenever it is read (no cov3D_precomp).  A misaligned
+ * `rotations` is refused with GSR_ERR_INVALID_ARGUMENT before anything is enqueued; the Python and LibTorch hosts
+ * pass an aligned copy instead, so their operator surfaces accept any contiguous tensor.
+ * The active SH degree D may be below the allocated one: every pair 0 <= D <= 3, (D+1)^2 <= M <= 16 is legal, the
+ * coefficients beyond (D+1)^2 are not read and their gradient rows are written as zeros. */
+
 /* Replaces CudaRasterizer::Rasterizer::forward (rasterizer.h:23-51,
  * src/cuda_rasterizer/rasterizer_impl.cu:181-342).
  *   P Gaussians, D = SH degree (0..3), M = SH coefficients per Gaussian (shs is [P][M][3]).
