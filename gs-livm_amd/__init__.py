@@ -5,7 +5,8 @@ Layout (only what the hot path needs):
   _capi.py         ctypes binding of the C ABI (mirrors src/gs/rasterize_points.cu)
   rasterizer.py    host-side mirror of the reference operator surface (src/gs/rasterizer.cu)
   render_utils.py  Camera (rasterizer-facing part) and render() as in include/gs/gs/render_utils.cuh
-  loss.py          fused L1 + SSIM photometric loss (SURVEY.md 8(f) "next" row 2); fused LiDAR similarity loss
+  loss.py          fused L1 + SSIM photometric loss (SURVEY.md 8(f) "next" row 2); fused LiDAR similarity loss; fused
+                   delta-depth loss between keyframe pairs
   model.py         fused activations + Adam for the caller's leaf tensors (SURVEY.md 8(f) "next" row 1)
   synthetic.py     synthetic scenes of SURVEY.md section 8(d) for tests and bench
   multiview.py     view-parallel sharding + the two RCCL exchange steps
@@ -17,7 +18,8 @@ from . import multiview, synthetic  # noqa: F401
 from ._capi import (GsrError, LIB_PATH, NumRendered, emit_guard_trips, last_num_rendered, lib, mailbox_slow_path_last, mark_visible,
                     set_binning_capacity_hint, speculation_stats, set_near_far, set_near_far_thread, set_reference_rects_thread, async_outcomes_pending, set_near_far_hints, last_near_far, set_far_speculation, last_far_skipped, profile_enable, profile_read,  # noqa: F401
                     rasterize_backward, rasterize_forward, reference_rects, set_reference_rects, state_views)
-from .loss import PhotometricLoss, SimilarityLoss, photometric_loss, reference_window_1d, similarity_loss  # noqa: F401
+from .loss import (DeltaDepthLoss, PhotometricLoss, SimilarityLoss, delta_depth_loss, delta_pose, photometric_loss,  # noqa: F401
+                   reference_window_1d, similarity_loss)
 from .model import FusedActivations, FusedAdam, GaussianParameters, GrowableAdam, GrowableGaussians, VoxelIndex  # noqa: F401
 from . import ply  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer,  # noqa: F401
@@ -42,5 +44,5 @@ def torch_ops():
     return mod
 
 
-__all__ = ["SimilarityLoss", "similarity_loss", "VoxelIndex", "PhotometricLoss", "photometric_loss", "reference_window_1d", "FusedActivations", "FusedAdam", "GaussianParameters", "GrowableAdam", "GrowableGaussians", "ply", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "Camera", "render", "get_projection_matrix", "rasterize_forward",
+__all__ = ["DeltaDepthLoss", "delta_depth_loss", "delta_pose", "SimilarityLoss", "similarity_loss", "VoxelIndex", "PhotometricLoss", "photometric_loss", "reference_window_1d", "FusedActivations", "FusedAdam", "GaussianParameters", "GrowableAdam", "GrowableGaussians", "ply", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "Camera", "render", "get_projection_matrix", "rasterize_forward",
            "rasterize_backward", "mark_visible", "state_views", "set_reference_rects", "reference_rects", "last_num_rendered", "set_binning_capacity_hint", "speculation_stats", "emit_guard_trips", "mailbox_slow_path_last", "set_near_far", "set_near_far_thread", "set_reference_rects_thread", "async_outcomes_pending", "set_near_far_hints", "last_near_far", "set_far_speculation", "last_far_skipped", "NumRendered", "lib", "torch_ops", "synthetic", "multiview", "GsrError", "LIB_PATH"]

@@ -66,7 +66,8 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_last_far_skipped", "gsr_far_skips", "gsr_far_skip_misses", "gsr_async_far_frames",
            "gsr_near_budget_scale", "gsr_near_budget_feedback", "gsr_near_far_pause", "gsr_set_near_far_thread",
            "gsr_set_reference_rects_thread", "gsr_async_outcomes_pending", "gsr_async_outcomes_lost",
-           "gsr_frame_note_misses", "gsr_similarity_loss", "gsr_similarity_loss_workspace")
+           "gsr_frame_note_misses", "gsr_similarity_loss", "gsr_similarity_loss_workspace",
+           "gsr_delta_depth_loss", "gsr_delta_depth_loss_workspace")
 
 
 def lib():
@@ -166,6 +167,11 @@ def lib():
     L.gsr_similarity_loss_workspace.argtypes = [ci, ci]
     L.gsr_similarity_loss.restype = ci
     L.gsr_similarity_loss.argtypes = [ci, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp, ci, vp, sz, vp]
+    L.gsr_delta_depth_loss_workspace.restype = sz
+    L.gsr_delta_depth_loss_workspace.argtypes = [ci, ci]
+    L.gsr_delta_depth_loss.restype = ci
+    L.gsr_delta_depth_loss.argtypes = [ci, ci, vp, vp, vp, vp, C.POINTER(cf), C.POINTER(cf), C.POINTER(cf), cf, vp, vp,
+                                       vp, vp, vp, sz, vp]
     L.gsr_init_gaussians.restype = ci
     L.gsr_init_gaussians.argtypes = [ci, ci, vp, vp, vp, cf] + [vp] * 6 + [vp]
     L.gsr_ply_row_floats.restype = sz
@@ -582,6 +588,36 @@ def similarity_loss(points, sel, xyz, scaling, lambda_, grad_xyz=None, grad_scal
                                      _ptr(out3), _ptr(grad_xyz), _ptr(grad_scaling), int(bool(accumulate)), _ptr(ws),
                                      nbytes, _stream()))
     return out3
+
+
+def _host_floats(m, n):
+    """n floats of a small host matrix (tensor, array or nested list) as a ctypes array, row-major."""
+    t = torch.as_tensor(m, dtype=torch.float64).reshape(-1)
+    assert t.numel() == n, "expected %d elements" % n
+    return (C.c_float * n)(*[float(x) for x in t.tolist()])
+
+
+def delta_depth_loss(depth_src, acc_src, depth_ref, acc_ref, inv_K_src, K_ref, T_rel, lambda_, want_warped=False,
+                     want_grad_src=True, want_grad_ref=True):
+    """The delta-depth term of a keyframe pair in four launches (include/gsraster.h, gsr_delta_depth_loss).
+    depth_* / acc_*: [H,W] or [1,H,W] f32 on the device; inv_K_src, K_ref (3x3) and T_rel (3x4 or 4x4, loss.delta_pose)
+    on the host.  Returns (out3 = [loss, mean gap, share of unmasked pixels] device tensor, warped or None,
+    dL/ddepth_src or None, dL/ddepth_ref or None), the images shaped like depth_src."""
+    H, W = int(depth_src.shape[-2]), int(depth_src.shape[-1])
+    for t in (depth_src, acc_src, depth_ref, acc_ref):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == H * W
+    T = torch.as_tensor(T_rel, dtype=torch.float64).reshape(-1, 4)[:3]
+    kin, kref, trel = _host_floats(inv_K_src, 9), _host_floats(K_ref, 9), _host_floats(T, 12)
+    nbytes = int(lib().gsr_delta_depth_loss_workspace(H, W))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=depth_src.device)
+    out3 = torch.empty(3, dtype=torch.float32, device=depth_src.device)
+    warped = torch.empty_like(depth_src) if want_warped else None
+    gs = torch.empty_like(depth_src) if want_grad_src else None
+    gr = torch.empty_like(depth_ref) if want_grad_ref else None
+    _check(lib().gsr_delta_depth_loss(H, W, _ptr(depth_src), _ptr(acc_src), _ptr(depth_ref), _ptr(acc_ref), kin, kref,
+                                      trel, float(lambda_), _ptr(out3), _ptr(warped), _ptr(gs), _ptr(gr), _ptr(ws),
+                                      nbytes, _stream()))
+    return out3, warped, gs, gr
 
 
 # ---- "next" row 4: map growth and PLY export (include/gsraster.h; csrc/growth.hip) ----

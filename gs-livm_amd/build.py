@@ -33,6 +33,7 @@ UNITS = {
     "loss.hip": ["-fno-slp-vectorize"],  # (packing the 11-tap sums costs more moves than it saves: 944 -> 732 VALU in the backward)
     "growth.hip": [],
     "simi.hip": [],
+    "delta.hip": [],
     "api.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "gsr_internal.hpp"), os.path.join(CSRC, "sort_core.hpp"),

@@ -129,7 +129,8 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_blend_backward", "k_compact_touched", "k_gather_records", "k_gaussian_backward", "k_mark_visible", "k_sort_hist[depth]",
     "k_sort_scan_chunks[depth]", "k_sort_scan_top[depth]", "k_sort_scatter[depth]", "k_activate",
     "k_activate_backward", "k_adam", "k_loss_forward", "k_loss_finalize", "k_loss_backward", "k_init_gaussians", "k_pack_ply_rows", "k_model_step", "k_tile_order", "k_live_sat", "k_compact_near",
-    "k_simi_nearest", "k_simi_points", "k_simi_grads"};
+    "k_simi_nearest", "k_simi_points", "k_simi_grads",
+    "k_delta_project", "k_delta_sample", "k_delta_scatter", "k_delta_convert"};
 
 extern "C" {
 
@@ -1597,6 +1598,30 @@ int gsr_similarity_loss(int P, int m, int n, const float* points, const int* sel
   }
   HIP_TRY(launch_similarity_loss(P, m, n, points, sel, xyz, scaling, lambda, out3, grad_xyz, grad_scaling,
                                  accumulate ? 1 : 0, workspace, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+size_t gsr_delta_depth_loss_workspace(int height, int width) {
+  if (height < 2 || width < 2 || (unsigned long long)height * (unsigned long long)width >= 0x80000000ull) return 0;
+  return delta_workspace_bytes(height, width);
+}
+
+int gsr_delta_depth_loss(int height, int width, const float* depth_src, const float* acc_src, const float* depth_ref,
+                         const float* acc_ref, const float* inv_K_src9, const float* K_ref9, const float* T_rel12,
+                         float lambda, float* out3, float* warped, float* dL_ddepth_src, float* dL_ddepth_ref,
+                         char* workspace, size_t workspace_bytes, void* stream_) {
+  g_err[0] = 0;
+  if (height < 2 || width < 2)  // (the reference divides by W - 1 and H - 1)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape: at least 2 x 2");
+  if ((unsigned long long)height * (unsigned long long)width >= 0x80000000ull)  // (32-bit pixel indices)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  if (!depth_src || !acc_src || !depth_ref || !acc_ref || !inv_K_src9 || !K_ref9 || !T_rel12 || !out3 || !workspace)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (workspace_bytes < delta_workspace_bytes(height, width))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes", delta_workspace_bytes(height, width));
+  HIP_TRY(launch_delta_depth_loss(height, width, depth_src, acc_src, depth_ref, acc_ref, inv_K_src9, K_ref9, T_rel12,
+                                  lambda, out3, warped, dL_ddepth_src, dL_ddepth_ref, workspace,
+                                  (hipStream_t)stream_));
   return GSR_OK;
 }
 

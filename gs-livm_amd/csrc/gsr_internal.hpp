@@ -439,6 +439,13 @@ size_t simi_workspace_bytes(int m, int n);
 hipError_t launch_similarity_loss(int P, int m, int n, const float* points, const int* sel, const float* xyz,
                                   const float* scaling, float lambda, float* out3, float* grad_xyz,
                                   float* grad_scaling, int accumulate, char* workspace, hipStream_t s);
+// delta.hip (the delta-depth loss between a keyframe pair and its gradients towards both depth images; the three small
+// matrices are HOST pointers, composed on the host in double)
+size_t delta_workspace_bytes(int H, int W);
+hipError_t launch_delta_depth_loss(int H, int W, const float* depth_src, const float* acc_src, const float* depth_ref,
+                                   const float* acc_ref, const float* inv_K_src9, const float* K_ref9,
+                                   const float* T_rel12, float lambda, float* out3, float* warped,
+                                   float* dL_ddepth_src, float* dL_ddepth_ref, char* workspace, hipStream_t s);
 hipError_t launch_init_gaussians(int n, int M, const float* xyz, const float* covs, const float* rgbs, float scale_factor,
                                  float* xyz_out, float* fdc_out, float* frest_out, float* scaling_out,
                                  float* rotation_out, float* opacity_out, hipStream_t s);
@@ -463,7 +470,8 @@ enum KernelId {
   K_SORT_SCAN_CHUNKS, K_SORT_SCAN_TOP, K_SORT_SCATTER, K_TILE_RANGES, K_BLEND_FWD, K_BLEND_BWD, K_COMPACT_TOUCHED,
   K_GATHER_RECORDS, K_GAUSSIAN_BWD, K_MARK_VISIBLE, K_DSORT_HIST, K_DSORT_SCAN_CHUNKS, K_DSORT_SCAN_TOP,
   K_DSORT_SCATTER, K_ACTIVATE, K_ACTIVATE_BWD, K_ADAM, K_LOSS_FWD, K_LOSS_FINALIZE, K_LOSS_BWD, K_INIT_GAUSSIANS, K_PACK_PLY, K_MODEL_STEP, K_TILE_ORDER, K_LIVE_SAT, K_COMPACT_NEAR,
-  K_SIMI_NEAREST, K_SIMI_POINTS, K_SIMI_GRADS, K_COUNT
+  K_SIMI_NEAREST, K_SIMI_POINTS, K_SIMI_GRADS,
+  K_DELTA_PROJECT, K_DELTA_SAMPLE, K_DELTA_SCATTER, K_DELTA_CONVERT, K_COUNT
 };
 void prof_begin(int id, hipStream_t s);
 void prof_end(hipStream_t s);

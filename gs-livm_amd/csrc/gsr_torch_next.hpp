@@ -41,6 +41,18 @@ torch::Tensor photometric_loss_parts(const torch::Tensor& image, const torch::Te
 torch::Tensor similarity_loss(const torch::Tensor& points, const torch::Tensor& sel, const torch::Tensor& xyz,
                               const torch::Tensor& scaling, float lambda = 0.2f);
 
+// ---- the delta-depth loss between a history keyframe and its successor (optimize_vis step 5) ------------------------
+// The body of the loop at src/liw/lioOptimization.cpp:1780-1801 -- calcDeltaSimi (src/gs/gaussian.cu:116-199), the two
+// inv_depth, the masks, lambda * mean -- as ONE autograd node on the kernels of csrc/delta.hip.  depth_* / acc_*: the
+// rendered depth and silhouette (depth_sol) of the two views, [H,W] or [1,H,W] f32 on the device; inv_K_src, K_ref:
+// 3x3, T_rel: 3x4 or 4x4 ([R_rel | t_rel] = T_ref T_src^-1 as calcDeltaSimi composes it, i.e. with Get_R() transposed,
+// gaussian.cu:138-162), on the host or anywhere (they are read as 9 + 9 + 12 host floats).  Gradients w.r.t. the two
+// depth images only.  Returns the 0-dim loss.  (Not part of the oracle/ref_link link check, which stays as it is.)
+torch::Tensor delta_depth_loss(const torch::Tensor& depth_src, const torch::Tensor& acc_src,
+                               const torch::Tensor& depth_ref, const torch::Tensor& acc_ref,
+                               const torch::Tensor& inv_K_src, const torch::Tensor& K_ref, const torch::Tensor& T_rel,
+                               float lambda = 0.2f);
+
 // gs_hash_indexes_ (voxel key -> rows of its Gaussians, gaussian.cu:257-263) kept as ranges -- the reference's row
 // vectors are an iota from the running model size (src/liw/lioOptimization.cpp:1268-1279) -- and the selection of
 // calcSimiLoss (gaussian.cu:201-228) on them.

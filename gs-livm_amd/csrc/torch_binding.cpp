@@ -438,6 +438,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("image"), py::arg("gt"), py::arg("lambda_dssim") = 0.2f, py::arg("window1d") = py::none());
   n.def("similarity_loss", &nx::similarity_loss, py::arg("points"), py::arg("sel"), py::arg("xyz"), py::arg("scaling"),
         py::arg("lambda_") = 0.2f);
+  n.def("delta_depth_loss", &nx::delta_depth_loss, py::arg("depth_src"), py::arg("acc_src"), py::arg("depth_ref"),
+        py::arg("acc_ref"), py::arg("inv_K_src"), py::arg("K_ref"), py::arg("T_rel"), py::arg("lambda_") = 0.2f);
   py::class_<nx::VoxelIndex>(n, "VoxelIndex")
       .def(py::init<>())
       .def("add", &nx::VoxelIndex::add, py::arg("keys"), py::arg("counts"), py::arg("first_row"))

@@ -11,6 +11,7 @@
 //   the tensor construction of addNewPointcloud            src/gs/gaussian.cu:241-313
 //   Save_ply / Write_output_ply                            src/gs/gaussian.cu:494-573
 //   compute_min_distance + the selection of calcSimiLoss   src/gs/gaussian.cu:87-114, 201-239
+//   calcDeltaSimi + the loop body around it                src/gs/gaussian.cu:116-199, lioOptimization.cpp:1780-1801
 #include "gsr_torch_next.hpp"
 
 #include <c10/hip/HIPStream.h>
@@ -114,6 +115,47 @@ struct SimilarityLossFn : public torch::autograd::Function<SimilarityLossFn> {
   }
 };
 
+struct DeltaDepthLossFn : public torch::autograd::Function<DeltaDepthLossFn> {
+  static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor depth_src, torch::Tensor acc_src,
+                               torch::Tensor depth_ref, torch::Tensor acc_ref, torch::Tensor inv_K_src,
+                               torch::Tensor K_ref, torch::Tensor T_rel, double lambda) {
+    const torch::Tensor ds = dev_f32(depth_src, "depth_src"), as = dev_f32(acc_src, "acc_src"),
+                        dr = dev_f32(depth_ref, "depth_ref"), ar = dev_f32(acc_ref, "acc_ref");
+    if (ds.dim() < 2) throw std::invalid_argument("delta_depth_loss: [H,W] or [1,H,W] images");
+    const int64_t H = ds.size(-2), W = ds.size(-1);
+    if (ds.numel() != H * W || as.numel() != H * W || dr.numel() != H * W || ar.numel() != H * W)
+      throw std::invalid_argument("delta_depth_loss: four images of one shape [H,W] or [1,H,W]");
+    auto host = [](const torch::Tensor& t, int64_t rows, const char* name) {
+      if (!t.defined() || t.dim() != 2 || t.size(0) < rows)
+        throw std::invalid_argument(std::string(name) + ": a 2-d matrix of at least three rows");
+      return t.to(torch::kCPU, torch::kFloat64).slice(0, 0, rows).to(torch::kFloat32).contiguous();
+    };
+    const torch::Tensor ki = host(inv_K_src, 3, "inv_K_src"), kr = host(K_ref, 3, "K_ref"), tr = host(T_rel, 3, "T_rel");
+    if (ki.numel() != 9 || kr.numel() != 9 || tr.numel() != 12)
+      throw std::invalid_argument("delta_depth_loss: inv_K_src and K_ref are 3x3, T_rel is 3x4 or 4x4");
+    torch::Tensor gs = depth_src.requires_grad() ? torch::empty_like(ds) : torch::Tensor();
+    torch::Tensor gr = depth_ref.requires_grad() ? torch::empty_like(dr) : torch::Tensor();
+    const size_t nbytes = gsr_delta_depth_loss_workspace(static_cast<int>(H), static_cast<int>(W));
+    torch::Tensor ws = torch::empty({static_cast<long long>(nbytes ? nbytes : 1)}, ds.options().dtype(torch::kByte));
+    torch::Tensor out3 = torch::empty({3}, ds.options());
+    check(gsr_delta_depth_loss(static_cast<int>(H), static_cast<int>(W), fp(ds), fp(as), fp(dr), fp(ar),
+                               ki.data_ptr<float>(), kr.data_ptr<float>(), tr.data_ptr<float>(),
+                               static_cast<float>(lambda), out3.data_ptr<float>(), nullptr, fp(gs), fp(gr),
+                               reinterpret_cast<char*>(ws.data_ptr()), nbytes, current_stream()),
+          "gsr_delta_depth_loss");
+    ctx->save_for_backward({gs.defined() ? gs : torch::empty({0}, ds.options()),
+                            gr.defined() ? gr : torch::empty({0}, ds.options())});
+    return out3[0];
+  }
+  static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx,
+                                               torch::autograd::tensor_list grad_outputs) {
+    const auto saved = ctx->get_saved_variables();
+    const torch::Tensor gs = saved[0], gr = saved[1], g = grad_outputs[0];
+    return {gs.numel() ? gs * g : torch::Tensor(), torch::Tensor(), gr.numel() ? gr * g : torch::Tensor(),
+            torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor()};
+  }
+};
+
 struct ActivateFn : public torch::autograd::Function<ActivateFn> {
   static torch::autograd::tensor_list forward(torch::autograd::AutogradContext* ctx, torch::Tensor scaling_raw,
                                               torch::Tensor rotation_raw, torch::Tensor opacity_raw,
@@ -175,6 +217,14 @@ torch::Tensor photometric_loss_parts(const torch::Tensor& image, const torch::Te
 torch::Tensor similarity_loss(const torch::Tensor& points, const torch::Tensor& sel, const torch::Tensor& xyz,
                               const torch::Tensor& scaling, float lambda) {
   return SimilarityLossFn::apply(points, sel, xyz, scaling, static_cast<double>(lambda));
+}
+
+torch::Tensor delta_depth_loss(const torch::Tensor& depth_src, const torch::Tensor& acc_src,
+                               const torch::Tensor& depth_ref, const torch::Tensor& acc_ref,
+                               const torch::Tensor& inv_K_src, const torch::Tensor& K_ref, const torch::Tensor& T_rel,
+                               float lambda) {
+  return DeltaDepthLossFn::apply(depth_src, acc_src, depth_ref, acc_ref, inv_K_src, K_ref, T_rel,
+                                 static_cast<double>(lambda));
 }
 
 int64_t VoxelIndex::add(const std::vector<std::size_t>& keys, const std::vector<int64_t>& counts, int64_t first_row) {

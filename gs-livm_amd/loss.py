@@ -1,6 +1,8 @@
 """Host-side mirror of the reference's image loss (include/gs/gs/loss_utils.cuh) on the fused kernels of
 csrc/loss.hip (SURVEY.md section 8(f) "next" row 2), and of its LiDAR similarity loss
-(GaussianModel::compute_min_distance, src/gs/gaussian.cu:87-114) on those of csrc/simi.hip."""
+(GaussianModel::compute_min_distance, src/gs/gaussian.cu:87-114) on those of csrc/simi.hip, and of the delta-depth
+term between keyframe pairs (GaussianModel::calcDeltaSimi, src/gs/gaussian.cu:116-199, and the loop around it,
+src/liw/lioOptimization.cpp:1780-1801) on those of csrc/delta.hip."""
 import math
 
 import torch
@@ -72,3 +74,49 @@ def similarity_loss(points, sel, xyz, scaling, lambda_=0.2):
     [m,3] f32 and sel [n] int32 (ascending unique rows) come from `VoxelIndex.select` (model.py), xyz is the model's
     _xyz and scaling its activated scales.  Returns the 0-dim loss."""
     return SimilarityLoss.apply(points, sel, xyz, scaling, float(lambda_))
+
+
+class DeltaDepthLoss(torch.autograd.Function):
+    """loss = lambda * mean|inv_depth(calcDeltaSimi(src, ref)) mask - inv_depth(depth_ref) mask|
+    (src/liw/lioOptimization.cpp:1780-1801) as one node; gradients w.r.t. the two rendered DEPTH images only (the
+    silhouettes enter through comparisons; the matrices are data), scaled by the upstream scalar.  In the reference this
+    term never moves a Gaussian, because its rasterizer's backward drops dL/ddepth; here it does when the views were
+    rendered with depth_gradient=True."""
+
+    @staticmethod
+    def forward(ctx, depth_src, acc_src, depth_ref, acc_ref, inv_K_src, K_ref, T_rel, lambda_):
+        need_s, need_r = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        out3, _, gs, gr = _capi.delta_depth_loss(depth_src.contiguous(), acc_src.contiguous(), depth_ref.contiguous(),
+                                                 acc_ref.contiguous(), inv_K_src, K_ref, T_rel, lambda_,
+                                                 want_warped=False, want_grad_src=need_s, want_grad_ref=need_r)
+        ctx.grads = (gs, gr)
+        ctx.parts = out3  # [loss, mean gap, share of unmasked pixels] for logging
+        return out3[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        gs, gr = ctx.grads
+        return ((gs * g if gs is not None else None), None, (gr * g if gr is not None else None), None, None, None,
+                None, None)
+
+
+def delta_depth_loss(depth_src, acc_src, depth_ref, acc_ref, inv_K_src, K_ref, T_rel, lambda_=0.2):
+    """Drop-in for the body of the loop at lioOptimization.cpp:1780-1801 (lambda_delta_depth_simi:
+    config/basic_common.yaml:65): depth_* / acc_* are the rendered depth and silhouette (`depth_sol`) of the history
+    keyframe and its successor, [H,W] or [1,H,W] f32 on the device; inv_K_src, K_ref: 3x3 on the host; T_rel: what
+    `delta_pose` returns.  Returns the 0-dim loss."""
+    return DeltaDepthLoss.apply(depth_src, acc_src, depth_ref, acc_ref, inv_K_src, K_ref, T_rel, float(lambda_))
+
+
+def delta_pose(R_src, t_src, R_ref, t_ref):
+    """T_rel = T_ref T_src^-1 as calcDeltaSimi builds it (src/gs/gaussian.cu:138-162), [3,4] float32 on the host.
+    R_* are what the cameras' Get_R() return.  The reference reads Eigen's COLUMN-major Matrix3f through from_blob as
+    ROW-major (:138-151), so the 4x4 matrices it composes hold the TRANSPOSE of Get_R(); that is reproduced here.
+    Computed in float64 and rounded once."""
+    def T(R, t):
+        m = torch.eye(4, dtype=torch.float64)
+        m[:3, :3] = torch.as_tensor(R, dtype=torch.float64).reshape(3, 3).t()
+        m[:3, 3] = torch.as_tensor(t, dtype=torch.float64).reshape(3)
+        return m
+    rel = T(R_ref, t_ref) @ torch.linalg.inv(T(R_src, t_src))
+    return rel[:3].to(torch.float32)

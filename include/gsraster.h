@@ -371,6 +371,34 @@ int gsr_similarity_loss(int P, int m, int n, const float* points, const int* sel
                         const float* scaling, float lambda, float* out3, float* grad_xyz, float* grad_scaling,
                         int accumulate, char* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the delta-depth loss between a history keyframe and its successor (step 5 of optimize_vis), fused ----
+ * For every SOURCE pixel (u, v) with d = depth_src[v][u]:
+ *   p' = R_rel inv_K_src (u d, v d, d) + t_rel,  Z'[v][u] = p'.z,  (X, Y) = (K_ref p').xy / (K_ref p').z
+ *   out[v][u] = bilinear sample of Z' -- the image indexed by SOURCE pixels -- at (X, Y), zero padding, align_corners
+ *   a = inv_depth(out), b = inv_depth(depth_ref), inv_depth(x) = x <= 0.01 ? 0 : 1 / x
+ *   mask = !(acc_src < 0.5) * !(acc_ref < 0.5),  L = lambda * mean over all H W pixels of |a mask - b mask|
+ * replaces GaussianModel::calcDeltaSimi (src/gs/gaussian.cu:116-199), the two inv_depth (include/gs/gs/loss_utils.cuh:
+ * 15-21), the masks and the mean of src/liw/lioOptimization.cpp:1780-1801 (lambda_delta_depth_simi of
+ * config/basic_common.yaml:65) and their autograd: about forty Torch ops and nine small uploads per pair there, four
+ * launches here (three without dL_ddepth_src).  The sampling is the reference's, as it stands (see csrc/delta.hip).
+ * depth_*, acc_* (the rendered depth and silhouette of the two views): device [H][W] f32.  inv_K_src9, K_ref9 (3x3) and
+ * T_rel12 (3x4, [R_rel | t_rel] = T_ref T_src^-1) are row-major on the HOST and are read before the call returns.
+ * out3 (device) = {L, mean gap (L before lambda), share of pixels with mask = 1}.
+ * warped (nullable, [H][W]) = out, the image the reference dumps to latest_depth.jpg.
+ * dL_ddepth_src / dL_ddepth_ref (nullable, [H][W]) = dL/ddepth for upstream gradient 1, every element WRITTEN; they
+ * are the derivative of the forward above (taps and sample coordinates), with sign(0) = 0, no gradient through a
+ * clamped inv_depth, and the slope of the cell floor() selects at an integer coordinate.  acc gets no gradient.
+ * A sample coordinate that is not finite or beyond +-2^30 is outside the image: value 0, no gradient.
+ * Refused (GSR_ERR_INVALID_ARGUMENT, nothing launched or written): height or width < 2, height * width >= 2^31, a null
+ * required pointer, workspace_bytes below the query.  The workspace needs no alignment.
+ * Deterministic (the many-to-one tap sums are 64-bit integer fixed point, no float atomics, fixed-order reductions),
+ * no host synchronisation, no allocation, the caller's stream only. */
+size_t gsr_delta_depth_loss_workspace(int height, int width);
+int gsr_delta_depth_loss(int height, int width, const float* depth_src, const float* acc_src, const float* depth_ref,
+                         const float* acc_ref, const float* inv_K_src9, const float* K_ref9, const float* T_rel12,
+                         float lambda, float* out3, float* warped, float* dL_ddepth_src, float* dL_ddepth_ref,
+                         char* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- "next" row: the data formats either side of the path ----
  * gsr_init_gaussians: new map points -> leaf parameter rows, the arithmetic of GaussianModel::addNewPointcloud
  * (src/gs/gaussian.cu:241-313): _xyz = xyz; _scaling = log(sqrt(diag(cov) * scale_factor)) (decomposeSR keeps the
