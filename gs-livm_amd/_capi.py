@@ -67,7 +67,8 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_near_budget_scale", "gsr_near_budget_feedback", "gsr_near_far_pause", "gsr_set_near_far_thread",
            "gsr_set_reference_rects_thread", "gsr_async_outcomes_pending", "gsr_async_outcomes_lost",
            "gsr_frame_note_misses", "gsr_similarity_loss", "gsr_similarity_loss_workspace",
-           "gsr_delta_depth_loss", "gsr_delta_depth_loss_workspace")
+           "gsr_delta_depth_loss", "gsr_delta_depth_loss_workspace", "gsr_image_metrics",
+           "gsr_image_metrics_workspace", "gsr_pack_image_u8", "gsr_pack_depth_u8")
 
 
 def lib():
@@ -172,6 +173,14 @@ def lib():
     L.gsr_delta_depth_loss.restype = ci
     L.gsr_delta_depth_loss.argtypes = [ci, ci, vp, vp, vp, vp, C.POINTER(cf), C.POINTER(cf), C.POINTER(cf), cf, vp, vp,
                                        vp, vp, vp, sz, vp]
+    L.gsr_image_metrics_workspace.restype = sz
+    L.gsr_image_metrics_workspace.argtypes = [ci, ci, ci]
+    L.gsr_image_metrics.restype = ci
+    L.gsr_image_metrics.argtypes = [ci, ci, ci, vp, vp, C.POINTER(cf), vp, vp, vp, sz, vp]
+    L.gsr_pack_image_u8.restype = ci
+    L.gsr_pack_image_u8.argtypes = [ci, ci, vp, ci, vp, sz, vp]
+    L.gsr_pack_depth_u8.restype = ci
+    L.gsr_pack_depth_u8.argtypes = [ci, ci, vp, cf, vp, sz, vp]
     L.gsr_init_gaussians.restype = ci
     L.gsr_init_gaussians.argtypes = [ci, ci, vp, vp, vp, cf] + [vp] * 6 + [vp]
     L.gsr_ply_row_floats.restype = sz
@@ -618,6 +627,61 @@ def delta_depth_loss(depth_src, acc_src, depth_ref, acc_ref, inv_K_src, K_ref, T
                                       trel, float(lambda_), _ptr(out3), _ptr(warped), _ptr(gs), _ptr(gr), _ptr(ws),
                                       nbytes, _stream()))
     return out3, warped, gs, gr
+
+
+def image_metrics(img, gt, window11, out=None, totals=None):
+    """{psnr, ssim, l1, mse} of img against gt ([C,H,W] f32 on the device) in two launches (include/gsraster.h,
+    gsr_image_metrics).  out: a contiguous device f32 [4] to write (a row of a larger tensor); totals: a device float64
+    [4] the call adds {psnr, ssim, l1, 1} to.  Returns out (a new tensor when none is given)."""
+    assert img.dim() == 3 and img.shape == gt.shape and img.is_cuda and img.dtype == torch.float32 == gt.dtype
+    Cn, H, W = (int(x) for x in img.shape)
+    img, gt = img.contiguous(), gt.contiguous()
+    if out is None:
+        out = torch.empty(4, dtype=torch.float32, device=img.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.numel() == 4 and out.is_contiguous()
+    if totals is not None:
+        assert totals.is_cuda and totals.dtype == torch.float64 and totals.numel() == 4 and totals.is_contiguous()
+    nbytes = int(lib().gsr_image_metrics_workspace(Cn, H, W))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=img.device)
+    win = (C.c_float * 11)(*[float(x) for x in window11])
+    _check(lib().gsr_image_metrics(Cn, H, W, _ptr(img), _ptr(gt), win, _ptr(out), _ptr(totals), _ptr(ws), nbytes,
+                                   _stream()))
+    return out
+
+
+def _rows_u8(out, shape, dev):
+    """(out, pitch): `out` -- a uint8 device tensor of `shape` whose elements of a row are adjacent, e.g. a column slice
+    of a wider image -- or a new one."""
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    if out.dtype != torch.uint8 or out.device != dev or tuple(out.shape) != tuple(shape):
+        raise ValueError("out must be a uint8 tensor of shape %s on the device of the image" % (tuple(shape),))
+    row = shape[1] * (shape[2] if len(shape) == 3 else 1)   # bytes of a row
+    want = (None, shape[2], 1) if len(shape) == 3 else (None, 1)
+    pitch = int(out.stride(0)) if shape[0] > 1 else row
+    if any(shape[d] > 1 and out.stride(d) != want[d] for d in range(1, len(shape))) or pitch < row:
+        raise ValueError("out: the bytes of a row must be adjacent and rows must not overlap")
+    return out, pitch
+
+
+def pack_image_u8(img, bgr=True, out=None):
+    """[3,H,W] f32 -> interleaved uint8 [H,W,3] (include/gsraster.h, gsr_pack_image_u8), written into `out` if given."""
+    assert img.dim() == 3 and img.size(0) == 3 and img.is_cuda and img.dtype == torch.float32
+    H, W = int(img.size(1)), int(img.size(2))
+    img = img.contiguous()
+    out, pitch = _rows_u8(out, (H, W, 3), img.device)
+    _check(lib().gsr_pack_image_u8(H, W, _ptr(img), int(bool(bgr)), C.c_void_p(out.data_ptr()), pitch, _stream()))
+    return out
+
+
+def pack_depth_u8(depth, max_depth, out=None):
+    """[H,W] or [1,H,W] f32 -> uint8 [H,W] (include/gsraster.h, gsr_pack_depth_u8), written into `out` if given."""
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    assert depth.is_cuda and depth.dtype == torch.float32 and depth.numel() == H * W
+    depth = depth.contiguous()
+    out, pitch = _rows_u8(out, (H, W), depth.device)
+    _check(lib().gsr_pack_depth_u8(H, W, _ptr(depth), float(max_depth), C.c_void_p(out.data_ptr()), pitch, _stream()))
+    return out
 
 
 # ---- "next" row 4: map growth and PLY export (include/gsraster.h; csrc/growth.hip) ----

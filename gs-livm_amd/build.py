@@ -34,6 +34,7 @@ UNITS = {
     "growth.hip": [],
     "simi.hip": [],
     "delta.hip": [],
+    "metrics.hip": ["-fno-slp-vectorize"],  # (k_metrics_forward is k_loss_forward's arithmetic: built like loss.hip)
     "api.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "gsr_internal.hpp"), os.path.join(CSRC, "sort_core.hpp"),

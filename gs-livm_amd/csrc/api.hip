@@ -130,7 +130,8 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_sort_scan_chunks[depth]", "k_sort_scan_top[depth]", "k_sort_scatter[depth]", "k_activate",
     "k_activate_backward", "k_adam", "k_loss_forward", "k_loss_finalize", "k_loss_backward", "k_init_gaussians", "k_pack_ply_rows", "k_model_step", "k_tile_order", "k_live_sat", "k_compact_near",
     "k_simi_nearest", "k_simi_points", "k_simi_grads",
-    "k_delta_project", "k_delta_sample", "k_delta_scatter", "k_delta_convert"};
+    "k_delta_project", "k_delta_sample", "k_delta_scatter", "k_delta_convert",
+    "k_metrics_forward", "k_metrics_finalize", "k_pack_image_u8", "k_pack_depth_u8"};
 
 extern "C" {
 
@@ -1622,6 +1623,57 @@ int gsr_delta_depth_loss(int height, int width, const float* depth_src, const fl
   HIP_TRY(launch_delta_depth_loss(height, width, depth_src, acc_src, depth_ref, acc_ref, inv_K_src9, K_ref9, T_rel12,
                                   lambda, out3, warped, dL_ddepth_src, dL_ddepth_ref, workspace,
                                   (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+size_t gsr_image_metrics_workspace(int channels, int height, int width) {
+  if (channels <= 0 || height <= 0 || width <= 0 ||
+      (unsigned long long)height * (unsigned long long)width >= 0x7fffffffull)
+    return 0;
+  return metrics_workspace_bytes(channels, height, width);
+}
+
+int gsr_image_metrics(int channels, int height, int width, const float* img, const float* gt,
+                      const float* window11_host, float* out4, double* totals, char* workspace, size_t workspace_bytes,
+                      void* stream_) {
+  g_err[0] = 0;
+  if (channels <= 0 || height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if ((unsigned long long)height * (unsigned long long)width >= 0x7fffffffull)  // (32-bit offsets inside a plane)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  if (!img || !gt || !window11_host || !out4 || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (workspace_bytes < metrics_workspace_bytes(channels, height, width))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes",
+                metrics_workspace_bytes(channels, height, width));
+  HIP_TRY(launch_image_metrics(channels, height, width, img, gt, window11_host, out4, totals, workspace,
+                               (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+int gsr_pack_image_u8(int height, int width, const float* img3, int bgr, unsigned char* out, size_t pitch_bytes,
+                      void* stream_) {
+  g_err[0] = 0;
+  if (height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if ((unsigned long long)height * (unsigned long long)width >= 0x7fffffffull)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  if (!img3 || !out) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (pitch_bytes < 3 * (size_t)width)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: a row has %zu bytes", 3 * (size_t)width);
+  HIP_TRY(launch_pack_image_u8(height, width, img3, bgr, out, pitch_bytes, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+int gsr_pack_depth_u8(int height, int width, const float* depth, float max_depth, unsigned char* out,
+                      size_t pitch_bytes, void* stream_) {
+  g_err[0] = 0;
+  if (height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if ((unsigned long long)height * (unsigned long long)width >= 0x7fffffffull)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  if (!depth || !out) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (pitch_bytes < (size_t)width)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: a row has %zu bytes", (size_t)width);
+  if (!(max_depth > 0.f) || !(max_depth <= 3.402823466e38f))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "max_depth must be positive and finite");
+  HIP_TRY(launch_pack_depth_u8(height, width, depth, max_depth, out, pitch_bytes, (hipStream_t)stream_));
   return GSR_OK;
 }
 

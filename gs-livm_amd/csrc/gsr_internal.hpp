@@ -446,6 +446,14 @@ hipError_t launch_delta_depth_loss(int H, int W, const float* depth_src, const f
                                    const float* acc_ref, const float* inv_K_src9, const float* K_ref9,
                                    const float* T_rel12, float lambda, float* out3, float* warped,
                                    float* dL_ddepth_src, float* dL_ddepth_ref, char* workspace, hipStream_t s);
+// metrics.hip (the evaluation pass: PSNR / SSIM / L1 / mse of a render against its ground truth, 8-bit frame export)
+size_t metrics_workspace_bytes(int C, int H, int W);
+hipError_t launch_image_metrics(int C, int H, int W, const float* img, const float* gt, const float* window11,
+                                float* out4, double* totals, char* workspace, hipStream_t s);
+hipError_t launch_pack_image_u8(int H, int W, const float* img3, int bgr, unsigned char* out, size_t pitch,
+                                hipStream_t s);
+hipError_t launch_pack_depth_u8(int H, int W, const float* depth, float max_depth, unsigned char* out, size_t pitch,
+                                hipStream_t s);
 hipError_t launch_init_gaussians(int n, int M, const float* xyz, const float* covs, const float* rgbs, float scale_factor,
                                  float* xyz_out, float* fdc_out, float* frest_out, float* scaling_out,
                                  float* rotation_out, float* opacity_out, hipStream_t s);
@@ -471,7 +479,8 @@ enum KernelId {
   K_GATHER_RECORDS, K_GAUSSIAN_BWD, K_MARK_VISIBLE, K_DSORT_HIST, K_DSORT_SCAN_CHUNKS, K_DSORT_SCAN_TOP,
   K_DSORT_SCATTER, K_ACTIVATE, K_ACTIVATE_BWD, K_ADAM, K_LOSS_FWD, K_LOSS_FINALIZE, K_LOSS_BWD, K_INIT_GAUSSIANS, K_PACK_PLY, K_MODEL_STEP, K_TILE_ORDER, K_LIVE_SAT, K_COMPACT_NEAR,
   K_SIMI_NEAREST, K_SIMI_POINTS, K_SIMI_GRADS,
-  K_DELTA_PROJECT, K_DELTA_SAMPLE, K_DELTA_SCATTER, K_DELTA_CONVERT, K_COUNT
+  K_DELTA_PROJECT, K_DELTA_SAMPLE, K_DELTA_SCATTER, K_DELTA_CONVERT,
+  K_METRICS_FWD, K_METRICS_FINALIZE, K_PACK_IMAGE_U8, K_PACK_DEPTH_U8, K_COUNT
 };
 void prof_begin(int id, hipStream_t s);
 void prof_end(hipStream_t s);

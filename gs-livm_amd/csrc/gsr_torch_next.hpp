@@ -53,6 +53,24 @@ torch::Tensor delta_depth_loss(const torch::Tensor& depth_src, const torch::Tens
                                const torch::Tensor& inv_K_src, const torch::Tensor& K_ref, const torch::Tensor& T_rel,
                                float lambda = 0.2f);
 
+// ---- the evaluation pass (saveRender, src/liw/lioOptimization.cpp:2182-2245; the status line of optimize_vis) ------
+// [psnr, ssim, l1, mse] of image against gt ([C,H,W] f32 on the device) on the kernels of csrc/metrics.hip, a device
+// tensor, no graph: gaussian_splatting::psnr (loss_utils.cuh:89-93, the mean of the per-channel PSNRs, +inf where a
+// channel is identical) and ::ssim (:43-70) of :2203-2207 in two launches.  totals: a device float64 [4] that
+// {psnr, ssim, l1, 1} is added to -- psnr_value, ssim_value and count of :2184-2231 without an .item() per frame.
+// (Like delta_depth_loss, not part of the oracle/ref_link link check, which keeps its twenty entry points.)
+torch::Tensor image_metrics(const torch::Tensor& image, const torch::Tensor& gt,
+                            const torch::Tensor& window1d = torch::Tensor(),
+                            const torch::Tensor& totals = torch::Tensor());
+torch::Tensor psnr(const torch::Tensor& image, const torch::Tensor& gt);  // image_metrics(...)[0], 0-dim
+// tensor2CvMat3X (:2113-2136) on the device: [3,H,W] f32 -> uint8 [H,W,3] (x * 255, clamp, truncate; NaN -> 0), BGR
+// for cv::imwrite unless bgr = false.  out: a uint8 [H,W,3] view to write into, e.g. a column slice of the [H,2W,3]
+// image that replaces cv::hconcat (:2219-2220); undefined = a new tensor.
+torch::Tensor to_u8(const torch::Tensor& image, bool bgr = true, torch::Tensor out = torch::Tensor());
+// tensor2CvMat2X (:2150-2164) up to cv::applyColorMap: [H,W] or [1,H,W] f32 -> uint8 [H,W],
+// round_half_even(depth * (255 / max_depth)) saturated, NaN -> 0.
+torch::Tensor depth_to_u8(const torch::Tensor& depth, float max_depth = 50.0f, torch::Tensor out = torch::Tensor());
+
 // gs_hash_indexes_ (voxel key -> rows of its Gaussians, gaussian.cu:257-263) kept as ranges -- the reference's row
 // vectors are an iota from the running model size (src/liw/lioOptimization.cpp:1268-1279) -- and the selection of
 // calcSimiLoss (gaussian.cu:201-228) on them.

@@ -440,6 +440,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lambda_") = 0.2f);
   n.def("delta_depth_loss", &nx::delta_depth_loss, py::arg("depth_src"), py::arg("acc_src"), py::arg("depth_ref"),
         py::arg("acc_ref"), py::arg("inv_K_src"), py::arg("K_ref"), py::arg("T_rel"), py::arg("lambda_") = 0.2f);
+  n.def("image_metrics",
+        [opt](torch::Tensor image, torch::Tensor gt, py::object window, py::object totals) {
+          return nx::image_metrics(image, gt, opt(window), opt(totals));
+        },
+        py::arg("image"), py::arg("gt"), py::arg("window1d") = py::none(), py::arg("totals") = py::none());
+  n.def("psnr", &nx::psnr, py::arg("image"), py::arg("gt"));
+  n.def("to_u8", [opt](torch::Tensor image, bool bgr, py::object out) { return nx::to_u8(image, bgr, opt(out)); },
+        py::arg("image"), py::arg("bgr") = true, py::arg("out") = py::none());
+  n.def("depth_to_u8",
+        [opt](torch::Tensor depth, float max_depth, py::object out) { return nx::depth_to_u8(depth, max_depth, opt(out)); },
+        py::arg("depth"), py::arg("max_depth") = 50.0f, py::arg("out") = py::none());
   py::class_<nx::VoxelIndex>(n, "VoxelIndex")
       .def(py::init<>())
       .def("add", &nx::VoxelIndex::add, py::arg("keys"), py::arg("counts"), py::arg("first_row"))

@@ -12,6 +12,7 @@
 //   Save_ply / Write_output_ply                            src/gs/gaussian.cu:494-573
 //   compute_min_distance + the selection of calcSimiLoss   src/gs/gaussian.cu:87-114, 201-239
 //   calcDeltaSimi + the loop body around it                src/gs/gaussian.cu:116-199, lioOptimization.cpp:1780-1801
+//   psnr + ssim + tensor2CvMat3X / 2X of saveRender        loss_utils.cuh:89-93, lioOptimization.cpp:2113-2164, 2198-2231
 #include "gsr_torch_next.hpp"
 
 #include <c10/hip/HIPStream.h>
@@ -225,6 +226,68 @@ torch::Tensor delta_depth_loss(const torch::Tensor& depth_src, const torch::Tens
                                float lambda) {
   return DeltaDepthLossFn::apply(depth_src, acc_src, depth_ref, acc_ref, inv_K_src, K_ref, T_rel,
                                  static_cast<double>(lambda));
+}
+
+torch::Tensor image_metrics(const torch::Tensor& image, const torch::Tensor& gt, const torch::Tensor& window1d,
+                            const torch::Tensor& totals) {
+  torch::NoGradGuard no_grad;
+  const torch::Tensor img = dev_f32(image, "image"), ref = dev_f32(gt, "gt");
+  if (img.dim() != 3 || img.sizes() != ref.sizes()) throw std::invalid_argument("image_metrics: [C,H,W] images of one shape");
+  if (totals.defined() && (!totals.is_cuda() || totals.scalar_type() != torch::kFloat64 || totals.numel() != 4 ||
+                           !totals.is_contiguous()))
+    throw std::invalid_argument("image_metrics: totals is a contiguous float64 tensor of 4 elements on the device");
+  const int C = img.size(0), H = img.size(1), W = img.size(2);
+  float taps[11];
+  window_taps(window1d, taps);
+  const size_t nbytes = gsr_image_metrics_workspace(C, H, W);
+  torch::Tensor ws = torch::empty({static_cast<long long>(nbytes ? nbytes : 1)}, img.options().dtype(torch::kByte));
+  torch::Tensor out4 = torch::empty({4}, img.options());
+  check(gsr_image_metrics(C, H, W, fp(img), fp(ref), taps, out4.data_ptr<float>(),
+                          totals.defined() ? totals.data_ptr<double>() : nullptr,
+                          reinterpret_cast<char*>(ws.data_ptr()), nbytes, current_stream()),
+        "gsr_image_metrics");
+  return out4;
+}
+
+torch::Tensor psnr(const torch::Tensor& image, const torch::Tensor& gt) { return image_metrics(image, gt)[0]; }
+
+namespace {
+// `out` (or a new tensor) as rows of adjacent bytes: its pitch in bytes
+size_t rows_u8(torch::Tensor& out, std::vector<int64_t> shape, const torch::Tensor& like, const char* what) {
+  if (!out.defined()) out = torch::empty(shape, like.options().dtype(torch::kByte));
+  const int64_t row = shape[1] * (shape.size() == 3 ? shape[2] : 1);
+  bool ok = out.scalar_type() == torch::kByte && out.device() == like.device() && out.sizes().vec() == shape;
+  for (size_t d = 1; ok && d < shape.size(); d++)
+    ok = shape[d] <= 1 || out.stride(d) == (d + 1 < shape.size() ? shape[d + 1] : 1);
+  const int64_t pitch = shape[0] > 1 && ok ? out.stride(0) : row;
+  if (!ok || pitch < row)
+    throw std::invalid_argument(std::string(what) + ": out is a uint8 device tensor of the image's shape whose rows are adjacent bytes");
+  return static_cast<size_t>(pitch);
+}
+}  // namespace
+
+torch::Tensor to_u8(const torch::Tensor& image, bool bgr, torch::Tensor out) {
+  torch::NoGradGuard no_grad;
+  const torch::Tensor img = dev_f32(image, "image");
+  if (img.dim() != 3 || img.size(0) != 3) throw std::invalid_argument("to_u8: a [3,H,W] image");
+  const int64_t H = img.size(1), W = img.size(2);
+  const size_t pitch = rows_u8(out, {H, W, 3}, img, "to_u8");
+  check(gsr_pack_image_u8(static_cast<int>(H), static_cast<int>(W), fp(img), bgr ? 1 : 0,
+                          static_cast<unsigned char*>(out.data_ptr()), pitch, current_stream()),
+        "gsr_pack_image_u8");
+  return out;
+}
+
+torch::Tensor depth_to_u8(const torch::Tensor& depth, float max_depth, torch::Tensor out) {
+  torch::NoGradGuard no_grad;
+  const torch::Tensor d = dev_f32(depth, "depth");
+  if (d.dim() < 2 || d.numel() != d.size(-2) * d.size(-1)) throw std::invalid_argument("depth_to_u8: [H,W] or [1,H,W]");
+  const int64_t H = d.size(-2), W = d.size(-1);
+  const size_t pitch = rows_u8(out, {H, W}, d, "depth_to_u8");
+  check(gsr_pack_depth_u8(static_cast<int>(H), static_cast<int>(W), fp(d), max_depth,
+                          static_cast<unsigned char*>(out.data_ptr()), pitch, current_stream()),
+        "gsr_pack_depth_u8");
+  return out;
 }
 
 int64_t VoxelIndex::add(const std::vector<std::size_t>& keys, const std::vector<int64_t>& counts, int64_t first_row) {

@@ -1,0 +1,77 @@
+"""Host-side mirror of the reference's evaluation pass on the fused kernels of csrc/metrics.hip: what saveRender
+(src/liw/lioOptimization.cpp:2182-2245) and the status line of optimize_vis (:1739-1776) run on the device around a
+forward-only render -- gaussian_splatting::psnr and ::ssim (include/gs/gs/loss_utils.cuh:89-93, 43-70) and the 8-bit
+images of tensor2CvMat3X (:2113-2136) and tensor2CvMat2X (:2150-2164).  The JET colour map, PNG and MP4 writing stay
+with the host application."""
+import torch
+
+from . import _capi
+from .loss import reference_window_1d
+from .render_utils import render
+
+
+def image_metrics(img, gt, window11=None, totals=None):
+    """-> device tensor [psnr, ssim, l1, mse] of img against gt ([C,H,W] f32 on the device), two launches, no host
+    round trip.  psnr is the reference's mean of the per-channel PSNRs (+inf where a channel is identical); ssim and l1
+    are those of `photometric_loss`.  totals: a device float64 [4] that {psnr, ssim, l1, 1} is added to (the running
+    sums and the frame count of a keyframe sweep)."""
+    if window11 is None:
+        window11 = reference_window_1d()
+    return _capi.image_metrics(img, gt, window11.tolist(), totals=totals)
+
+
+def psnr(img, gt):
+    """Drop-in for gaussian_splatting::psnr(rendered_img, gt_img) (loss_utils.cuh:89-93): a 0-dim device tensor."""
+    return image_metrics(img, gt)[0]
+
+
+def to_u8(img, bgr=True, out=None):
+    """tensor2CvMat3X (:2113-2136) on the device: [3,H,W] f32 -> uint8 [H,W,3], x * 255 clamped to [0, 255] and
+    truncated (NaN -> 0), channels swapped for cv::imwrite unless bgr=False.  out: a uint8 [H,W,3] view to write into
+    -- e.g. a column slice of a wider [H,2W,3] image -- whose bytes outside the written pixels are left alone."""
+    return _capi.pack_image_u8(img, bgr=bgr, out=out)
+
+
+def side_by_side(img, gt, bgr=True):
+    """cv::hconcat(render_image, gt_image) of saveRender (:2219-2220): one uint8 [H,2W,3] device image."""
+    H, W = int(img.size(1)), int(img.size(2))
+    both = torch.empty((H, 2 * W, 3), dtype=torch.uint8, device=img.device)
+    to_u8(img, bgr=bgr, out=both[:, :W])
+    to_u8(gt, bgr=bgr, out=both[:, W:])
+    return both
+
+
+def depth_to_u8(depth, max_depth=50.0, out=None):
+    """tensor2CvMat2X (:2150-2164) up to its colour map: [H,W] or [1,H,W] f32 -> uint8 [H,W],
+    round_half_even(depth * (255 / max_depth)) saturated to [0, 255] (NaN -> 0): cv::Mat::convertTo(CV_8U) as OpenCV
+    documents it.  cv::applyColorMap(COLORMAP_JET) is the host's."""
+    return _capi.pack_depth_u8(depth, max_depth, out=out)
+
+
+def evaluate_keyframes(cameras, gts, model, bg, on_frame=None, window11=None):
+    """The loop of saveRender (:2198-2231): every keyframe is rendered forward-only and measured against its ground
+    truth ([3,H,W] f32 on the device); the per-frame metrics and their running float64 sums stay on the device and are
+    copied to the host ONCE, after the last frame (the reference makes two .item() round trips per frame).
+    on_frame(i, image, depth): hook of a host that exports frames (to_u8 / side_by_side / depth_to_u8, PNG writing).
+    -> dict(rows = CPU f32 [n,4] of {psnr, ssim, l1, mse} per frame, totals = CPU f64 [4] = {sum psnr, sum ssim,
+    sum l1, n}, mean_psnr, mean_ssim, frames = n)."""
+    cameras, gts = list(cameras), list(gts)
+    if len(cameras) != len(gts):
+        raise ValueError("one ground-truth image per camera")
+    n = len(cameras)
+    dev = model.Get_xyz().device
+    win = (reference_window_1d() if window11 is None else window11).tolist()
+    # one buffer, one copy: the four float64 totals in front (8-byte aligned), the n float32 rows behind them
+    buf = torch.zeros(32 + 16 * n, dtype=torch.uint8, device=dev)
+    totals, rows = buf[:32].view(torch.float64), buf[32:].view(torch.float32).view(n, 4)
+    with torch.no_grad():
+        for i, (cam, gt) in enumerate(zip(cameras, gts)):
+            image, depth, _ = render(cam, model, bg)
+            _capi.image_metrics(image, gt, win, out=rows[i], totals=totals)
+            if on_frame is not None:
+                on_frame(i, image, depth)
+    host = buf.cpu()
+    totals, rows = host[:32].view(torch.float64).clone(), host[32:].view(torch.float32).view(n, 4).clone()
+    count = float(totals[3])
+    mean = lambda s: float(s) / count if n else float("nan")  # noqa: E731  (the reference divides by count all the same)
+    return dict(rows=rows, totals=totals, mean_psnr=mean(totals[0]), mean_ssim=mean(totals[1]), frames=n)

@@ -399,6 +399,48 @@ int gsr_delta_depth_loss(int height, int width, const float* depth_src, const fl
                          float lambda, float* out3, float* warped, float* dL_ddepth_src, float* dL_ddepth_ref,
                          char* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the evaluation pass around a forward-only render: PSNR, SSIM and 8-bit frame export ----
+ * gsr_image_metrics: out4 (device) = {psnr, ssim, l1, mse} of img against gt, [channels][H][W] device f32, in two
+ * launches:
+ *   mse_c = mean over H W of (img - gt)^2 in channel c,  psnr = mean_c 20 log10(1 / sqrt(mse_c)),  mse = mean_c mse_c
+ *   ssim = mean(SSIM(img, gt)), l1 = mean|img - gt|: the arithmetic of gsr_photometric_loss, same window convention
+ * replaces gaussian_splatting::psnr and ::ssim (include/gs/gs/loss_utils.cuh:89-93, 43-70) as saveRender calls them per
+ * keyframe (src/liw/lioOptimization.cpp:2203-2207) and the status line of optimize_vis every 50 iterations
+ * (:1739-1776).  psnr is the reference's, as it stands: the MEAN OF THE PER-CHANNEL PSNRs, not the PSNR of the pooled
+ * error; it is evaluated in float64 from fixed-order float64 sums and narrowed once; a channel with mse_c == 0 makes it
+ * +inf, as 1.0 / 0 does there.  Nothing is stored per pixel: the workspace holds three floats per 54 x 32 work unit and
+ * needs no more than float alignment.
+ * totals (nullable, device, 4 doubles, 8-byte aligned): {(double)out4[0], (double)out4[1], (double)out4[2], 1.0} is
+ * ADDED to it -- the values as stored, widened -- so that after a keyframe sweep into one zeroed buffer it holds
+ * exactly the float64 sums of the per-frame psnr, ssim and l1 in stream order and the frame count (saveRender's
+ * psnr_value / ssim_value / count, :2184-2231, without its two .item() round trips per frame).  An infinite frame
+ * makes that sum infinite, as there.
+ * Refused (GSR_ERR_INVALID_ARGUMENT, nothing launched or written), in this order: a non-positive dimension; H * W >=
+ * 2^31 - 1; a null img, gt, window11_host, out4 or workspace; workspace_bytes below the query (the message names the
+ * bytes needed).  The query returns 0 for a refused shape.  Deterministic, no host synchronisation, no allocation,
+ * the caller's stream only.
+ *
+ * gsr_pack_image_u8: img3 [3][H][W] device f32 -> out, interleaved 8-bit [H][W][3] whose rows are pitch_bytes apart:
+ * v = x * 255 in float32, clamped to [0, 255], truncated toward zero; NaN -> 0 (the reference leaves that cast
+ * undefined).  bgr = 0: out[..][c] = plane c; bgr = 1: planes 2, 1, 0 -- what tensor2CvMat3X (:2113-2136:
+ * mul(255).clamp(0, 255).to(kU8) and the channel swap for cv::imwrite) returns.  The bytes between a row's 3 W bytes and
+ * the next row are never written, so the hconcat of :2219-2220 is two calls into one [H][2 W][3] buffer (out + 3 W for
+ * the right half, pitch 6 W).  Any out address and any pitch >= 3 W are accepted (4-byte stores are used where they
+ * allow it).  Refused: a non-positive dimension; H * W >= 2^31 - 1; a null pointer; pitch_bytes < 3 W.
+ *
+ * gsr_pack_depth_u8: depth [H][W] device f32 -> out, 8-bit [H][W] with a row pitch: round-half-to-even of
+ * depth * (255 / max_depth), the factor formed and the multiply done in float32, saturated to [0, 255], NaN -> 0 --
+ * cv::Mat::convertTo(CV_8U) as OpenCV documents it, i.e. tensor2CvMat2X (:2150-2164) up to its colour map, which
+ * stays on the host.  Refused: as above with pitch_bytes < W, and max_depth not positive and finite. */
+size_t gsr_image_metrics_workspace(int channels, int height, int width);
+int gsr_image_metrics(int channels, int height, int width, const float* img, const float* gt,
+                      const float* window11_host, float* out4, double* totals, char* workspace, size_t workspace_bytes,
+                      void* stream);
+int gsr_pack_image_u8(int height, int width, const float* img3, int bgr, unsigned char* out, size_t pitch_bytes,
+                      void* stream);
+int gsr_pack_depth_u8(int height, int width, const float* depth, float max_depth, unsigned char* out,
+                      size_t pitch_bytes, void* stream);
+
 /* ---- "next" row: the data formats either side of the path ----
  * gsr_init_gaussians: new map points -> leaf parameter rows, the arithmetic of GaussianModel::addNewPointcloud
  * (src/gs/gaussian.cu:241-313): _xyz = xyz; _scaling = log(sqrt(diag(cov) * scale_factor)) (decomposeSR keeps the
