@@ -22,7 +22,7 @@ from ._capi import (GsrError, LIB_PATH, NumRendered, emit_guard_trips, last_num_
 from .loss import (DeltaDepthLoss, PhotometricLoss, SimilarityLoss, delta_depth_loss, delta_pose, photometric_loss,  # noqa: F401
                    reference_window_1d, similarity_loss)
 from .metrics import depth_to_u8, evaluate_keyframes, image_metrics, psnr, side_by_side, to_u8  # noqa: F401
-from .model import FusedActivations, FusedAdam, GaussianParameters, GrowableAdam, GrowableGaussians, VoxelIndex  # noqa: F401
+from .model import FusedActivations, FusedAdam, GaussianParameters, GrowableAdam, GrowableGaussians, VoxelIndex, prune_rows  # noqa: F401
 from . import ply  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer,  # noqa: F401
                          rasterize_gaussians)
@@ -46,5 +46,5 @@ def torch_ops():
     return mod
 
 
-__all__ = ["image_metrics", "psnr", "to_u8", "side_by_side", "depth_to_u8", "evaluate_keyframes", "DeltaDepthLoss", "delta_depth_loss", "delta_pose", "SimilarityLoss", "similarity_loss", "VoxelIndex", "PhotometricLoss", "photometric_loss", "reference_window_1d", "FusedActivations", "FusedAdam", "GaussianParameters", "GrowableAdam", "GrowableGaussians", "ply", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "Camera", "render", "get_projection_matrix", "rasterize_forward",
+__all__ = ["prune_rows", "image_metrics", "psnr", "to_u8", "side_by_side", "depth_to_u8", "evaluate_keyframes", "DeltaDepthLoss", "delta_depth_loss", "delta_pose", "SimilarityLoss", "similarity_loss", "VoxelIndex", "PhotometricLoss", "photometric_loss", "reference_window_1d", "FusedActivations", "FusedAdam", "GaussianParameters", "GrowableAdam", "GrowableGaussians", "ply", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "Camera", "render", "get_projection_matrix", "rasterize_forward",
            "rasterize_backward", "mark_visible", "state_views", "set_reference_rects", "reference_rects", "last_num_rendered", "set_binning_capacity_hint", "speculation_stats", "emit_guard_trips", "mailbox_slow_path_last", "set_near_far", "set_near_far_thread", "set_reference_rects_thread", "async_outcomes_pending", "set_near_far_hints", "last_near_far", "set_far_speculation", "last_far_skipped", "NumRendered", "lib", "torch_ops", "synthetic", "multiview", "GsrError", "LIB_PATH"]

@@ -68,7 +68,8 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_set_reference_rects_thread", "gsr_async_outcomes_pending", "gsr_async_outcomes_lost",
            "gsr_frame_note_misses", "gsr_similarity_loss", "gsr_similarity_loss_workspace",
            "gsr_delta_depth_loss", "gsr_delta_depth_loss_workspace", "gsr_image_metrics",
-           "gsr_image_metrics_workspace", "gsr_pack_image_u8", "gsr_pack_depth_u8")
+           "gsr_image_metrics_workspace", "gsr_pack_image_u8", "gsr_pack_depth_u8", "gsr_prune_workspace",
+           "gsr_prune_mark", "gsr_prune_compact")
 
 
 def lib():
@@ -181,6 +182,12 @@ def lib():
     L.gsr_pack_image_u8.argtypes = [ci, ci, vp, ci, vp, sz, vp]
     L.gsr_pack_depth_u8.restype = ci
     L.gsr_pack_depth_u8.argtypes = [ci, ci, vp, cf, vp, sz, vp]
+    L.gsr_prune_workspace.restype = sz
+    L.gsr_prune_workspace.argtypes = [ci]
+    L.gsr_prune_mark.restype = ci
+    L.gsr_prune_mark.argtypes = [ci, vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, vp, sz, vp]
+    L.gsr_prune_compact.restype = ci
+    L.gsr_prune_compact.argtypes = [ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(ci), vp, vp, vp]
     L.gsr_init_gaussians.restype = ci
     L.gsr_init_gaussians.argtypes = [ci, ci, vp, vp, vp, cf] + [vp] * 6 + [vp]
     L.gsr_ply_row_floats.restype = sz
@@ -733,3 +740,52 @@ def model_step(params6, exp_avg6, exp_avg_sq6, g_xyz, g_scales, g_rot, g_opac, g
                                 _ptr(g_rot), _ptr(g_opac), _ptr(g_shs), _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), _ptr(o[3]), lr,
                                 float(beta1), float(beta2), float(eps), int(step), _stream()))
     return outs
+
+
+# ---- in-place pruning (include/gsraster.h; csrc/prune.hip) ----
+def prune_mark(xyz, scaling_raw, rotation_raw, opacity_raw, min_opacity=1.0 / 255.0, max_scale=0.3,
+               drop_nonfinite=True, drop=None, packed=False):
+    """The drop rule and the row map of the stable compaction, three launches (include/gsraster.h, gsr_prune_mark).
+    The raw leaves [P,3], [P,3], [P,4], [P,1] on the device; drop: an optional [P] bool / uint8 mask of the caller's.
+    Returns (reasons [P] uint8, row_map [P+1] int32, counts [5] int32 = {P', opacity, scale, non-finite, mask}),
+    device tensors; nothing waits for the device.  row_map and counts are views of ONE int32 [P+6] buffer, which
+    packed=True appends to the result: a host that wants both fetches them with one copy."""
+    P = int(xyz.size(0))
+    dev = xyz.device
+    for t in (xyz, scaling_raw, rotation_raw, opacity_raw):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and int(t.size(0)) == P
+    if drop is not None:
+        if drop.dtype == torch.bool:
+            drop = drop.view(torch.uint8)
+        assert drop.is_cuda and drop.is_contiguous() and drop.dtype == torch.uint8 and drop.numel() == P
+    reasons = torch.empty((P,), dtype=torch.uint8, device=dev)
+    both = torch.empty((P + 6,), dtype=torch.int32, device=dev)
+    row_map, counts = both[:P + 1], both[P + 1:]
+    nbytes = int(lib().gsr_prune_workspace(P))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _check(lib().gsr_prune_mark(P, _ptr(xyz), _ptr(scaling_raw), _ptr(rotation_raw), _ptr(opacity_raw), _ptr(drop),
+                                float(min_opacity), float(max_scale), int(bool(drop_nonfinite)), _ptr(reasons),
+                                C.c_void_p(row_map.data_ptr()), C.c_void_p(counts.data_ptr()), _ptr(ws), nbytes,
+                                _stream()))
+    return (reasons, row_map, counts, both) if packed else (reasons, row_map, counts)
+
+
+def prune_compact(src, dst, reasons, row_map):
+    """dst[k][row_map[i]] = src[k][i] for the rows with reasons[i] == 0, up to 18 tensors in ONE launch
+    (include/gsraster.h, gsr_prune_compact).  src[k]: [P, ...] f32; dst[k]: a buffer of its own with the same row shape
+    and at least row_map[P] rows, whose further rows are not written."""
+    n = len(src)
+    assert n == len(dst)
+    P = int(reasons.numel())
+    widths = []
+    for s, d in zip(src, dst):
+        assert s.is_cuda and s.is_contiguous() and s.dtype == torch.float32 and int(s.size(0)) == P
+        assert d.is_cuda and d.is_contiguous() and d.dtype == torch.float32 and d.shape[1:] == s.shape[1:]
+        assert s.numel() == 0 or d.numel() == 0 or s.data_ptr() != d.data_ptr()
+        widths.append(int(s[0].numel()) if P else 0)
+    assert reasons.is_cuda and reasons.dtype == torch.uint8 and reasons.is_contiguous()
+    assert row_map.is_cuda and row_map.dtype == torch.int32 and row_map.is_contiguous() and row_map.numel() == P + 1
+    VP = C.c_void_p * max(n, 1)
+    arr = lambda ts: VP(*[t.data_ptr() if t.numel() else None for t in ts])  # noqa: E731
+    _check(lib().gsr_prune_compact(P, n, arr(src), arr(dst), (C.c_int * max(n, 1))(*widths), _ptr(reasons),
+                                   C.c_void_p(row_map.data_ptr()), _stream()))

@@ -131,7 +131,8 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_activate_backward", "k_adam", "k_loss_forward", "k_loss_finalize", "k_loss_backward", "k_init_gaussians", "k_pack_ply_rows", "k_model_step", "k_tile_order", "k_live_sat", "k_compact_near",
     "k_simi_nearest", "k_simi_points", "k_simi_grads",
     "k_delta_project", "k_delta_sample", "k_delta_scatter", "k_delta_convert",
-    "k_metrics_forward", "k_metrics_finalize", "k_pack_image_u8", "k_pack_depth_u8"};
+    "k_metrics_forward", "k_metrics_finalize", "k_pack_image_u8", "k_pack_depth_u8",
+    "k_prune_mark", "k_prune_scan", "k_prune_rank", "k_prune_compact"};
 
 extern "C" {
 
@@ -1722,6 +1723,54 @@ int gsr_pack_ply_rows(int P, int M, const float* xyz, const float* features_dc, 
     return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
   HIP_TRY(launch_pack_ply_rows(P, M, xyz, features_dc, features_rest, opacity, scaling, rotation, rows,
                                (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+size_t gsr_prune_workspace(int P) {
+  if (P <= 0 || P > GSR_PRUNE_MAX_ROWS) return 0;
+  return prune_workspace_bytes(P);
+}
+
+int gsr_prune_mark(int P, const float* xyz, const float* scaling_raw, const float* rotation_raw,
+                   const float* opacity_raw, const unsigned char* drop, float min_opacity, float max_scale,
+                   int drop_nonfinite, unsigned char* reasons, int* row_map, int* counts5, char* workspace,
+                   size_t workspace_bytes, void* stream_) {
+  g_err[0] = 0;
+  if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (!row_map || !counts5) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (P > 0 && (!xyz || !scaling_raw || !rotation_raw || !opacity_raw || !reasons || !workspace))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (((uintptr_t)xyz | (uintptr_t)scaling_raw | (uintptr_t)rotation_raw | (uintptr_t)opacity_raw |
+       (uintptr_t)row_map | (uintptr_t)counts5 | (uintptr_t)workspace) & 3u)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "misaligned pointer: float and int32 arrays need 4-byte alignment");
+  if (workspace_bytes < prune_workspace_bytes(P))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes", prune_workspace_bytes(P));
+  HIP_TRY(launch_prune_mark(P, xyz, scaling_raw, rotation_raw, opacity_raw, drop, min_opacity, max_scale,
+                            drop_nonfinite ? 1 : 0, reasons, row_map, counts5, workspace, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+int gsr_prune_compact(int P, int n_tensors, const float* const* src, float* const* dst, const int* widths,
+                      const unsigned char* reasons, const int* row_map, void* stream_) {
+  g_err[0] = 0;
+  if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (n_tensors < 0 || n_tensors > PRUNE_MAX_TENSORS)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "bad tensor count: at most %d", PRUNE_MAX_TENSORS);
+  if (n_tensors > 0 && !widths) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  for (int k = 0; k < n_tensors; k++)
+    if (widths[k] < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad row width (tensor %d)", k);
+  if (n_tensors > 0 && prune_compact_blocks(P, n_tensors, widths) > 0x7fffffffull)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "model too large for one compaction launch");
+  if (P == 0 || n_tensors == 0) return GSR_OK;
+  if (!src || !dst || !reasons || !row_map) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  for (int k = 0; k < n_tensors; k++)
+    if (widths[k] > 0 && (!src[k] || !dst[k])) return fail(GSR_ERR_INVALID_ARGUMENT, "null tensor pointer (tensor %d)", k);
+  if ((uintptr_t)row_map & 3u)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "misaligned pointer: float and int32 arrays need 4-byte alignment");
+  for (int k = 0; k < n_tensors; k++)
+    if (widths[k] > 0 && (((uintptr_t)src[k] | (uintptr_t)dst[k]) & 3u))
+      return fail(GSR_ERR_INVALID_ARGUMENT, "misaligned pointer: float and int32 arrays need 4-byte alignment (tensor %d)", k);
+  HIP_TRY(launch_prune_compact(P, n_tensors, src, dst, widths, reasons, row_map, (hipStream_t)stream_));
   return GSR_OK;
 }
 

@@ -467,6 +467,16 @@ hipError_t launch_model_step(int P, int M, float* const* params, float* const* e
 hipError_t launch_adam(int n, float* const* params, float* const* grads, float* const* exp_avg,
                        float* const* exp_avg_sq, const size_t* numel, const float* lr, double beta1, double beta2,
                        double eps, int step, int zero_grads, hipStream_t s);
+// prune.hip (in-place pruning: the drop rule, the stable row map, the out-of-place compaction of up to 18 tensors)
+constexpr int PRUNE_MAX_TENSORS = 18;
+size_t prune_workspace_bytes(int P);
+hipError_t launch_prune_mark(int P, const float* xyz, const float* scaling_raw, const float* rotation_raw,
+                             const float* opacity_raw, const unsigned char* drop, float min_opacity, float max_scale,
+                             int drop_nonfinite, unsigned char* reasons, int* row_map, int* counts5, char* workspace,
+                             hipStream_t s);
+unsigned long long prune_compact_blocks(int P, int n, const int* widths);
+hipError_t launch_prune_compact(int P, int n, const float* const* src, float* const* dst, const int* widths,
+                                const unsigned char* reasons, const int* row_map, hipStream_t s);
 
 inline int sort_passes(int end_bit) { return (end_bit + 7) / 8; }
 // digit width: the key bits are split evenly over the passes (13 tile bits -> 7 + 6, 32 depth bits -> 4 x 8)
@@ -480,7 +490,8 @@ enum KernelId {
   K_DSORT_SCATTER, K_ACTIVATE, K_ACTIVATE_BWD, K_ADAM, K_LOSS_FWD, K_LOSS_FINALIZE, K_LOSS_BWD, K_INIT_GAUSSIANS, K_PACK_PLY, K_MODEL_STEP, K_TILE_ORDER, K_LIVE_SAT, K_COMPACT_NEAR,
   K_SIMI_NEAREST, K_SIMI_POINTS, K_SIMI_GRADS,
   K_DELTA_PROJECT, K_DELTA_SAMPLE, K_DELTA_SCATTER, K_DELTA_CONVERT,
-  K_METRICS_FWD, K_METRICS_FINALIZE, K_PACK_IMAGE_U8, K_PACK_DEPTH_U8, K_COUNT
+  K_METRICS_FWD, K_METRICS_FINALIZE, K_PACK_IMAGE_U8, K_PACK_DEPTH_U8,
+  K_PRUNE_MARK, K_PRUNE_SCAN, K_PRUNE_RANK, K_PRUNE_COMPACT, K_COUNT
 };
 void prof_begin(int id, hipStream_t s);
 void prof_end(hipStream_t s);
@@ -497,6 +508,11 @@ struct ProfScope {  // records a start/stop event pair around the launches in it
   }
   ~ProfScope() { if (on) prof_end(s); }
 };
+
+// The activations of the opacity leaf as k_activate and k_model_step hand it to the rasterizer (optimizer.hip) and as the
+// prune rule tests it (prune.hip): full-precision expf -- these kernels are HBM-bound, and the activated values feed the
+// exact-match stages downstream.
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // getRect (reference auxiliary.h:39-46): tile rectangle [x0,x1) x [y0,y1) touched by a splat of
 // integer pixel radius `radius` centred at (px,py); float arithmetic with truncating casts, exactly

@@ -86,6 +86,13 @@ class VoxelIndex {
   // `device` without waiting.  false where the reference returns false (no point left; also: no row to compare with).
   bool select(const std::unordered_map<std::size_t, torch::Tensor>& losses, torch::Tensor& points, torch::Tensor& sel,
               int64_t max_points = 500, torch::Device device = torch::kCUDA) const;
+  // Follows a stable compaction of the model's rows (prune_mark / FusedAdam::prune): row_map_cpu [P+1] integers on the
+  // host, the exclusive prefix sum of "kept".  (first, count) becomes (row_map[first], row_map[first + count] -
+  // row_map[first]); a voxel that loses all its rows stays registered with count 0, so adding its key again still
+  // throws.  Throws, and changes nothing, when a range ends beyond P.
+  void remap(const torch::Tensor& row_map_cpu);
+  // (first_row, count) of a key; false when the key is unknown
+  bool get(std::size_t key, int64_t& first_row, int64_t& count) const;
   std::size_t size() const { return ranges_.size(); }
   bool contains(std::size_t key) const { return ranges_.count(key) > 0; }
 
@@ -122,6 +129,11 @@ class FusedAdam {
   // GaussianModel::cat_tensors_to_optimizer (gaussian.cu:451-472): the leaf at `index` was replaced by a longer tensor
   // whose first rows are the old ones; its moments grow by zero rows
   void replace_param(size_t index, torch::Tensor new_param);
+  // GaussianModel::prune_optimizer (gaussian.cu:430-449) for all groups in ONE launch: every parameter and both of
+  // its moments are replaced by their compacted tensors -- the rows with reasons[i] == 0, in order, P_new of them
+  // (reasons, row_map: from prune_mark; P_new = row_map[P], which the caller has fetched).  The new parameters are
+  // fresh leaves that require grad as the old ones did; step_count() is unchanged.
+  void prune(const torch::Tensor& reasons, const torch::Tensor& row_map, int64_t P_new);
   int64_t step_count() const { return step_; }
   const std::vector<torch::Tensor>& params() const { return params_; }
   const std::vector<torch::Tensor>& exp_avg() const { return m_; }
@@ -133,6 +145,24 @@ class FusedAdam {
   double beta1_, beta2_, eps_;
   int64_t step_ = 0;
 };
+
+// ---- in-place pruning (an extension: the reference carries prune_optimizer and never calls it) ------------------------
+// The drop rule and the row map of the stable compaction on the kernels of csrc/prune.hip (include/gsraster.h,
+// gsr_prune_mark): a row leaves when sigmoid(_opacity) < min_opacity, any exp(_scaling) > max_scale, (drop_nonfinite) any
+// of the four tensors is NaN / +-Inf, or drop ([P] bool / uint8 on the device, may be undefined) marks it.  All device
+// tensors, nothing waits: reasons [P] uint8 (0 = keep), row_map [P+1] int32 (row_map[P] = P'), counts [5] int32 =
+// {P', opacity, scale, non-finite, mask}.  (Like delta_depth_loss and image_metrics, these entry points are not part of
+// the oracle/ref_link link check, which keeps its twenty entry points.)
+struct PruneMarks {
+  torch::Tensor reasons, row_map, counts;
+};
+PruneMarks prune_mark(const torch::Tensor& xyz, const torch::Tensor& scaling_raw, const torch::Tensor& rotation_raw,
+                      const torch::Tensor& opacity_raw, float min_opacity = 1.0f / 255.0f, float max_scale = 0.3f,
+                      bool drop_nonfinite = true, const torch::Tensor& drop = torch::Tensor());
+// tensors[k][reasons == 0] for up to any number of [P, ...] f32 device tensors, eighteen per launch: new [P_new, ...]
+// tensors
+std::vector<torch::Tensor> prune_rows(const std::vector<torch::Tensor>& tensors, const torch::Tensor& reasons,
+                                      const torch::Tensor& row_map, int64_t P_new);
 
 // ---- row 4: map growth and PLY export ---------------------------------------------------------------------------
 // The tensor construction of GaussianModel::addNewPointcloud (src/gs/gaussian.cu:241-313) for n new points -- xyz

@@ -16,8 +16,7 @@
 
 namespace gsr {
 
-// full-precision expf: these kernels are HBM-bound, and exp(_scaling) feeds the exact-match stages downstream
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+// (sigmoidf_ and the full-precision expf: gsr_internal.hpp -- shared with the prune rule of prune.hip)
 
 __global__ __launch_bounds__(256) void k_activate(const int P, const int M, const float* __restrict__ scaling_raw,
                                                   const float* __restrict__ rotation_raw,

@@ -1,0 +1,287 @@
+// prune.hip -- in-place pruning of the model: rows that are dead to the rasterizer for good are marked, the surviving
+// rows get their new row numbers, and the leaves and their Adam moments are compacted (the shrinking half of the
+// optimiser-state surgery: GaussianModel::prune_optimizer, reference src/gs/gaussian.cu:430-449 -- an index_select of a
+// leaf and of both of its moments, per group; the reference never calls it, so this is an extension).
+//
+// Removal is a STABLE stream compaction: survivors keep their relative order, so a voxel's row range stays a range
+// (VoxelIndex) and the rasterizer's depth ties, which are broken by ascending row number, fall as before.
+//
+// Launches of one prune of a whole model, whatever P: FOUR.
+//   k_prune_mark     one thread per row: the drop rule -> reasons[P]; per-workgroup totals of "kept" and of each reason
+//   k_prune_scan     ONE workgroup: exclusive scan of the per-workgroup kept totals (in place), the reason totals,
+//                    counts[5] and row_map[P] = P'
+//   k_prune_rank     one thread per row: row_map[i] = workgroup base + rank inside the workgroup (ballot / popcount)
+//   k_prune_compact  one thread per SOURCE float of the virtual concatenation of up to 18 tensors:
+//                    dst[row_map[i]] = src[i] where reasons[i] == 0
+// No workgroup waits for another (no look-back chain, no spin), and no atomics: row_map and the counts are the same
+// whatever the order the workgroups run in.  Plain vector loads and stores only.
+//
+// The compaction is out of place on purpose: an in-place stable compaction races between workgroups (one writes the
+// rows another has yet to read).  Rows [P', ...) of a destination are not written.
+#include "gsr_internal.hpp"
+
+namespace gsr {
+
+constexpr int PRUNE_BLOCK = 256;      // rows per workgroup of k_prune_mark / k_prune_rank (4 waves)
+constexpr int PRUNE_WAVES = PRUNE_BLOCK / 64;
+constexpr int PRUNE_SCAN_ITEMS = 4;   // consecutive workgroup totals per thread of k_prune_scan: 1024 per pass of its loop
+constexpr int COMPACT_ITEMS = 4;      // floats per thread of k_prune_compact, 256 apart: 1024 consecutive floats per workgroup
+constexpr int COMPACT_TILE = 256 * COMPACT_ITEMS;
+
+// reasons[i]: 0 = keep
+constexpr unsigned R_OPACITY = 1u, R_SCALE = 2u, R_NONFINITE = 4u, R_MASK = 8u;
+
+inline size_t prune_blocks(int P) { return ((size_t)P + PRUNE_BLOCK - 1) / PRUNE_BLOCK; }
+// [5][nblocks] int32: [0] kept rows per workgroup -> their exclusive scan; [1..4] rows per workgroup with reason bit 0..3
+size_t prune_workspace_bytes(int P) { return P > 0 ? 5 * prune_blocks(P) * sizeof(int) : 0; }
+
+__device__ __forceinline__ bool nonfinite_(float x) { return (__float_as_uint(x) & 0x7F800000u) == 0x7F800000u; }
+
+// The activated values are those of k_activate / k_model_step bit for bit (same expf, same sigmoidf_), so "dropped for
+// scale" is exactly "k_preprocess' scale cull fires at scale_modifier 1", and the comparisons are the rasterizer's:
+// a value ON a threshold is kept (the culls are strict), a NaN compares false in both tests (hence the third bit).
+__global__ __launch_bounds__(PRUNE_BLOCK) void k_prune_mark(const int P, const float* __restrict__ xyz,
+                                                            const float* __restrict__ scaling_raw,
+                                                            const float* __restrict__ rotation_raw,
+                                                            const float* __restrict__ opacity_raw,
+                                                            const unsigned char* __restrict__ drop,
+                                                            const float min_opacity, const float max_scale,
+                                                            const int drop_nonfinite, unsigned char* __restrict__ reasons,
+                                                            int* __restrict__ totals, const int nblocks) {
+  __shared__ int sh[PRUNE_WAVES][5];
+  const int i = blockIdx.x * PRUNE_BLOCK + threadIdx.x;
+  const bool in = i < P;
+  unsigned r = 0;
+  if (in) {
+    const size_t i3 = 3 * (size_t)i, i4 = 4 * (size_t)i;
+    const float o = opacity_raw[i];
+    const float s0 = scaling_raw[i3], s1 = scaling_raw[i3 + 1], s2 = scaling_raw[i3 + 2];
+    if (sigmoidf_(o) < min_opacity) r |= R_OPACITY;
+    if (expf(s0) > max_scale || expf(s1) > max_scale || expf(s2) > max_scale) r |= R_SCALE;
+    if (drop_nonfinite) {
+      bool bad = nonfinite_(o) || nonfinite_(s0) || nonfinite_(s1) || nonfinite_(s2);
+#pragma unroll
+      for (int k = 0; k < 3; k++) bad = bad || nonfinite_(xyz[i3 + k]);
+#pragma unroll
+      for (int k = 0; k < 4; k++) bad = bad || nonfinite_(rotation_raw[i4 + k]);
+      if (bad) r |= R_NONFINITE;
+    }
+    if (drop && drop[i]) r |= R_MASK;
+    reasons[i] = (unsigned char)r;
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int n_keep = __popcll(__ballot(in && r == 0));
+  int n_r[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) n_r[k] = __popcll(__ballot((r >> k) & 1u));
+  if (lane == 0) {
+    sh[wave][0] = n_keep;
+#pragma unroll
+    for (int k = 0; k < 4; k++) sh[wave][1 + k] = n_r[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    int t = 0;
+#pragma unroll
+    for (int w = 0; w < PRUNE_WAVES; w++) t += sh[w][threadIdx.x];
+    totals[(size_t)threadIdx.x * nblocks + blockIdx.x] = t;
+  }
+}
+
+// sum over the workgroup (256 threads) of v, returned to every thread; `sh`: PRUNE_WAVES ints
+__device__ __forceinline__ int block_sum(int v, int* sh) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  __syncthreads();  // (sh may still be read from the previous use)
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int t = 0;
+#pragma unroll
+  for (int w = 0; w < PRUNE_WAVES; w++) t += sh[w];
+  return t;
+}
+
+// ONE workgroup.  totals[0][.] -> exclusive scan in place, 1024 workgroup totals per pass of the loop with the running
+// sum carried in a register; then the four reason totals, counts5 and row_map[P].  nblocks == 0 (P == 0) writes zeros.
+__global__ __launch_bounds__(PRUNE_BLOCK) void k_prune_scan(int* __restrict__ totals, const int nblocks,
+                                                            int* __restrict__ counts5, int* __restrict__ row_map_end) {
+  __shared__ int sh[PRUNE_WAVES];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  int carry = 0;
+  for (int base = 0; base < nblocks; base += PRUNE_BLOCK * PRUNE_SCAN_ITEMS) {  // (uniform trip count)
+    const int j0 = base + (int)threadIdx.x * PRUNE_SCAN_ITEMS;
+    int v[PRUNE_SCAN_ITEMS], mine = 0;
+#pragma unroll
+    for (int k = 0; k < PRUNE_SCAN_ITEMS; k++) {
+      v[k] = j0 + k < nblocks ? totals[j0 + k] : 0;
+      mine += v[k];
+    }
+    int incl = mine;  // inclusive scan of the threads' sums inside the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(incl, d);
+      if (lane >= d) incl += up;
+    }
+    __syncthreads();  // the previous pass has read sh
+    if (lane == 63) sh[wave] = incl;
+    __syncthreads();
+    int before = carry, all = 0;
+#pragma unroll
+    for (int w = 0; w < PRUNE_WAVES; w++) {
+      if (w < wave) before += sh[w];
+      all += sh[w];
+    }
+    int run = before + incl - mine;
+#pragma unroll
+    for (int k = 0; k < PRUNE_SCAN_ITEMS; k++) {
+      if (j0 + k < nblocks) totals[j0 + k] = run;
+      run += v[k];
+    }
+    carry += all;
+  }
+  int n_r[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    int t = 0;
+    for (int j = threadIdx.x; j < nblocks; j += PRUNE_BLOCK) t += totals[(size_t)(1 + k) * nblocks + j];
+    n_r[k] = block_sum(t, sh);
+  }
+  if (threadIdx.x == 0) {
+    counts5[0] = carry;
+#pragma unroll
+    for (int k = 0; k < 4; k++) counts5[1 + k] = n_r[k];
+    *row_map_end = carry;
+  }
+}
+
+__global__ __launch_bounds__(PRUNE_BLOCK) void k_prune_rank(const int P, const unsigned char* __restrict__ reasons,
+                                                            const int* __restrict__ bases, int* __restrict__ row_map) {
+  __shared__ int sh[PRUNE_WAVES];
+  const int i = blockIdx.x * PRUNE_BLOCK + threadIdx.x;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const bool keep = i < P && reasons[i] == 0;
+  const unsigned long long b = __ballot(keep);
+  const int rank = __popcll(b & ((1ull << lane) - 1ull));
+  if (lane == 0) sh[wave] = __popcll(b);
+  __syncthreads();
+  int before = bases[blockIdx.x];
+#pragma unroll
+  for (int w = 0; w < PRUNE_WAVES; w++)
+    if (w < wave) before += sh[w];
+  if (i < P) row_map[i] = before + rank;
+}
+
+struct CompactArgs {
+  const float* src[PRUNE_MAX_TENSORS];
+  float* dst[PRUNE_MAX_TENSORS];
+  unsigned long long numel[PRUNE_MAX_TENSORS];  // P * width
+  unsigned end[PRUNE_MAX_TENSORS];              // cumulative count of workgroups (COMPACT_TILE floats each)
+  unsigned width[PRUNE_MAX_TENSORS];            // floats per row (> 0: empty tensors are left out on the host)
+  int n;
+  const unsigned char* reasons;
+  const int* row_map;
+};
+
+// Thread per source float: a wave instruction reads 64 consecutive floats and writes them, as far as they are kept,
+// to consecutive addresses again (a kept run of rows stays a run; the write only shifts down).  A workgroup takes 1024
+// consecutive floats of ONE tensor (the tensor is looked up once, on the scalar unit); its first float's row and column
+// take one division, the 1024 floats behind it 32-bit arithmetic on small numbers.  The four loads of a thread are
+// issued before the first store depends on them.
+__global__ __launch_bounds__(256) void k_prune_compact(const CompactArgs a) {
+  int t = 0;
+  unsigned start = 0;
+#pragma unroll
+  for (int k = 0; k < PRUNE_MAX_TENSORS; k++) {
+    if (k < a.n && blockIdx.x >= a.end[k]) { t = k + 1; start = a.end[k]; }
+  }
+  if (t >= a.n) return;
+  const unsigned long long numel = a.numel[t];
+  const unsigned w = a.width[t];
+  const float* __restrict__ src = a.src[t];
+  float* __restrict__ dst = a.dst[t];
+  const unsigned long long e0 = (unsigned long long)(blockIdx.x - start) * COMPACT_TILE;
+  unsigned long long row0;
+  unsigned c0;
+  if (numel <= 0xFFFFFFFFull) { const uint32_t q = (uint32_t)e0 / w; row0 = q; c0 = (uint32_t)e0 - q * w; }
+  else { row0 = e0 / w; c0 = (unsigned)(e0 - row0 * w); }
+  float v[COMPACT_ITEMS];
+  unsigned long long out[COMPACT_ITEMS];
+  bool keep[COMPACT_ITEMS];
+#pragma unroll
+  for (int k = 0; k < COMPACT_ITEMS; k++) {
+    const unsigned local = (unsigned)k * 256u + threadIdx.x;
+    const unsigned long long e = e0 + local;
+    keep[k] = false;
+    v[k] = 0.f;
+    out[k] = 0;
+    if (e < numel) {
+      const unsigned l = c0 + local;  // < width + COMPACT_TILE
+      const unsigned dr = l / w, c = l - dr * w;
+      const unsigned long long i = row0 + dr;  // < P
+      v[k] = src[e];
+      keep[k] = a.reasons[i] == 0;
+      out[k] = (unsigned long long)(unsigned)a.row_map[i] * w + c;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < COMPACT_ITEMS; k++)
+    if (keep[k]) dst[out[k]] = v[k];
+}
+
+hipError_t launch_prune_mark(int P, const float* xyz, const float* scaling_raw, const float* rotation_raw,
+                             const float* opacity_raw, const unsigned char* drop, float min_opacity, float max_scale,
+                             int drop_nonfinite, unsigned char* reasons, int* row_map, int* counts5, char* workspace,
+                             hipStream_t s) {
+  const int nblocks = (int)prune_blocks(P);
+  int* totals = reinterpret_cast<int*>(workspace);
+  if (nblocks) {
+    ProfScope ps(K_PRUNE_MARK, s);
+    hipLaunchKernelGGL(k_prune_mark, dim3(nblocks), dim3(PRUNE_BLOCK), 0, s, P, xyz, scaling_raw, rotation_raw,
+                       opacity_raw, drop, min_opacity, max_scale, drop_nonfinite, reasons, totals, nblocks);
+  }
+  {
+    ProfScope ps(K_PRUNE_SCAN, s);
+    hipLaunchKernelGGL(k_prune_scan, dim3(1), dim3(PRUNE_BLOCK), 0, s, totals, nblocks, counts5, row_map + P);
+  }
+  if (nblocks) {
+    ProfScope ps(K_PRUNE_RANK, s);
+    hipLaunchKernelGGL(k_prune_rank, dim3(nblocks), dim3(PRUNE_BLOCK), 0, s, P, reasons, totals, row_map);
+  }
+  return hipGetLastError();
+}
+
+// workgroups of the one compaction launch (the entry point refuses a model that needs more than a grid holds)
+unsigned long long prune_compact_blocks(int P, int n, const int* widths) {
+  unsigned long long blocks = 0;
+  for (int k = 0; k < n; k++)
+    if (widths[k] > 0) blocks += ((unsigned long long)P * (unsigned long long)widths[k] + COMPACT_TILE - 1) / COMPACT_TILE;
+  return blocks;
+}
+
+hipError_t launch_prune_compact(int P, int n, const float* const* src, float* const* dst, const int* widths,
+                                const unsigned char* reasons, const int* row_map, hipStream_t s) {
+  CompactArgs a;
+  a.n = 0;
+  a.reasons = reasons;
+  a.row_map = row_map;
+  unsigned long long cum = 0;
+  for (int k = 0; k < PRUNE_MAX_TENSORS; k++) {
+    a.src[k] = nullptr; a.dst[k] = nullptr; a.numel[k] = 0; a.width[k] = 1; a.end[k] = 0;
+  }
+  for (int k = 0; k < n; k++) {
+    if (widths[k] <= 0) continue;  // e.g. _features_rest at M = 1: nothing to move
+    const int j = a.n++;
+    a.src[j] = src[k]; a.dst[j] = dst[k];
+    a.width[j] = (unsigned)widths[k];
+    a.numel[j] = (unsigned long long)P * (unsigned long long)widths[k];
+    cum += (a.numel[j] + COMPACT_TILE - 1) / COMPACT_TILE;
+    a.end[j] = (unsigned)cum;
+  }
+  for (int k = a.n; k < PRUNE_MAX_TENSORS; k++) a.end[k] = (unsigned)cum;
+  if (cum == 0) return hipSuccess;
+  ProfScope ps(K_PRUNE_COMPACT, s);
+  hipLaunchKernelGGL(k_prune_compact, dim3((unsigned)cum), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace gsr

@@ -462,6 +462,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return py::make_tuple(points, sel);
            },
            py::arg("losses"), py::arg("max_points") = 500, py::arg("device") = "cuda")
+      .def("remap", &nx::VoxelIndex::remap, py::arg("row_map"))
+      .def("get",
+           [](const nx::VoxelIndex& self, std::size_t key) -> py::object {
+             int64_t first = 0, count = 0;
+             if (!self.get(key, first, count)) return py::none();
+             return py::make_tuple(first, count);
+           })
       .def("__len__", &nx::VoxelIndex::size)
       .def("__contains__", &nx::VoxelIndex::contains);
   n.def("activate", [](torch::Tensor s, torch::Tensor r, torch::Tensor o, torch::Tensor dc, torch::Tensor rest) {
@@ -479,10 +486,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
              return std::make_tuple(a.scaling, a.rotation, a.opacity, a.features);
            })
       .def("replace_param", &nx::FusedAdam::replace_param)
+      .def("prune", &nx::FusedAdam::prune, py::arg("reasons"), py::arg("row_map"), py::arg("P_new"))
       .def("step_count", &nx::FusedAdam::step_count)
       .def("params", &nx::FusedAdam::params)
       .def("exp_avg", &nx::FusedAdam::exp_avg)
       .def("exp_avg_sq", &nx::FusedAdam::exp_avg_sq);
+  n.def("prune_mark",
+        [opt](torch::Tensor xyz, torch::Tensor s, torch::Tensor r, torch::Tensor o, float min_opacity, float max_scale,
+              bool drop_nonfinite, py::object drop) {
+          const nx::PruneMarks p = nx::prune_mark(xyz, s, r, o, min_opacity, max_scale, drop_nonfinite, opt(drop));
+          return std::make_tuple(p.reasons, p.row_map, p.counts);
+        },
+        py::arg("xyz"), py::arg("scaling_raw"), py::arg("rotation_raw"), py::arg("opacity_raw"),
+        py::arg("min_opacity") = 1.0f / 255.0f, py::arg("max_scale") = 0.3f, py::arg("drop_nonfinite") = true,
+        py::arg("drop") = py::none());
+  n.def("prune_rows", &nx::prune_rows, py::arg("tensors"), py::arg("reasons"), py::arg("row_map"), py::arg("P_new"));
   n.def("init_gaussians", &nx::init_gaussians);
   n.def("pack_ply_rows", &nx::pack_ply_rows);
   n.def("write_ply", &nx::write_ply);

@@ -12,6 +12,7 @@
 //   Save_ply / Write_output_ply                            src/gs/gaussian.cu:494-573
 //   compute_min_distance + the selection of calcSimiLoss   src/gs/gaussian.cu:87-114, 201-239
 //   calcDeltaSimi + the loop body around it                src/gs/gaussian.cu:116-199, lioOptimization.cpp:1780-1801
+//   prune_optimizer (carried, never called there)          src/gs/gaussian.cu:430-449
 //   psnr + ssim + tensor2CvMat3X / 2X of saveRender        loss_utils.cuh:89-93, lioOptimization.cpp:2113-2164, 2198-2231
 #include "gsr_torch_next.hpp"
 
@@ -306,6 +307,31 @@ int64_t VoxelIndex::add(const std::vector<std::size_t>& keys, const std::vector<
   return row;
 }
 
+void VoxelIndex::remap(const torch::Tensor& row_map_cpu) {
+  if (!row_map_cpu.defined() || row_map_cpu.numel() == 0)
+    throw std::invalid_argument("VoxelIndex::remap: row_map has P + 1 entries");
+  const torch::Tensor rm = row_map_cpu.to(torch::kCPU, torch::kInt64).reshape({-1}).contiguous();
+  const int64_t* m = rm.data_ptr<int64_t>();
+  const int64_t P = rm.numel() - 1;
+  for (const auto& kv : ranges_)
+    if (kv.second.first < 0 || kv.second.first + kv.second.second > P)
+      throw std::invalid_argument("VoxelIndex::remap: a voxel's rows end at " +
+                                  std::to_string(kv.second.first + kv.second.second) + ", row_map covers " +
+                                  std::to_string(P) + " rows");
+  for (auto& kv : ranges_) {
+    const int64_t first = m[kv.second.first], end = m[kv.second.first + kv.second.second];
+    kv.second = std::make_pair(first, end - first);
+  }
+}
+
+bool VoxelIndex::get(std::size_t key, int64_t& first_row, int64_t& count) const {
+  const auto it = ranges_.find(key);
+  if (it == ranges_.end()) return false;
+  first_row = it->second.first;
+  count = it->second.second;
+  return true;
+}
+
 bool VoxelIndex::select(const std::unordered_map<std::size_t, torch::Tensor>& losses, torch::Tensor& points,
                         torch::Tensor& sel, int64_t max_points, torch::Device device) const {
   std::vector<std::size_t> hit;
@@ -420,6 +446,98 @@ void FusedAdam::replace_param(size_t index, torch::Tensor new_param) {
   grow(m_[index]);
   grow(v_[index]);
   params_[index] = std::move(new_param);
+}
+
+PruneMarks prune_mark(const torch::Tensor& xyz, const torch::Tensor& scaling_raw, const torch::Tensor& rotation_raw,
+                      const torch::Tensor& opacity_raw, float min_opacity, float max_scale, bool drop_nonfinite,
+                      const torch::Tensor& drop) {
+  torch::NoGradGuard no_grad;
+  const torch::Tensor x = dev_f32(xyz, "xyz"), s = dev_f32(scaling_raw, "_scaling"), r = dev_f32(rotation_raw, "_rotation"),
+                      o = dev_f32(opacity_raw, "_opacity");
+  const int64_t P = x.size(0);
+  if (x.numel() != 3 * P || s.numel() != 3 * P || r.numel() != 4 * P || o.numel() != P)
+    throw std::invalid_argument("prune_mark: xyz [P,3], scaling [P,3], rotation [P,4], opacity [P,1]");
+  torch::Tensor mask;
+  if (drop.defined()) {
+    if (!drop.is_cuda() || (drop.scalar_type() != torch::kBool && drop.scalar_type() != torch::kByte) || drop.numel() != P)
+      throw std::invalid_argument("prune_mark: drop is a bool or uint8 device tensor of P entries");
+    mask = drop.contiguous();
+  }
+  const auto bytes = x.options().dtype(torch::kByte), ints = x.options().dtype(torch::kInt32);
+  PruneMarks out{torch::empty({P}, bytes), torch::empty({P + 1}, ints), torch::empty({5}, ints)};
+  const size_t nbytes = gsr_prune_workspace(static_cast<int>(P));
+  torch::Tensor ws = torch::empty({static_cast<long long>(nbytes ? nbytes : 1)}, bytes);
+  check(gsr_prune_mark(static_cast<int>(P), fp(x), fp(s), fp(r), fp(o),
+                       mask.defined() && P ? static_cast<const unsigned char*>(mask.data_ptr()) : nullptr, min_opacity,
+                       max_scale, drop_nonfinite ? 1 : 0, P ? out.reasons.data_ptr<unsigned char>() : nullptr,
+                       out.row_map.data_ptr<int>(), out.counts.data_ptr<int>(), reinterpret_cast<char*>(ws.data_ptr()),
+                       nbytes, current_stream()),
+        "gsr_prune_mark");
+  return out;
+}
+
+namespace {
+// dst[k][row_map[i]] = src[k][i] where reasons[i] == 0, at most eighteen tensors: one launch
+void compact18(const std::vector<torch::Tensor>& src, const std::vector<torch::Tensor>& dst, const torch::Tensor& reasons,
+               const torch::Tensor& row_map) {
+  const int64_t P = reasons.numel();
+  if (!reasons.is_cuda() || reasons.scalar_type() != torch::kByte || !reasons.is_contiguous() || !row_map.is_cuda() ||
+      row_map.scalar_type() != torch::kInt32 || !row_map.is_contiguous() || row_map.numel() != P + 1)
+    throw std::invalid_argument("prune: reasons [P] uint8 and row_map [P+1] int32 on the device, from prune_mark");
+  const float* s[18];
+  float* d[18];
+  int w[18];
+  const int n = static_cast<int>(src.size());
+  for (int k = 0; k < n; k++) {
+    if (src[k].size(0) != P) throw std::invalid_argument("prune: a tensor does not have P rows");
+    s[k] = fp(src[k]); d[k] = fp(dst[k]);
+    w[k] = P ? static_cast<int>(src[k].numel() / P) : 0;
+  }
+  check(gsr_prune_compact(static_cast<int>(P), n, s, d, w, P ? reasons.data_ptr<unsigned char>() : nullptr,
+                          row_map.data_ptr<int>(), current_stream()),
+        "gsr_prune_compact");
+}
+
+torch::Tensor rows_like(const torch::Tensor& t, int64_t rows) {
+  std::vector<int64_t> shape = t.sizes().vec();
+  shape[0] = rows;
+  return torch::empty(shape, t.options().requires_grad(false));
+}
+}  // namespace
+
+std::vector<torch::Tensor> prune_rows(const std::vector<torch::Tensor>& tensors, const torch::Tensor& reasons,
+                                      const torch::Tensor& row_map, int64_t P_new) {
+  torch::NoGradGuard no_grad;
+  std::vector<torch::Tensor> out;
+  for (size_t b = 0; b < tensors.size(); b += 18) {
+    std::vector<torch::Tensor> src, dst;
+    for (size_t k = b; k < std::min(tensors.size(), b + 18); k++) {
+      src.push_back(dev_f32(tensors[k], "tensor").detach());
+      dst.push_back(rows_like(src.back(), P_new));
+    }
+    compact18(src, dst, reasons, row_map);
+    out.insert(out.end(), dst.begin(), dst.end());
+  }
+  return out;
+}
+
+void FusedAdam::prune(const torch::Tensor& reasons, const torch::Tensor& row_map, int64_t P_new) {
+  torch::NoGradGuard no_grad;
+  if (3 * params_.size() > 18) throw std::invalid_argument("FusedAdam::prune: at most six parameter tensors");
+  std::vector<torch::Tensor> src;
+  for (size_t k = 0; k < params_.size(); k++) {
+    src.push_back(params_[k]);
+    src.push_back(m_[k]);
+    src.push_back(v_[k]);
+  }
+  const std::vector<torch::Tensor> dst = prune_rows(src, reasons, row_map, P_new);
+  for (size_t k = 0; k < params_.size(); k++) {
+    const bool rg = params_[k].requires_grad();
+    params_[k] = dst[3 * k];
+    params_[k].set_requires_grad(rg);
+    m_[k] = dst[3 * k + 1];
+    v_[k] = dst[3 * k + 2];
+  }
 }
 
 void init_gaussians(const torch::Tensor& xyz, const torch::Tensor& covs, const torch::Tensor& rgbs, float scale_factor,

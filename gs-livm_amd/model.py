@@ -10,6 +10,9 @@ kernels of csrc/optimizer.hip (SURVEY.md section 8(f) "next" row 1):
   * `GrowableGaussians` -- row 4: the model as capacity buffers that grow in place
     (GaussianModel::addNewPointcloud / densification_postfix / cat_tensors_to_optimizer,
     src/gs/gaussian.cu:241-313, 451-472, 524-540);
+  * `GrowableGaussians.prune` / `prune_rows` -- the shrinking half, GaussianModel::prune_optimizer (gaussian.cu:430-449,
+    which the reference carries and never calls): rows that are dead to the rasterizer for good leave the leaves, the
+    Adam moments and the voxel index by a stable compaction (csrc/prune.hip);
   * `VoxelIndex` -- gs_hash_indexes_ (voxel key -> rows of its Gaussians, gaussian.cu:257-263) and the selection
     of calcSimiLoss (:201-228) on row RANGES, which feeds the fused similarity loss (csrc/simi.hip, loss.py).
 """
@@ -231,6 +234,28 @@ class VoxelIndex:
             row += c
         return row
 
+    def remap(self, row_map):
+        """Follows a stable compaction of the model's rows (GrowableGaussians.prune): row_map [P+1] (host integers) is
+        the exclusive prefix sum of "kept", so a key's (first, count) becomes
+        (row_map[first], row_map[first + count] - row_map[first]) -- a range stays a range.  A voxel that loses all its
+        rows stays registered with count 0 (adding its key again is still the duplicate-key error).  Host only, one
+        vectorised pass over the keys.  Raises (and changes nothing) when a range ends beyond the P rows of row_map."""
+        rm = row_map.cpu().numpy() if isinstance(row_map, torch.Tensor) else np.asarray(row_map)
+        rm = rm.astype(np.int64).reshape(-1)
+        if rm.size == 0:
+            raise ValueError("VoxelIndex.remap: row_map has P + 1 entries")
+        if not self._ranges:
+            return
+        keys = list(self._ranges)
+        rng = np.array([self._ranges[k] for k in keys], dtype=np.int64).reshape(-1, 2)
+        first, end = rng[:, 0], rng[:, 0] + rng[:, 1]
+        if int(first.min()) < 0 or int(end.max()) > rm.size - 1:
+            raise ValueError("VoxelIndex.remap: a voxel's rows end at %d, row_map covers %d rows"
+                             % (int(end.max()), rm.size - 1))
+        new_first = rm[first]
+        new_count = rm[end] - new_first
+        self._ranges = dict(zip(keys, zip(new_first.tolist(), new_count.tolist())))
+
     def select(self, losses, max_points=500, generator=None):
         """Steps 1-2 of GaussianModel::calcSimiLoss (src/gs/gaussian.cu:201-228) on the host.
 
@@ -352,6 +377,56 @@ class GrowableGaussians(GaussianParameters):
         self._bind()
         return lo, hi
 
+    @torch.no_grad()
+    def prune(self, min_opacity=1.0 / 255.0, max_scale=0.3, drop_nonfinite=True, drop=None):
+        """Removes the rows that are dead to the rasterizer for good -- the shrinking counterpart of add_new_pointcloud,
+        GaussianModel::prune_optimizer (src/gs/gaussian.cu:430-449) for all six groups at once.  A row leaves when
+          * sigmoid(_opacity) < min_opacity: below 1/255 its alpha never reaches the blend's 1/255 test, forward or
+            backward, so it contributes to no pixel and gets no photometric gradient;
+          * any exp(_scaling) > max_scale: k_preprocess' scale cull (at scale_modifier 1) drops it outright -- no tiles,
+            no gradient, nothing that would bring the scale back;
+          * drop_nonfinite and any of xyz / scaling / rotation / opacity is NaN or +-Inf;
+          * drop (optional [P] bool or uint8 device tensor) marks it.
+        Values ON a threshold stay (the rasterizer culls on >).  The survivors keep their order (a stable compaction),
+        so `voxel_index` ranges stay ranges and depth ties fall as before; with the defaults no pixel and no survivor's
+        gradient changes.  The Adam moments move with their rows, rows [P', capacity) of both moments are zero
+        afterwards (add_new_pointcloud relies on that), the step count and the capacity are kept.
+        Cost: four launches, ONE host wait per prune (the copy of the row map, which carries P'), and a transient
+        second set of capacity buffers (the compaction is out of place); the old set is released on return.
+        When nothing is dropped nothing is moved or re-bound: leaf objects and cached activations survive.  Otherwise
+        the leaves are new Parameter objects (as after a growth), cached activations and parked gradients are
+        dropped, and a `sel` obtained from `voxel_index.select` BEFORE the prune is stale: select again.
+        Returns {"P_before", "P_after", "n_opacity", "n_scale", "n_nonfinite", "n_mask" (a row with several reasons
+        counts under each), "row_map": [P+1] int32 on the host, row_map[i] = new row of old row i, row_map[P] = P',
+        "reasons": [P] uint8 on the device, 0 = kept}."""
+        P, b = self.P, self._buf
+        if drop is not None:
+            drop = drop.to(self.device).reshape(-1).contiguous()
+            if drop.numel() != P:
+                raise ValueError("prune: drop has %d entries, the model %d rows" % (drop.numel(), P))
+        reasons, row_map, _, both = _capi.prune_mark(b["_xyz"][:P], b["_scaling"][:P], b["_rotation"][:P],
+                                                     b["_opacity"][:P], min_opacity, max_scale, drop_nonfinite, drop,
+                                                     packed=True)
+        host = both.cpu()  # the one host wait
+        row_map_host, counts = host[:P + 1], [int(c) for c in host[P + 1:]]
+        P_new = counts[0]
+        out = dict(P_before=P, P_after=P_new, n_opacity=counts[1], n_scale=counts[2], n_nonfinite=counts[3],
+                   n_mask=counts[4], row_map=row_map_host, reasons=reasons)
+        if P_new == P:
+            return out
+        src, dst, fresh = [], [], ({}, {}, {})
+        for name, tail in self._shapes().items():
+            for store, new in zip((self._buf, self._m, self._v), fresh):
+                new[name] = torch.zeros((self.capacity,) + tail, dtype=torch.float32, device=self.device)
+                src.append(store[name][:P])
+                dst.append(new[name])
+        _capi.prune_compact(src, dst, reasons, row_map)
+        self._buf, self._m, self._v = fresh
+        self.P = P_new
+        self._bind()
+        self.voxel_index.remap(row_map_host)
+        return out
+
     def calc_simi_loss(self, losses, lambda_=0.2, scaling=None, max_points=500, generator=None):
         """GaussianModel::calcSimiLoss (src/gs/gaussian.cu:201-239): the similarity loss of the LiDAR points in
         `losses` ({voxel key: [k,3] CPU f32}) against the Gaussians of their voxels, or None where the reference
@@ -365,6 +440,19 @@ class GrowableGaussians(GaussianParameters):
         if scaling is None:
             scaling = self.Get_scaling()
         return similarity_loss(points, sel, self._xyz, scaling, lambda_)
+
+
+@torch.no_grad()
+def prune_rows(tensors, reasons, row_map, P_new):
+    """For callers who hold plain tensors: the rows of each [P, ...] f32 device tensor with reasons[i] == 0, in order,
+    as new [P_new, ...] tensors -- t[reasons == 0] for all of them, eighteen per launch (csrc/prune.hip).
+    reasons / row_map: what _capi.prune_mark returned; P_new = int(row_map[P]), which the caller has fetched."""
+    tensors = [t.contiguous() for t in tensors]
+    P_new = int(P_new)
+    outs = [torch.empty((P_new,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device) for t in tensors]
+    for i in range(0, len(tensors), 18):
+        _capi.prune_compact(tensors[i:i + 18], outs[i:i + 18], reasons, row_map)
+    return outs
 
 
 class GrowableAdam(FusedAdam):

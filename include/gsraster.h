@@ -461,6 +461,47 @@ size_t gsr_ply_row_floats(int M);
 int gsr_pack_ply_rows(int P, int M, const float* xyz, const float* features_dc, const float* features_rest,
                       const float* opacity, const float* scaling, const float* rotation, float* rows, void* stream);
 
+/* ---- in-place pruning: the rows that are dead to the rasterizer for good leave the model (an extension) ----
+ * The other half of the optimiser-state surgery: GaussianModel::prune_optimizer (src/gs/gaussian.cu:430-449) is an
+ * index_select of a leaf and of both of its Adam moments, per group; the reference carries it and never calls it.
+ * Removal is a STABLE compaction: surviving rows keep their relative order (a voxel's row range stays a range; the
+ * rasterizer breaks depth ties by ascending row number).
+ *
+ * gsr_prune_mark (three launches): reasons[P] (uint8, 0 = keep) and the row map of the compaction.  Drop bits:
+ *   bit 0  sigmoid(opacity_raw) < min_opacity      (below 1/255 a row's alpha never reaches the blend's 1/255 test)
+ *   bit 1  any exp(scaling_raw[k]) > max_scale     (k_preprocess' scale cull at scale_modifier 1, forward.cu:19-25)
+ *   bit 2  drop_nonfinite != 0 and any of xyz, scaling_raw, rotation_raw, opacity_raw is NaN or +-Inf (a NaN compares
+ *          false in both tests above and would otherwise stay for ever)
+ *   bit 3  drop (nullable, [P] bytes) is non-zero: the caller's own mask
+ * The activated values are gsr_activate's bit for bit; a value ON a threshold is kept (the rasterizer culls on >).
+ *   row_map [P + 1] int32: the exclusive prefix sum of "kept" -- row_map[i] is the new row of old row i (for a dropped
+ *     row: the new row of the next survivor), row_map[P] = P', the new row count;
+ *   counts5 [5] int32 = {P', rows with bit 0, with bit 1, with bit 2, with bit 3} (a row counts under each of its bits).
+ * xyz [P][3], scaling_raw [P][3], rotation_raw [P][4], opacity_raw [P]: the raw leaves.  workspace: gsr_prune_workspace(P)
+ * bytes -- five int32 per 256 rows, nothing per row.
+ * gsr_prune_compact (ONE launch for all tensors, whatever P): for up to 18 tensors -- six leaves x {parameter, exp_avg,
+ * exp_avg_sq} -- of widths[k] floats per row, dst[k][row_map[i]] = src[k][i] for every row with reasons[i] == 0.  src
+ * and dst are HOST arrays of device pointers; a destination is a buffer of its own of at least row_map[P] rows (out of
+ * place: an in-place stable compaction races), rows [row_map[P], ...) of it are not written.  A tensor of width 0
+ * (_features_rest at M = 1) is skipped and its pointers are not looked at.
+ * Alignment of caller tensors: they are contiguous and need only the alignment of their element, 4 bytes (reasons and
+ * drop: 1) -- every access is an element access.  A pointer at any other offset is refused.
+ * Refused (GSR_ERR_INVALID_ARGUMENT, nothing enqueued or written), in this order: shape (P < 0 or P > GSR_PRUNE_MAX_ROWS;
+ * compact: more than 18 tensors, a negative width, a model beyond one launch's 2^31 - 1 workgroups of 1024 floats); a
+ * null required pointer; a misaligned pointer; workspace_bytes below the query (the message names the bytes needed).
+ * P == 0: no row is touched; gsr_prune_mark writes row_map[0] = 0 and counts5 = {0, ...} (only those two are required),
+ * gsr_prune_compact returns at once.  The query returns 0 for P <= 0 and for a refused P.
+ * Deterministic (no atomics, no workgroup waits for another), no host synchronisation, no allocation, the caller's
+ * stream only. */
+#define GSR_PRUNE_MAX_ROWS 0x7fffff00
+size_t gsr_prune_workspace(int P);
+int gsr_prune_mark(int P, const float* xyz, const float* scaling_raw, const float* rotation_raw,
+                   const float* opacity_raw, const unsigned char* drop, float min_opacity, float max_scale,
+                   int drop_nonfinite, unsigned char* reasons, int* row_map, int* counts5, char* workspace,
+                   size_t workspace_bytes, void* stream);
+int gsr_prune_compact(int P, int n_tensors, const float* const* src, float* const* dst, const int* widths,
+                      const unsigned char* reasons, const int* row_map, void* stream);
+
 /* Optional per-kernel device timing (hipEvent pairs recorded on the launch stream around every
  * kernel launch while enabled).  Measurement aid for bench.py's roofline line; the reference has only
  * host wall-clock timers (include/common/timer/timer.h:36-52).  Not thread-safe; off by default.
