@@ -401,8 +401,12 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_preprocess(
           // Exact-conservative footprint: a pixel can only receive alpha = min(.99, op*exp(power)) >= 1/255
           // if -power <= ln(255*op); the axis-aligned box of that ellipse (plus slack for rounding in
           // the blend kernels) bounds every contributing pixel.  op < 1/255 never contributes.
+          // A non-finite opacity is never culled: alpha is 0.99 wherever op * exp(power) is NaN -- everywhere for a NaN
+          // opacity, and for +-Inf wherever exp(power) has underflowed to 0, which lies OUTSIDE any footprint box.
           float hx, hy;
-          if (op < 1.0f / 255.0f) {
+          if (!(fabsf(op) < INFINITY)) {
+            hx = hy = 1e30f;  // no culling, in either binning mode
+          } else if (op < 1.0f / 255.0f) {
             hx = hy = -1e30f;  // box test can never pass
           } else {
             const float tau = footprint_tau(op);
@@ -1436,10 +1440,14 @@ __device__ __forceinline__ void gather_finish(Sums r, const uint32_t id, const i
   const float S3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w1), 16));
   const float S4 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w0), 32));
   const float mc = -0.5f * op;
+  // The opacity is a factor of every pixel's term in the reference (dL_dG = opacity * dL_dalpha, backward.cu:583): a
+  // Gaussian none of whose pixels took it gets no term at all, i.e. 0 -- not 0 * opacity, which is NaN for an opacity
+  // of +-Inf or NaN.  Sums of exact zeros are exact zeros; for a finite opacity the product is the same 0.
+  auto times = [](const float sum, const float factor) { return sum == 0.0f ? 0.0f : sum * factor; };
   if (lane == 0) { dL_dcolor[3 * id] = w0; dL_dcolor[3 * id + 1] = w1; }
-  if (lane == 16) { dL_dcolor[3 * id + 2] = w0; dL_dmean2D[3 * id] = -(cx * S3 + cy * S4) * (op * ddelx_dx); }
-  if (lane == 32) { dL_dmean2D[3 * id + 1] = -(cz * S4 + cy * S3) * (op * ddely_dy); dL_dconic[4 * id] = w1 * mc; }
-  if (lane == 48) { dL_dconic[4 * id + 1] = w0 * mc; dL_dconic[4 * id + 3] = w1 * mc; }
+  if (lane == 16) { dL_dcolor[3 * id + 2] = w0; dL_dmean2D[3 * id] = times(-(cx * S3 + cy * S4), op * ddelx_dx); }
+  if (lane == 32) { dL_dmean2D[3 * id + 1] = times(-(cz * S4 + cy * S3), op * ddely_dy); dL_dconic[4 * id] = times(w1, mc); }
+  if (lane == 48) { dL_dconic[4 * id + 1] = times(w0, mc); dL_dconic[4 * id + 3] = times(w1, mc); }
   if (lane == 63) dL_dopacity[id] = v8;
   if constexpr (Sums::depth) {
     float v9 = row_allsum_(r.v9);

@@ -583,7 +583,10 @@ __global__ __launch_bounds__(256) void k_blend_backward(
         const float oma = 1.0f - alpha;
         const float rom = __builtin_amdgcn_rcpf(oma);
         const float Tn = T * rom;  // T / (1 - alpha)
-        const float D = __builtin_fmaf(b.z, dp0, __builtin_fmaf(b.w, dp1, __builtin_fmaf(blue, dp2, dacc_z))) - S;
+        // (a lane that does not take the splat takes D = 0 as well: with a non-finite colour 0 * D would be NaN and
+        // would enter S -- the reference's accum_rec never sees a splat its pixel skipped)
+        const float Draw = __builtin_fmaf(b.z, dp0, __builtin_fmaf(b.w, dp1, __builtin_fmaf(blue, dp2, dacc_z))) - S;
+        const float D = ok ? Draw : 0.0f;
         if (__ballot(ok) != 0ull) {
           const float G = ok ? Graw : 0.0f;
           const float dch = alpha * Tn;

@@ -78,7 +78,27 @@ typedef char* (*gsr_alloc_fn)(void* ctx, size_t bytes);
  * The host-thread state behind this (mailbox word, counters, prediction) is per thread and device;
  * one thread's forwards must be ordered on the device (ONE stream at a time per host thread -- the
  * reference uses the default stream only); a thread that changes streams is detected and the
- * previous stream is drained first.  Calls from different host threads are independent. */
+ * previous stream is drained first.  Calls from different host threads are independent.
+ *
+ * Non-finite inputs.  A NaN or +-Inf in a Gaussian is not an error and never leaves a buffer: every index derives from
+ * the tile rectangle, which is clamped to the grid after a float -> int conversion that gives 0 for NaN and saturates
+ * (v_cvt_i32_f32; the reference's cvt.rzi.s32.f32 does the same).  What the row then does is the reference's own
+ * arithmetic, in both binning modes alike (tests/test_gpu_nonfinite.py):
+ *   means3D      NaN / +-Inf in any component: the projected centre is NaN or infinite, the rectangle is empty, the row
+ *                is culled (radii 0, no gradient).  gsr_mark_visible reports a NaN depth as present (`<=` is false).
+ *   scales, rotations, cov3D_precomp
+ *                NaN, or an Inf that turns into NaN in the covariance: the radius is NaN -> radii 0, yet the rectangle
+ *                of radius 0 is the ONE tile under the centre; the conic is NaN, alpha = min(0.99, NaN) = 0.99: the row
+ *                paints that tile.  (The reference leaves this instance's sort key uninitialised; it is emitted here.)
+ *                A scale of +Inf is scale-culled.  The row's own gradients are zero (radii 0).
+ *   opacities    NaN and +Inf: alpha 0.99 over the whole 3-sigma rectangle.  -Inf: alpha 0.99 where exp(power) has
+ *                underflowed to 0 (-Inf * 0 = NaN), nothing elsewhere.  A non-finite opacity is never footprint-culled.
+ *                A row that no pixel blended gets exact zero gradients, whatever its opacity.
+ *   shs          a NaN colour sum becomes 0 (black): max(NaN, 0) is NaN-ignoring here, where the reference's glm::max
+ *                returns NaN.  +Inf gives an infinite colour: infinite / NaN pixels under the row, and NaN gradients
+ *                for the rows in front of it on those pixels (the reference's accum_rec recurrence).
+ *   colors_precomp  blended as given: non-finite pixels and gradients as for an infinite SH colour.
+ * Gradients of rows that share no tile with a poisoned row are unaffected. */
 int gsr_forward(gsr_alloc_fn geometry_alloc, void* geometry_ctx, gsr_alloc_fn binning_alloc, void* binning_ctx,
                 gsr_alloc_fn image_alloc, void* image_ctx, int P, int D, int M, const float* background, int width,
                 int height, const float* means3D, const float* shs, const float* colors_precomp,
@@ -461,7 +481,7 @@ size_t gsr_ply_row_floats(int M);
 int gsr_pack_ply_rows(int P, int M, const float* xyz, const float* features_dc, const float* features_rest,
                       const float* opacity, const float* scaling, const float* rotation, float* rows, void* stream);
 
-/* ---- in-place pruning: the rows that are dead to the rasterizer for good leave the model (an extension) ----
+/* ---- in-place pruning: the rows that no optimiser step brings back leave the model (an extension) ----
  * The other half of the optimiser-state surgery: GaussianModel::prune_optimizer (src/gs/gaussian.cu:430-449) is an
  * index_select of a leaf and of both of its Adam moments, per group; the reference carries it and never calls it.
  * Removal is a STABLE compaction: surviving rows keep their relative order (a voxel's row range stays a range; the
@@ -471,7 +491,8 @@ int gsr_pack_ply_rows(int P, int M, const float* xyz, const float* features_dc, 
  *   bit 0  sigmoid(opacity_raw) < min_opacity      (below 1/255 a row's alpha never reaches the blend's 1/255 test)
  *   bit 1  any exp(scaling_raw[k]) > max_scale     (k_preprocess' scale cull at scale_modifier 1, forward.cu:19-25)
  *   bit 2  drop_nonfinite != 0 and any of xyz, scaling_raw, rotation_raw, opacity_raw is NaN or +-Inf (a NaN compares
- *          false in both tests above and would otherwise stay for ever)
+ *          false in both tests above and would otherwise stay for ever).  Such a row is NOT invisible to gsr_forward
+ *          ("Non-finite inputs" above): dropping it changes the pixels it painted.
  *   bit 3  drop (nullable, [P] bytes) is non-zero: the caller's own mask
  * The activated values are gsr_activate's bit for bit; a value ON a threshold is kept (the rasterizer culls on >).
  *   row_map [P + 1] int32: the exclusive prefix sum of "kept" -- row_map[i] is the new row of old row i (for a dropped

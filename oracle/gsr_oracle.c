@@ -61,6 +61,17 @@ static inline float fminf_(float a, float b) { return fminf(a, b); }
 static inline float fmaxf_(float a, float b) { return fmaxf(a, b); }
 static inline int imin(int a, int b) { return a < b ? a : b; }
 static inline int imax(int a, int b) { return a > b ? a : b; }
+/* float -> int, defined for every input: truncation toward zero, NaN -> 0, saturation at INT_MIN / INT_MAX.  That is
+ * the rule of the reference's own conversion instruction (PTX cvt.rzi.s32.f32: "NaN results in 0", out-of-range
+ * values clamp) and of the product's (CDNA v_cvt_i32_f32: NaN -> 0, +-Inf and out-of-range saturate).  A plain C
+ * cast is undefined behaviour for those inputs, and on x86 (cvttss2si) it yields INT_MIN for all of them: a NaN
+ * radius then became -2147483648 and a whole-grid rectangle.  Every float -> int conversion below goes through here. */
+static inline int f2i(float v) {
+  if (v != v) return 0;
+  if (v >= 2147483648.0f) return INT32_MAX;
+  if (v <= -2147483648.0f) return INT32_MIN;
+  return (int)v;
+}
 
 /* include/gs/cuda_rasterizer/auxiliary.h:48-64 (transformPoint4x3 / 4x4): matrices
  * are column-major 4x4 in memory. */
@@ -82,10 +93,10 @@ static float ndc2pix(float v, int S) { return (float)((((double)v + 1.0) * (doub
  * step, truncating casts, clamp to [0, grid]. */
 static void tile_rect(float px, float py, int radius, int gx, int gy, int* x0, int* y0, int* x1, int* y1) {
   float r = (float)radius;
-  *x0 = imin(gx, imax(0, (int)((px - r) / (float)TILE)));
-  *y0 = imin(gy, imax(0, (int)((py - r) / (float)TILE)));
-  *x1 = imin(gx, imax(0, (int)((((px + r) + (float)TILE) - 1.0f) / (float)TILE)));
-  *y1 = imin(gy, imax(0, (int)((((py + r) + (float)TILE) - 1.0f) / (float)TILE)));
+  *x0 = imin(gx, imax(0, f2i((px - r) / (float)TILE)));
+  *y0 = imin(gy, imax(0, f2i((py - r) / (float)TILE)));
+  *x1 = imin(gx, imax(0, f2i((((px + r) + (float)TILE) - 1.0f) / (float)TILE)));
+  *y1 = imin(gy, imax(0, f2i((((py + r) + (float)TILE) - 1.0f) / (float)TILE)));
 }
 
 /* SH basis constants: auxiliary.h:22-33 */
@@ -192,7 +203,7 @@ typedef struct gsro_frame {
   float* final_T;
   uint32_t* n_contrib;
   float *out_color, *out_depth, *out_acc;
-  uint8_t* fragile; /* [H*W] 1 = some threshold test of this pixel sat within rounding distance (see blend_tile) */
+  uint8_t* fragile; /* [H*W] != 0 = some threshold test of this pixel sat within rounding distance (see blend_tile) */
   int own_cov3D, own_rgb;
   const float* colors_used; /* rgb or colors_precomp */
   const float* cov3D_used;
@@ -235,6 +246,10 @@ static float ln_upper(float x) {
 /* narrows [x0,x1) x [y0,y1); an empty result has x1 <= x0 or y1 <= y0 */
 static void tighten_rect(float px, float py, const float conic[3], float op, int* x0, int* y0, int* x1, int* y1) {
   float hx, hy;
+  /* a non-finite opacity is never culled: alpha = min(0.99, op * exp(power)) is 0.99 wherever the product is NaN --
+   * everywhere for a NaN opacity, and for +-Inf wherever exp(power) has underflowed to 0, which is OUTSIDE any
+   * footprint box.  (-Inf < 1/255 would otherwise drop a row that the reference's rectangles paint.) */
+  if (!(fabsf(op) < INFINITY)) return;
   if (op < 1.0f / 255.0f) {
     *x1 = *x0;
     return;
@@ -246,10 +261,10 @@ static void tighten_rect(float px, float py, const float conic[3], float op, int
   hy = sqrtf(2.0f * tau * conic[0] / dc) + 0.05f;
   if (!(hx < 1e6f)) return;
   const float lim = 1e6f;
-  int bx0 = (int)ceilf(fmaxf_(-lim, fminf_(lim, (px - hx - 15.0f) * 0.0625f)));
-  int bx1 = (int)floorf(fmaxf_(-lim, fminf_(lim, (px + hx) * 0.0625f))) + 1;
-  int by0 = (int)ceilf(fmaxf_(-lim, fminf_(lim, (py - hy - 15.0f) * 0.0625f)));
-  int by1 = (int)floorf(fmaxf_(-lim, fminf_(lim, (py + hy) * 0.0625f))) + 1;
+  int bx0 = f2i(ceilf(fmaxf_(-lim, fminf_(lim, (px - hx - 15.0f) * 0.0625f))));
+  int bx1 = f2i(floorf(fmaxf_(-lim, fminf_(lim, (px + hx) * 0.0625f)))) + 1;
+  int by0 = f2i(ceilf(fmaxf_(-lim, fminf_(lim, (py - hy - 15.0f) * 0.0625f))));
+  int by1 = f2i(floorf(fmaxf_(-lim, fminf_(lim, (py + hy) * 0.0625f)))) + 1;
   if (bx0 > *x0) *x0 = bx0;
   if (bx1 < *x1) *x1 = bx1;
   if (by0 > *y0) *y0 = by0;
@@ -296,11 +311,11 @@ static void preprocess_one(gsro_frame* f, int idx, const float* means3D, const f
   float my_radius = ceilf(3.f * sqrtf(fmaxf_(lambda1, lambda2)));
   float pix[2] = {ndc2pix(ppx, f->W), ndc2pix(ppy, f->H)};
   int x0, y0, x1, y1;
-  tile_rect(pix[0], pix[1], (int)my_radius, f->gx, f->gy, &x0, &y0, &x1, &y1);
+  tile_rect(pix[0], pix[1], f2i(my_radius), f->gx, f->gy, &x0, &y0, &x1, &y1);
   if ((x1 - x0) * (y1 - y0) == 0) return;
   if (!colors_precomp) sh_to_rgb(f->D, f->M, p, campos, shs + (size_t)idx * f->M * 3, f->rgb + 3 * idx, f->clamped + 3 * idx);
   f->depths[idx] = pv[2];
-  f->radii[idx] = (int)my_radius;
+  f->radii[idx] = f2i(my_radius);
   f->means2D[2 * idx] = pix[0];
   f->means2D[2 * idx + 1] = pix[1];
   f->conic_opacity[4 * idx + 0] = conic[0];
@@ -379,11 +394,16 @@ static void blend_tile(gsro_frame* f, int tx, int ty, const float* bg) {
          * ~ a few ulp of the LARGEST term, and alpha inherits it as a RELATIVE error (alpha = op * e^power).  The
          * window of the alpha cut and of power > 0 therefore scales with that uncertainty. */
         float unc = 6e-7f * (fabsf(co[0] * dx * dx) + fabsf(co[2] * dy * dy) + 2.0f * fabsf(co[1] * dx * dy));
-        if (fabsf(alpha * 255.0f - 1.0f) < 2e-5f + unc || fabsf(power) < 1e-6f + unc) fragile = 1;
+        if (fabsf(alpha * 255.0f - 1.0f) < 2e-5f + unc || fabsf(power) < 1e-6f + unc) fragile |= 1;
+        /* An opacity of -Inf: alpha = -Inf * G is -Inf (skipped) where G > 0 and NaN (-> 0.99, blended) where G == 0.
+         * G passes through the subnormals between power = -87.3 (FLT_MIN) and -104 (half the smallest subnormal);
+         * libm's expf returns them, a hardware exp unit flushes them to 0.  Pixels in that band are decided by the
+         * implementation of exp alone, and a flip moves them by up to 0.99 T, not by a small alpha: bit 1 of the flag. */
+        if (co[3] == -INFINITY && power < -87.0f && power > -104.5f) fragile |= 2;
         if (alpha < 1.0f / 255.0f) continue;
         float test_T = T * (1 - alpha);
         t_unc += alpha * unc / (1.0f - alpha); /* relative uncertainty T inherits from the alphas before it */
-        if (fabsf(test_T * 10000.0f - 1.0f) < 2e-4f + t_unc) fragile = 1;
+        if (fabsf(test_T * 10000.0f - 1.0f) < 2e-4f + t_unc) fragile |= 1;
         if (test_T < 0.0001f) break; /* done = true */
         for (int ch = 0; ch < 3; ch++) C[ch] += feat[3 * g + ch] * alpha * T;
         Dp += f->depths[g] * alpha * T; /* forward.cu:386 */
@@ -454,12 +474,15 @@ gsro_frame* gsro_forward(int P, int D, int M, const float* background, int W, in
 
 #pragma omp parallel for schedule(dynamic, 1024)
   for (int i = 0; i < P; i++) { /* duplicateWithKeys */
-    if (f->radii[i] <= 0) continue;
+    /* The reference tests radii > 0 here (rasterizer_impl.cu:78).  For finite inputs that is tiles_touched > 0 under its
+     * rectangles; a NaN radius (NaN scale or rotation) converts to 0 yet keeps a one-tile rectangle, and the reference
+     * then leaves that instance's key uninitialised.  Defined here as the product defines it: an instance is emitted
+     * for every tile counted in tiles_touched. */
+    if (!f->tiles_touched[i]) continue;
     uint32_t off = i == 0 ? 0 : f->point_offsets[i - 1];
     int x0, y0, x1, y1;
     tile_rect(f->means2D[2 * i], f->means2D[2 * i + 1], f->radii[i], f->gx, f->gy, &x0, &y0, &x1, &y1);
     if (g_tight) {
-      if (!f->tiles_touched[i]) continue;
       tighten_rect(f->means2D[2 * i], f->means2D[2 * i + 1], f->conic_opacity + 4 * i, f->conic_opacity[4 * i + 3],
                    &x0, &y0, &x1, &y1);
     }

@@ -77,22 +77,44 @@ def test_tile_culling_leaves_images_and_gradients_bit_identical(P, W, H, seed, D
         sc["scales"][:20] = 0.29
         sc["opacities"][100:300] = 0.003
         sc["opacities"][300:500] = 0.0045
+    _culling_is_invisible(sc, seed, shrinks=P >= 2500)
+    # ... for EVERY input: rows with an opacity of NaN, +Inf and -Inf.  NaN and +Inf blend at min(0.99, NaN) = 0.99 over
+    # the whole rectangle; -Inf blends where exp(power) has underflowed to 0 (-Inf * 0 = NaN), which lies outside any
+    # footprint box -- a culled mode that drops the row on `op < 1/255` changes the image.  The rows are needles, so
+    # that the 3-sigma square holds such pixels.
+    vis = np.flatnonzero(O.forward(sc, keep_handle=False).radii > 0)[:6]
+    assert vis.size >= 3
+    sc["scales"][vis] = np.array([0.25, 0.004, 0.004], np.float32)
+    for j, r in enumerate(vis):
+        sc["opacities"][r] = (np.nan, np.inf, -np.inf)[j % 3]
+    a = _culling_is_invisible(sc, seed, shrinks=False)
+    clean = dict(sc, opacities=np.where(np.isfinite(sc["opacities"]), sc["opacities"], 0.0).astype(np.float32))
+    assert not np.array_equal(a.out_color, O.forward(clean, keep_handle=False).out_color)   # (the rows do paint)
+
+
+def _same(x, y):
+    return np.array_equal(x, y, equal_nan=True)   # (bit-identical; a NaN gradient of a poisoned row equals itself)
+
+
+def _culling_is_invisible(sc, seed, shrinks):
+    W, H = sc["W"], sc["H"]
     O.set_threads(1)
     a, b = O.forward(sc), O.forward(sc, tight=True)
     for k in ("radii", "means2D", "depths", "conic_opacity", "out_color", "out_depth", "out_acc", "final_T",
               "fragile"):
-        assert np.array_equal(getattr(a, k), getattr(b, k)), k
+        assert _same(getattr(a, k), getattr(b, k)), k
     assert (b.tiles_touched <= a.tiles_touched).all() and b.R <= a.R
-    if P >= 2500:
+    if shrinks:
         assert b.R < 0.9 * a.R
     dcol, dacc = S.make_upstream_grads(W, H, seed)
     ga, gb = O.backward(a, sc, dcol, dacc), O.backward(b, sc, dcol, dacc)
     for k in ga:
-        assert np.array_equal(ga[k], gb[k]), k
+        assert _same(ga[k], gb[k]), k
     # every instance of the culled list is an instance of the reference list, in the same relative order
     ia = set(zip((a.keys >> np.uint64(32)).tolist(), a.point_list.tolist()))
     ib = list(zip((b.keys >> np.uint64(32)).tolist(), b.point_list.tolist()))
     assert all(x in ia for x in ib)
+    return a
 
 
 def test_small_matrix_helpers_match_the_references_glm():
