@@ -69,7 +69,8 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_frame_note_misses", "gsr_similarity_loss", "gsr_similarity_loss_workspace",
            "gsr_delta_depth_loss", "gsr_delta_depth_loss_workspace", "gsr_image_metrics",
            "gsr_image_metrics_workspace", "gsr_pack_image_u8", "gsr_pack_depth_u8", "gsr_prune_workspace",
-           "gsr_prune_mark", "gsr_prune_compact")
+           "gsr_prune_mark", "gsr_prune_compact", "gsr_lidar_depth_image", "gsr_lidar_depth_loss",
+           "gsr_lidar_depth_loss_workspace")
 
 
 def lib():
@@ -174,6 +175,12 @@ def lib():
     L.gsr_delta_depth_loss.restype = ci
     L.gsr_delta_depth_loss.argtypes = [ci, ci, vp, vp, vp, vp, C.POINTER(cf), C.POINTER(cf), C.POINTER(cf), cf, vp, vp,
                                        vp, vp, vp, sz, vp]
+    L.gsr_lidar_depth_image.restype = ci
+    L.gsr_lidar_depth_image.argtypes = [ci, vp, C.POINTER(cf), C.POINTER(cf), ci, ci, cf, cf, vp, vp, vp]
+    L.gsr_lidar_depth_loss_workspace.restype = sz
+    L.gsr_lidar_depth_loss_workspace.argtypes = [ci, ci]
+    L.gsr_lidar_depth_loss.restype = ci
+    L.gsr_lidar_depth_loss.argtypes = [ci, ci, vp, vp, vp, cf, cf, vp, vp, vp, vp, sz, vp]
     L.gsr_image_metrics_workspace.restype = sz
     L.gsr_image_metrics_workspace.argtypes = [ci, ci, ci]
     L.gsr_image_metrics.restype = ci
@@ -634,6 +641,42 @@ def delta_depth_loss(depth_src, acc_src, depth_ref, acc_ref, inv_K_src, K_ref, T
                                       trel, float(lambda_), _ptr(out3), _ptr(warped), _ptr(gs), _ptr(gr), _ptr(ws),
                                       nbytes, _stream()))
     return out3, warped, gs, gr
+
+
+def lidar_depth_image(points_world, T_cw, K, height, width, min_depth=0.2, max_depth=float("inf"), want_counts=False):
+    """The z-buffer of a LiDAR sweep in a keyframe's view in three launches (include/gsraster.h,
+    gsr_lidar_depth_image).  points_world: [n,3] f32 on the device (n == 0 is legal); T_cw (3x4 or 4x4, [R | t] with
+    x_c = R x_w + t) and K (3x3) on the host.  Returns the [H,W] f32 image -- the smallest z per pixel, 0 where no
+    point lands -- and, with want_counts, an int32 device tensor {points kept, pixels hit} beside it."""
+    assert points_world.is_cuda and points_world.dtype == torch.float32 and points_world.is_contiguous()
+    assert points_world.dim() == 2 and points_world.size(1) == 3
+    n, H, W = int(points_world.size(0)), int(height), int(width)
+    T = torch.as_tensor(T_cw, dtype=torch.float64).reshape(-1, 4)[:3]
+    tcw, k9 = _host_floats(T, 12), _host_floats(K, 9)
+    dev = points_world.device
+    image = torch.empty((max(H, 0), max(W, 0)), dtype=torch.float32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev) if want_counts else None
+    _check(lib().gsr_lidar_depth_image(n, _ptr(points_world), tcw, k9, H, W, float(min_depth), float(max_depth),
+                                       _ptr(image), _ptr(counts), _stream()))
+    return (image, counts) if want_counts else image
+
+
+def lidar_depth_loss(depth, acc, lidar_depth, acc_min, lambda_, want_grad_depth=True, want_grad_acc=True):
+    """The masked depth L1 of a render against a LiDAR depth image in three launches (include/gsraster.h,
+    gsr_lidar_depth_loss).  depth / acc: the rasterizer's second and third outputs, [H,W] or [1,H,W] f32 on the device;
+    lidar_depth: what lidar_depth_image returns.  Returns (out3 = [loss, mean |depth error| in metres, supervised
+    share] device tensor, dL/ddepth or None, dL/dacc or None), the gradients shaped like depth and acc."""
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    for t in (depth, acc, lidar_depth):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == H * W
+    nbytes = int(lib().gsr_lidar_depth_loss_workspace(H, W))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=depth.device)
+    out3 = torch.empty(3, dtype=torch.float32, device=depth.device)
+    gd = torch.empty_like(depth) if want_grad_depth else None
+    ga = torch.empty_like(acc) if want_grad_acc else None
+    _check(lib().gsr_lidar_depth_loss(H, W, _ptr(depth), _ptr(acc), _ptr(lidar_depth), float(acc_min), float(lambda_),
+                                      _ptr(out3), _ptr(gd), _ptr(ga), _ptr(ws), nbytes, _stream()))
+    return out3, gd, ga
 
 
 def image_metrics(img, gt, window11, out=None, totals=None):

@@ -34,6 +34,7 @@ UNITS = {
     "growth.hip": [],
     "simi.hip": [],
     "delta.hip": [],
+    "lidar.hip": [],
     "prune.hip": [],
     "metrics.hip": ["-fno-slp-vectorize"],  # (k_metrics_forward is k_loss_forward's arithmetic: built like loss.hip)
     "api.hip": [],

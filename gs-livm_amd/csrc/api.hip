@@ -131,6 +131,8 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_activate_backward", "k_adam", "k_loss_forward", "k_loss_finalize", "k_loss_backward", "k_init_gaussians", "k_pack_ply_rows", "k_model_step", "k_tile_order", "k_live_sat", "k_compact_near",
     "k_simi_nearest", "k_simi_points", "k_simi_grads",
     "k_delta_project", "k_delta_sample", "k_delta_scatter", "k_delta_convert",
+    "k_lidar_clear", "k_lidar_splat", "k_lidar_convert", "k_lidar_loss_forward", "k_lidar_loss_finish",
+    "k_lidar_loss_grads",
     "k_metrics_forward", "k_metrics_finalize", "k_pack_image_u8", "k_pack_depth_u8",
     "k_prune_mark", "k_prune_scan", "k_prune_rank", "k_prune_compact"};
 
@@ -1624,6 +1626,45 @@ int gsr_delta_depth_loss(int height, int width, const float* depth_src, const fl
   HIP_TRY(launch_delta_depth_loss(height, width, depth_src, acc_src, depth_ref, acc_ref, inv_K_src9, K_ref9, T_rel12,
                                   lambda, out3, warped, dL_ddepth_src, dL_ddepth_ref, workspace,
                                   (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+int gsr_lidar_depth_image(int n, const float* points_world, const float* T_cw12, const float* K9, int height, int width,
+                          float min_depth, float max_depth, float* lidar_depth, int* counts2, void* stream_) {
+  g_err[0] = 0;
+  if (n < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad n");
+  if (height < 1 || width < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if ((unsigned long long)height * (unsigned long long)width >= 0x80000000ull)  // (32-bit pixel indices)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  if ((n > 0 && !points_world) || !T_cw12 || !K9 || !lidar_depth) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (!(min_depth >= 0.f && min_depth <= 3.402823466e38f))  // (false for NaN and +inf)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "bad min_depth: finite and >= 0");
+  if (!(max_depth > min_depth)) return fail(GSR_ERR_INVALID_ARGUMENT, "bad max_depth: greater than min_depth");
+  HIP_TRY(launch_lidar_depth_image(n, points_world, T_cw12, K9, height, width, min_depth, max_depth, lidar_depth,
+                                   counts2, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+size_t gsr_lidar_depth_loss_workspace(int height, int width) {
+  if (height < 1 || width < 1 || (unsigned long long)height * (unsigned long long)width >= 0x80000000ull) return 0;
+  return lidar_loss_workspace_bytes(height, width);
+}
+
+int gsr_lidar_depth_loss(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
+                         float acc_min, float lambda, float* out3, float* dL_ddepth, float* dL_dacc, char* workspace,
+                         size_t workspace_bytes, void* stream_) {
+  g_err[0] = 0;
+  if (height < 1 || width < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if ((unsigned long long)height * (unsigned long long)width >= 0x80000000ull)  // (32-bit pixel indices)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  if (!depth || !acc || !lidar_depth || !out3 || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (!(acc_min > 0.f && acc_min <= 3.402823466e38f))  // (false for NaN and +inf)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "bad acc_min: finite and > 0");
+  if (workspace_bytes < lidar_loss_workspace_bytes(height, width))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes",
+                lidar_loss_workspace_bytes(height, width));
+  HIP_TRY(launch_lidar_depth_loss(height, width, depth, acc, lidar_depth, acc_min, lambda, out3, dL_ddepth, dL_dacc,
+                                  workspace, (hipStream_t)stream_));
   return GSR_OK;
 }
 

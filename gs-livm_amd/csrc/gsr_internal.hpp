@@ -446,6 +446,15 @@ hipError_t launch_delta_depth_loss(int H, int W, const float* depth_src, const f
                                    const float* acc_ref, const float* inv_K_src9, const float* K_ref9,
                                    const float* T_rel12, float lambda, float* out3, float* warped,
                                    float* dL_ddepth_src, float* dL_ddepth_ref, char* workspace, hipStream_t s);
+// lidar.hip (LiDAR depth supervision: a sweep's z-buffer in a keyframe's view, and the masked depth L1 of a render
+// against it with the gradients towards depth and silhouette; T_cw12 and K9 are HOST pointers, composed in double)
+hipError_t launch_lidar_depth_image(int n, const float* points_world, const float* T_cw12, const float* K9, int H,
+                                    int W, float min_depth, float max_depth, float* lidar_depth, int* counts2,
+                                    hipStream_t s);
+size_t lidar_loss_workspace_bytes(int H, int W);
+hipError_t launch_lidar_depth_loss(int H, int W, const float* depth, const float* acc, const float* lidar_depth,
+                                   float acc_min, float lambda, float* out3, float* dL_ddepth, float* dL_dacc,
+                                   char* workspace, hipStream_t s);
 // metrics.hip (the evaluation pass: PSNR / SSIM / L1 / mse of a render against its ground truth, 8-bit frame export)
 size_t metrics_workspace_bytes(int C, int H, int W);
 hipError_t launch_image_metrics(int C, int H, int W, const float* img, const float* gt, const float* window11,
@@ -490,6 +499,8 @@ enum KernelId {
   K_DSORT_SCATTER, K_ACTIVATE, K_ACTIVATE_BWD, K_ADAM, K_LOSS_FWD, K_LOSS_FINALIZE, K_LOSS_BWD, K_INIT_GAUSSIANS, K_PACK_PLY, K_MODEL_STEP, K_TILE_ORDER, K_LIVE_SAT, K_COMPACT_NEAR,
   K_SIMI_NEAREST, K_SIMI_POINTS, K_SIMI_GRADS,
   K_DELTA_PROJECT, K_DELTA_SAMPLE, K_DELTA_SCATTER, K_DELTA_CONVERT,
+  // (beside the other depth term; ids are looked up by name, and the prune kernels stay the last four)
+  K_LIDAR_CLEAR, K_LIDAR_SPLAT, K_LIDAR_CONVERT, K_LIDAR_LOSS_FWD, K_LIDAR_LOSS_FINISH, K_LIDAR_LOSS_GRADS,
   K_METRICS_FWD, K_METRICS_FINALIZE, K_PACK_IMAGE_U8, K_PACK_DEPTH_U8,
   K_PRUNE_MARK, K_PRUNE_SCAN, K_PRUNE_RANK, K_PRUNE_COMPACT, K_COUNT
 };

@@ -10,6 +10,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <limits>
 #include <string>
 #include <tuple>
 #include <unordered_map>
@@ -52,6 +53,22 @@ torch::Tensor delta_depth_loss(const torch::Tensor& depth_src, const torch::Tens
                                const torch::Tensor& depth_ref, const torch::Tensor& acc_ref,
                                const torch::Tensor& inv_K_src, const torch::Tensor& K_ref, const torch::Tensor& T_rel,
                                float lambda = 0.2f);
+
+// ---- LiDAR depth supervision (an extension; csrc/lidar.hip) ----------------------------------------------------------
+// lidar_depth_image: the z-buffer of a sweep in a keyframe's view, built once when gsAddCamera makes the keyframe:
+// points_world [n,3] f32 on the device (n == 0 is legal), T_cw 3x4 or 4x4 ([R | t], x_c = R x_w + t) and K 3x3 on the
+// host or anywhere (read as 12 + 9 host floats) -> [H,W] f32, the smallest z per pixel, 0 where no point lands.
+// counts (optional): receives an int32 device tensor {points kept, pixels hit}.
+torch::Tensor lidar_depth_image(const torch::Tensor& points_world, const torch::Tensor& T_cw, const torch::Tensor& K,
+                                int64_t height, int64_t width, float min_depth = 0.2f,
+                                float max_depth = std::numeric_limits<float>::infinity(),
+                                torch::Tensor* counts = nullptr);
+// lidar_depth_loss: lambda * mean over the supervised pixels (lidar_depth > 0 and acc >= acc_min) of
+// |depth / acc - lidar_depth| as ONE autograd node; depth / acc: the rasterizer's second and third outputs, [H,W] or
+// [1,H,W] f32 on the device.  Gradients w.r.t. depth and acc only.  Returns the 0-dim loss.
+// (Like delta_depth_loss, these two are not part of the oracle/ref_link link check, which stays as it is.)
+torch::Tensor lidar_depth_loss(const torch::Tensor& depth, const torch::Tensor& acc, const torch::Tensor& lidar_depth,
+                               float acc_min = 0.5f, float lambda = 1.0f);
 
 // ---- the evaluation pass (saveRender, src/liw/lioOptimization.cpp:2182-2245; the status line of optimize_vis) ------
 // [psnr, ssim, l1, mse] of image against gt ([C,H,W] f32 on the device) on the kernels of csrc/metrics.hip, a device

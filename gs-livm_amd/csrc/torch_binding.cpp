@@ -440,6 +440,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lambda_") = 0.2f);
   n.def("delta_depth_loss", &nx::delta_depth_loss, py::arg("depth_src"), py::arg("acc_src"), py::arg("depth_ref"),
         py::arg("acc_ref"), py::arg("inv_K_src"), py::arg("K_ref"), py::arg("T_rel"), py::arg("lambda_") = 0.2f);
+  n.def("lidar_depth_image",
+        [](torch::Tensor points_world, torch::Tensor T_cw, torch::Tensor K, int64_t height, int64_t width,
+           float min_depth, float max_depth, bool want_counts) -> py::object {
+          torch::Tensor counts;
+          torch::Tensor image = nx::lidar_depth_image(points_world, T_cw, K, height, width, min_depth, max_depth,
+                                                      want_counts ? &counts : nullptr);
+          if (!want_counts) return py::cast(image);
+          return py::make_tuple(image, counts);
+        },
+        py::arg("points_world"), py::arg("T_cw"), py::arg("K"), py::arg("height"), py::arg("width"),
+        py::arg("min_depth") = 0.2f, py::arg("max_depth") = std::numeric_limits<float>::infinity(),
+        py::arg("want_counts") = false);
+  n.def("lidar_depth_loss", &nx::lidar_depth_loss, py::arg("depth"), py::arg("acc"), py::arg("lidar_depth"),
+        py::arg("acc_min") = 0.5f, py::arg("lambda_") = 1.0f);
   n.def("image_metrics",
         [opt](torch::Tensor image, torch::Tensor gt, py::object window, py::object totals) {
           return nx::image_metrics(image, gt, opt(window), opt(totals));

@@ -158,6 +158,36 @@ struct DeltaDepthLossFn : public torch::autograd::Function<DeltaDepthLossFn> {
   }
 };
 
+struct LidarDepthLossFn : public torch::autograd::Function<LidarDepthLossFn> {
+  static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor depth, torch::Tensor acc,
+                               torch::Tensor lidar_depth, double acc_min, double lambda) {
+    const torch::Tensor d = dev_f32(depth, "depth"), a = dev_f32(acc, "acc"), zl = dev_f32(lidar_depth, "lidar_depth");
+    if (d.dim() < 2) throw std::invalid_argument("lidar_depth_loss: [H,W] or [1,H,W] images");
+    const int64_t H = d.size(-2), W = d.size(-1);
+    if (d.numel() != H * W || a.numel() != H * W || zl.numel() != H * W)
+      throw std::invalid_argument("lidar_depth_loss: three images of one shape [H,W] or [1,H,W]");
+    torch::Tensor gd = depth.requires_grad() ? torch::empty_like(d) : torch::Tensor();
+    torch::Tensor ga = acc.requires_grad() ? torch::empty_like(d) : torch::Tensor();
+    const size_t nbytes = gsr_lidar_depth_loss_workspace(static_cast<int>(H), static_cast<int>(W));
+    torch::Tensor ws = torch::empty({static_cast<long long>(nbytes ? nbytes : 1)}, d.options().dtype(torch::kByte));
+    torch::Tensor out3 = torch::empty({3}, d.options());
+    check(gsr_lidar_depth_loss(static_cast<int>(H), static_cast<int>(W), fp(d), fp(a), fp(zl),
+                               static_cast<float>(acc_min), static_cast<float>(lambda), out3.data_ptr<float>(), fp(gd),
+                               fp(ga), reinterpret_cast<char*>(ws.data_ptr()), nbytes, current_stream()),
+          "gsr_lidar_depth_loss");
+    ctx->save_for_backward({gd.defined() ? gd : torch::empty({0}, d.options()),
+                            ga.defined() ? ga.view_as(acc) : torch::empty({0}, d.options())});
+    return out3[0];
+  }
+  static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx,
+                                               torch::autograd::tensor_list grad_outputs) {
+    const auto saved = ctx->get_saved_variables();
+    const torch::Tensor gd = saved[0], ga = saved[1], g = grad_outputs[0];
+    return {gd.numel() ? gd * g : torch::Tensor(), ga.numel() ? ga * g : torch::Tensor(), torch::Tensor(),
+            torch::Tensor(), torch::Tensor()};
+  }
+};
+
 struct ActivateFn : public torch::autograd::Function<ActivateFn> {
   static torch::autograd::tensor_list forward(torch::autograd::AutogradContext* ctx, torch::Tensor scaling_raw,
                                               torch::Tensor rotation_raw, torch::Tensor opacity_raw,
@@ -227,6 +257,34 @@ torch::Tensor delta_depth_loss(const torch::Tensor& depth_src, const torch::Tens
                                float lambda) {
   return DeltaDepthLossFn::apply(depth_src, acc_src, depth_ref, acc_ref, inv_K_src, K_ref, T_rel,
                                  static_cast<double>(lambda));
+}
+
+torch::Tensor lidar_depth_image(const torch::Tensor& points_world, const torch::Tensor& T_cw, const torch::Tensor& K,
+                                int64_t height, int64_t width, float min_depth, float max_depth,
+                                torch::Tensor* counts) {
+  torch::NoGradGuard no_grad;
+  const torch::Tensor p = dev_f32(points_world, "points_world");
+  if (p.dim() != 2 || p.size(1) != 3) throw std::invalid_argument("lidar_depth_image: points_world is [n,3]");
+  auto host = [](const torch::Tensor& t, const char* name) {
+    if (!t.defined() || t.dim() != 2 || t.size(0) < 3)
+      throw std::invalid_argument(std::string(name) + ": a 2-d matrix of at least three rows");
+    return t.to(torch::kCPU, torch::kFloat64).slice(0, 0, 3).to(torch::kFloat32).contiguous();
+  };
+  const torch::Tensor tcw = host(T_cw, "T_cw"), k = host(K, "K");
+  if (tcw.numel() != 12 || k.numel() != 9) throw std::invalid_argument("lidar_depth_image: T_cw is 3x4 or 4x4, K is 3x3");
+  torch::Tensor image = torch::empty({std::max<int64_t>(height, 0), std::max<int64_t>(width, 0)}, p.options());
+  torch::Tensor c2 = counts ? torch::empty({2}, p.options().dtype(torch::kInt32)) : torch::Tensor();
+  check(gsr_lidar_depth_image(static_cast<int>(p.size(0)), fp(p), tcw.data_ptr<float>(), k.data_ptr<float>(),
+                              static_cast<int>(height), static_cast<int>(width), min_depth, max_depth, fp(image),
+                              counts ? c2.data_ptr<int>() : nullptr, current_stream()),
+        "gsr_lidar_depth_image");
+  if (counts) *counts = c2;
+  return image;
+}
+
+torch::Tensor lidar_depth_loss(const torch::Tensor& depth, const torch::Tensor& acc, const torch::Tensor& lidar_depth,
+                               float acc_min, float lambda) {
+  return LidarDepthLossFn::apply(depth, acc, lidar_depth, static_cast<double>(acc_min), static_cast<double>(lambda));
 }
 
 torch::Tensor image_metrics(const torch::Tensor& image, const torch::Tensor& gt, const torch::Tensor& window1d,

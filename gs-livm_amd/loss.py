@@ -2,7 +2,8 @@
 csrc/loss.hip (SURVEY.md section 8(f) "next" row 2), and of its LiDAR similarity loss
 (GaussianModel::compute_min_distance, src/gs/gaussian.cu:87-114) on those of csrc/simi.hip, and of the delta-depth
 term between keyframe pairs (GaussianModel::calcDeltaSimi, src/gs/gaussian.cu:116-199, and the loop around it,
-src/liw/lioOptimization.cpp:1780-1801) on those of csrc/delta.hip."""
+src/liw/lioOptimization.cpp:1780-1801) on those of csrc/delta.hip, and the LiDAR depth supervision of csrc/lidar.hip
+(an extension: a sweep's z-buffer in a keyframe's view and the masked depth L1 of a render against it)."""
 import math
 
 import torch
@@ -120,3 +121,56 @@ def delta_pose(R_src, t_src, R_ref, t_ref):
         return m
     rel = T(R_ref, t_ref) @ torch.linalg.inv(T(R_src, t_src))
     return rel[:3].to(torch.float32)
+
+
+def lidar_depth_image(points_world, T_cw, K, height, width, min_depth=0.2, max_depth=float("inf"), want_counts=False):
+    """The LiDAR depth image of a keyframe, built once when the keyframe is created: the smallest camera-frame z of
+    the sweep's points per pixel, 0 where none lands ([H,W] f32 on the device of points_world [n,3]).  T_cw: 3x4 or 4x4
+    ([R | t], x_c = R x_w + t: `world_to_camera`), K: 3x3 (`raster_K`), both on the host.  min_depth = 0.2 is the
+    rasterizer's near cull.  want_counts adds an int32 device tensor {points kept, pixels hit}."""
+    return _capi.lidar_depth_image(points_world.contiguous(), T_cw, K, height, width, min_depth, max_depth,
+                                   want_counts)
+
+
+class LidarDepthLoss(torch.autograd.Function):
+    """loss = lambda * mean over the supervised pixels of |depth / acc - lidar_depth| as one node (csrc/lidar.hip);
+    supervised: lidar_depth > 0 and acc >= acc_min.  Gradients w.r.t. the rendered depth and silhouette only (the
+    LiDAR image is data), scaled by the upstream scalar.  They move the Gaussians when the view was rendered with
+    depth_gradient=True; without it only the silhouette route does."""
+
+    @staticmethod
+    def forward(ctx, depth, acc, lidar_depth, acc_min, lambda_):
+        need_d, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        out3, gd, ga = _capi.lidar_depth_loss(depth.contiguous(), acc.contiguous(), lidar_depth.contiguous(), acc_min,
+                                              lambda_, want_grad_depth=need_d, want_grad_acc=need_a)
+        ctx.grads = (gd, ga)
+        ctx.parts = out3  # [loss, mean |depth error| in metres, supervised share] for logging
+        return out3[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        gd, ga = ctx.grads
+        return (gd * g if gd is not None else None), (ga * g if ga is not None else None), None, None, None
+
+
+def lidar_depth_loss(depth, acc, lidar_depth, acc_min=0.5, lambda_=1.0):
+    """depth, acc: the second and third outputs of `render` ([H,W] or [1,H,W] f32 on the device, un-normalised);
+    lidar_depth: `lidar_depth_image` of the same view.  acc_min = 0.5 is the threshold of the reference's silhouette
+    masks (lioOptimization.cpp:1786-1792).  Returns the 0-dim loss."""
+    return LidarDepthLoss.apply(depth, acc, lidar_depth, float(acc_min), float(lambda_))
+
+
+def raster_K(width, height, FoVx, FoVy):
+    """The intrinsics under which pixel (u, v) of a LiDAR depth image is pixel (u, v) of a render of the same camera:
+    fx = W / (2 tan(FoVx / 2)), cx = (W - 1) / 2, likewise in y (the rasterizer's ndc2Pix puts the centre of pixel u at
+    ((ndc + 1) W - 1) / 2).  [3,3] float64 on the host."""
+    fx = width / (2.0 * math.tan(FoVx * 0.5))
+    fy = height / (2.0 * math.tan(FoVy * 0.5))
+    return torch.tensor([[fx, 0.0, (width - 1) * 0.5], [0.0, fy, (height - 1) * 0.5], [0.0, 0.0, 1.0]],
+                        dtype=torch.float64)
+
+
+def world_to_camera(camera):
+    """[R | t] with x_c = R x_w + t, [3,4] float32 on the host, from the TRANSPOSED world-to-camera matrix a
+    render_utils.Camera holds (world_view_transform, camera.cu:39-40)."""
+    return camera.Get_world_view_transform().detach().cpu().t()[:3].contiguous().to(torch.float32)

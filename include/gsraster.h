@@ -419,6 +419,47 @@ int gsr_delta_depth_loss(int height, int width, const float* depth_src, const fl
                          float lambda, float* out3, float* warped, float* dL_ddepth_src, float* dL_ddepth_ref,
                          char* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- LiDAR depth supervision: a sweep's z-buffer in a keyframe's view, and the masked depth L1 against it ----
+ * An extension (the reference compares rendered depths with each other only, and its backward drops dL/ddepth): the
+ * consumer of gsr_backward_depth that pins a render to the measured geometry.  Two calls, because they run at
+ * different rates: the image once per keyframe, the loss per view per optimiser iteration.
+ *
+ * gsr_lidar_depth_image: for every point x of points_world (device [n][3] f32)
+ *   p = R x + t,  z = p.z,  (X, Y) = (K p).xy / (K p).z,  (ix, iy) = (floor(X + 0.5), floor(Y + 0.5))
+ * -- pixel u covers [u - 0.5, u + 0.5), the rasterizer's convention -- and lidar_depth[iy][ix] (device [H][W] f32) is
+ * the SMALLEST z of the points of the pixel, 0.0f where there is none; every element is WRITTEN.  T_cw12 (3x4, [R | t],
+ * x_c = R x_w + t) and K9 (3x3) are row-major on the HOST and are read before the call returns; K [R | t] is composed
+ * in double and rounded once.  A point is dropped when a coordinate of x, z, X or Y is not finite, z <= min_depth,
+ * z > max_depth, |X| or |Y| exceeds 2^30 (tested before any conversion to an integer), or the pixel lies outside the
+ * image.  counts2 (nullable, device, 2 ints) = {points kept, pixels hit}.  The minimum is a 32-bit integer atomic on
+ * the bits of the positive float, taken in the image itself: no workspace, no float atomics, and the image does not
+ * depend on the order of the points, bit for bit.  Three launches (one when n == 0, which is legal: an all-zero image
+ * and counts2 = {0, 0}).
+ * Refused (GSR_ERR_INVALID_ARGUMENT, nothing launched or written): n < 0, height or width < 1, height * width >= 2^31,
+ * a null T_cw12, K9 or lidar_depth, a null points_world with n > 0, min_depth not finite or < 0, max_depth not greater
+ * than min_depth (+inf is allowed).
+ *
+ * gsr_lidar_depth_loss: depth = D = sum z alpha T and acc = A = sum alpha T are the rasterizer's second and third
+ * outputs (un-normalised), lidar_depth the image above, all device [H][W] f32.  A pixel is SUPERVISED iff
+ * lidar_depth > 0 and A >= acc_min (false for NaN); on those pixels e = D / A - lidar_depth and
+ *   L = lambda * sum|e| / max(n_sup, 1),   out3 (device) = {L, sum|e| / max(n_sup, 1), n_sup / (H W)}
+ * -- the second value is the mean absolute depth error in metres.  dL_ddepth / dL_dacc (nullable, [H][W]) for upstream
+ * gradient 1, every element WRITTEN:  dL/dD = c sign(e) / A,  dL/dA = -c sign(e) D / A^2,  c = lambda / n_sup, with
+ * sign(0) = 0, exactly 0 on unsupervised pixels, and all zero with out3 = {0, 0, 0} when n_sup == 0.  The normaliser
+ * is the supervised count, not H W: the weight of the term does not depend on the density of the sweep.
+ * Three launches (two without gradients).
+ * Refused (GSR_ERR_INVALID_ARGUMENT, nothing launched or written): height or width < 1, height * width >= 2^31, a null
+ * required pointer, acc_min not finite or <= 0, workspace_bytes below the query (the message names the bytes needed).
+ * The workspace needs no alignment; the query returns 0 for a refused shape.
+ * Both calls: deterministic (fixed-order f64 partial sums narrowed once, integer atomics only), no host
+ * synchronisation, no allocation, the caller's stream only. */
+int gsr_lidar_depth_image(int n, const float* points_world, const float* T_cw12, const float* K9, int height, int width,
+                          float min_depth, float max_depth, float* lidar_depth, int* counts2, void* stream);
+size_t gsr_lidar_depth_loss_workspace(int height, int width);
+int gsr_lidar_depth_loss(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
+                         float acc_min, float lambda, float* out3, float* dL_ddepth, float* dL_dacc, char* workspace,
+                         size_t workspace_bytes, void* stream);
+
 /* ---- the evaluation pass around a forward-only render: PSNR, SSIM and 8-bit frame export ----
  * gsr_image_metrics: out4 (device) = {psnr, ssim, l1, mse} of img against gt, [channels][H][W] device f32, in two
  * launches:
