@@ -70,7 +70,8 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_delta_depth_loss", "gsr_delta_depth_loss_workspace", "gsr_image_metrics",
            "gsr_image_metrics_workspace", "gsr_pack_image_u8", "gsr_pack_depth_u8", "gsr_prune_workspace",
            "gsr_prune_mark", "gsr_prune_compact", "gsr_lidar_depth_image", "gsr_lidar_depth_loss",
-           "gsr_lidar_depth_loss_workspace")
+           "gsr_lidar_depth_loss_workspace", "gsr_density_accumulate", "gsr_densify_workspace", "gsr_densify_mark",
+           "gsr_densify_apply")
 
 
 def lib():
@@ -195,6 +196,14 @@ def lib():
     L.gsr_prune_mark.argtypes = [ci, vp, vp, vp, vp, vp, cf, cf, ci, vp, vp, vp, vp, sz, vp]
     L.gsr_prune_compact.restype = ci
     L.gsr_prune_compact.argtypes = [ci, ci, C.POINTER(vp), C.POINTER(vp), C.POINTER(ci), vp, vp, vp]
+    L.gsr_density_accumulate.restype = ci
+    L.gsr_density_accumulate.argtypes = [ci, vp, vp, vp, vp]
+    L.gsr_densify_workspace.restype = sz
+    L.gsr_densify_workspace.argtypes = [ci]
+    L.gsr_densify_mark.restype = ci
+    L.gsr_densify_mark.argtypes = [ci, vp, vp, cf, cf, ci, vp, vp, vp, vp, sz, vp]
+    L.gsr_densify_apply.restype = ci
+    L.gsr_densify_apply.argtypes = [ci, ci, ci, vp, vp, C.c_ulonglong] + [vp] * 6 + [C.POINTER(vp), C.POINTER(vp), vp, vp]
     L.gsr_init_gaussians.restype = ci
     L.gsr_init_gaussians.argtypes = [ci, ci, vp, vp, vp, cf] + [vp] * 6 + [vp]
     L.gsr_ply_row_floats.restype = sz
@@ -832,3 +841,62 @@ def prune_compact(src, dst, reasons, row_map):
     arr = lambda ts: VP(*[t.data_ptr() if t.numel() else None for t in ts])  # noqa: E731
     _check(lib().gsr_prune_compact(P, n, arr(src), arr(dst), (C.c_int * max(n, 1))(*widths), _ptr(reasons),
                                    C.c_void_p(row_map.data_ptr()), _stream()))
+
+
+# ---- adaptive density control (include/gsraster.h; csrc/densify.hip) ----
+def density_accumulate(radii, dL_dmean2D, stats):
+    """One view's statistics, one launch (include/gsraster.h, gsr_density_accumulate): radii [P] int32 (the forward's),
+    dL_dmean2D [P,3] f32 (the backward's, unscaled), stats [P,3] f32 = {grad_sum, views, max_radius}, updated in place
+    for the visible rows with a finite gradient norm."""
+    P = int(radii.numel())
+    assert radii.is_cuda and radii.is_contiguous() and radii.dtype == torch.int32
+    assert dL_dmean2D.is_cuda and dL_dmean2D.is_contiguous() and dL_dmean2D.dtype == torch.float32
+    assert stats.is_cuda and stats.is_contiguous() and stats.dtype == torch.float32
+    assert tuple(dL_dmean2D.shape) == (P, 3) and tuple(stats.shape) == (P, 3)
+    _check(lib().gsr_density_accumulate(P, _ptr(radii), _ptr(dL_dmean2D), _ptr(stats), _stream()))
+
+
+def densify_mark(stats, scaling_raw, grad_threshold, size_threshold, max_new=None, packed=False):
+    """The clone / split rule, three launches (include/gsraster.h, gsr_densify_mark).  stats / scaling_raw: [P,3] f32.
+    Returns (kinds [P] uint8: 0 none, 1 clone, 2 split; offsets [P+1] int32; counts [3] int32 = {n_new, clones,
+    splits}), device tensors; nothing waits for the device.  offsets and counts are views of ONE int32 [P+4] buffer,
+    which packed=True appends to the result."""
+    P = int(stats.size(0))
+    dev = stats.device
+    for t in (stats, scaling_raw):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (P, 3)
+    kinds = torch.empty((P,), dtype=torch.uint8, device=dev)
+    both = torch.empty((P + 4,), dtype=torch.int32, device=dev)
+    offsets, counts = both[:P + 1], both[P + 1:]
+    nbytes = int(lib().gsr_densify_workspace(P))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    _check(lib().gsr_densify_mark(P, _ptr(stats), _ptr(scaling_raw), float(grad_threshold), float(size_threshold),
+                                  -1 if max_new is None else int(max_new), _ptr(kinds),
+                                  C.c_void_p(offsets.data_ptr()), C.c_void_p(counts.data_ptr()), _ptr(ws), nbytes,
+                                  _stream()))
+    return (kinds, offsets, counts, both) if packed else (kinds, offsets, counts)
+
+
+def densify_apply(P, n_new, kinds, offsets, seed, params6, exp_avg6=None, exp_avg_sq6=None, stats=None):
+    """Clone and split in place, one launch (include/gsraster.h, gsr_densify_apply).  params6: the six raw leaves in
+    the order xyz, features_dc, features_rest, scaling, rotation, opacity as CAPACITY buffers of at least P + n_new
+    rows; exp_avg6 / exp_avg_sq6 (six buffers each, or None) and stats ([., 3] or None) likewise."""
+    P, n_new = int(P), int(n_new)
+    frest = params6[2]
+    M = 1 + (int(frest.size(1)) if frest.numel() else 0)
+    groups = [params6] + [g for g in (exp_avg6, exp_avg_sq6) if g is not None]
+    for g in groups:
+        assert len(g) == 6
+        for t in g:
+            assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32
+            assert t.numel() == 0 or int(t.size(0)) >= P + n_new, "densify_apply: a buffer holds fewer than P + n_new rows"
+    if stats is not None:
+        assert stats.is_cuda and stats.is_contiguous() and stats.dtype == torch.float32
+        assert stats.dim() == 2 and stats.size(1) == 3 and int(stats.size(0)) >= P + n_new
+    assert kinds.is_cuda and kinds.dtype == torch.uint8 and kinds.is_contiguous() and kinds.numel() == P
+    assert offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() == P + 1
+    VP = C.c_void_p * 6
+    arr = lambda ts: None if ts is None else VP(*[t.data_ptr() if t.numel() else None for t in ts])  # noqa: E731
+    _check(lib().gsr_densify_apply(P, M, n_new, _ptr(kinds), C.c_void_p(offsets.data_ptr()),
+                                   int(seed) & 0xFFFFFFFFFFFFFFFF, *[_ptr(t) for t in params6], arr(exp_avg6),
+                                   arr(exp_avg_sq6), _ptr(stats), _stream()))

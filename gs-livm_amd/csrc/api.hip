@@ -133,6 +133,7 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_delta_project", "k_delta_sample", "k_delta_scatter", "k_delta_convert",
     "k_lidar_clear", "k_lidar_splat", "k_lidar_convert", "k_lidar_loss_forward", "k_lidar_loss_finish",
     "k_lidar_loss_grads",
+    "k_density_accumulate", "k_densify_mark", "k_densify_scan", "k_densify_rank", "k_densify_apply",
     "k_metrics_forward", "k_metrics_finalize", "k_pack_image_u8", "k_pack_depth_u8",
     "k_prune_mark", "k_prune_scan", "k_prune_rank", "k_prune_compact"};
 
@@ -1812,6 +1813,68 @@ int gsr_prune_compact(int P, int n_tensors, const float* const* src, float* cons
     if (widths[k] > 0 && (((uintptr_t)src[k] | (uintptr_t)dst[k]) & 3u))
       return fail(GSR_ERR_INVALID_ARGUMENT, "misaligned pointer: float and int32 arrays need 4-byte alignment (tensor %d)", k);
   HIP_TRY(launch_prune_compact(P, n_tensors, src, dst, widths, reasons, row_map, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+static const char* const kMisaligned = "misaligned pointer: float and int32 arrays need 4-byte alignment";
+
+int gsr_density_accumulate(int P, const int* radii, const float* dL_dmean2D, float* stats, void* stream_) {
+  g_err[0] = 0;
+  if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (P == 0) return GSR_OK;
+  if (!radii || !dL_dmean2D || !stats) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (((uintptr_t)radii | (uintptr_t)dL_dmean2D | (uintptr_t)stats) & 3u)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned);
+  HIP_TRY(launch_density_accumulate(P, radii, dL_dmean2D, stats, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+size_t gsr_densify_workspace(int P) {
+  if (P <= 0 || P > GSR_PRUNE_MAX_ROWS) return 0;
+  return densify_workspace_bytes(P);
+}
+
+int gsr_densify_mark(int P, const float* stats, const float* scaling_raw, float grad_threshold, float size_threshold,
+                     int max_new, unsigned char* kinds, int* offsets, int* counts3, char* workspace,
+                     size_t workspace_bytes, void* stream_) {
+  g_err[0] = 0;
+  if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (!offsets || !counts3) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (P > 0 && (!stats || !scaling_raw || !kinds || !workspace)) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (((uintptr_t)stats | (uintptr_t)scaling_raw | (uintptr_t)offsets | (uintptr_t)counts3 | (uintptr_t)workspace) & 3u)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned);
+  if (workspace_bytes < densify_workspace_bytes(P))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes", densify_workspace_bytes(P));
+  HIP_TRY(launch_densify_mark(P, stats, scaling_raw, grad_threshold, size_threshold, max_new, kinds, offsets, counts3,
+                              workspace, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+int gsr_densify_apply(int P, int M, int n_new, const unsigned char* kinds, const int* offsets, unsigned long long seed,
+                      float* xyz, float* features_dc, float* features_rest, float* scaling_raw, float* rotation_raw,
+                      float* opacity_raw, float* const* exp_avg6, float* const* exp_avg_sq6, float* stats,
+                      void* stream_) {
+  g_err[0] = 0;
+  if (P < 0 || n_new < 0 || (long long)P + (long long)n_new > (long long)GSR_PRUNE_MAX_ROWS)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/n_new");
+  if (M < 1 || M > 16) return fail(GSR_ERR_INVALID_ARGUMENT, "bad M");
+  if (P == 0 || n_new == 0) return GSR_OK;
+  float* const params6[6] = {xyz, features_dc, M > 1 ? features_rest : nullptr, scaling_raw, rotation_raw, opacity_raw};
+  if (!kinds || !offsets) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  for (int k = 0; k < 6; k++) {
+    if (k == 2 && M == 1) continue;  // _features_rest at M = 1: its pointers are not looked at
+    if (!params6[k] || (exp_avg6 && !exp_avg6[k]) || (exp_avg_sq6 && !exp_avg_sq6[k]))
+      return fail(GSR_ERR_INVALID_ARGUMENT, "null tensor pointer (group %d)", k);
+  }
+  uintptr_t bits = (uintptr_t)offsets | (uintptr_t)stats;
+  for (int k = 0; k < 6; k++) {
+    if (k == 2 && M == 1) continue;
+    bits |= (uintptr_t)params6[k] | (uintptr_t)(exp_avg6 ? exp_avg6[k] : nullptr) |
+            (uintptr_t)(exp_avg_sq6 ? exp_avg_sq6[k] : nullptr);
+  }
+  if (bits & 3u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned);
+  HIP_TRY(launch_densify_apply(P, M, kinds, offsets, seed, params6, exp_avg6, exp_avg_sq6, stats,
+                               (hipStream_t)stream_));
   return GSR_OK;
 }
 

@@ -486,6 +486,15 @@ hipError_t launch_prune_mark(int P, const float* xyz, const float* scaling_raw, 
 unsigned long long prune_compact_blocks(int P, int n, const int* widths);
 hipError_t launch_prune_compact(int P, int n, const float* const* src, float* const* dst, const int* widths,
                                 const unsigned char* reasons, const int* row_map, hipStream_t s);
+// densify.hip (adaptive density control: the gradient statistics, the clone / split marks, the in-place surgery)
+size_t densify_workspace_bytes(int P);
+hipError_t launch_density_accumulate(int P, const int* radii, const float* dL_dmean2D, float* stats, hipStream_t s);
+hipError_t launch_densify_mark(int P, const float* stats, const float* scaling_raw, float grad_threshold,
+                               float size_threshold, int max_new, unsigned char* kinds, int* offsets, int* counts3,
+                               char* workspace, hipStream_t s);
+hipError_t launch_densify_apply(int P, int M, const unsigned char* kinds, const int* offsets, unsigned long long seed,
+                                float* const* params6, float* const* exp_avg6, float* const* exp_avg_sq6, float* stats,
+                                hipStream_t s);
 
 inline int sort_passes(int end_bit) { return (end_bit + 7) / 8; }
 // digit width: the key bits are split evenly over the passes (13 tile bits -> 7 + 6, 32 depth bits -> 4 x 8)
@@ -501,6 +510,7 @@ enum KernelId {
   K_DELTA_PROJECT, K_DELTA_SAMPLE, K_DELTA_SCATTER, K_DELTA_CONVERT,
   // (beside the other depth term; ids are looked up by name, and the prune kernels stay the last four)
   K_LIDAR_CLEAR, K_LIDAR_SPLAT, K_LIDAR_CONVERT, K_LIDAR_LOSS_FWD, K_LIDAR_LOSS_FINISH, K_LIDAR_LOSS_GRADS,
+  K_DENSITY_ACCUMULATE, K_DENSIFY_MARK, K_DENSIFY_SCAN, K_DENSIFY_RANK, K_DENSIFY_APPLY,
   K_METRICS_FWD, K_METRICS_FINALIZE, K_PACK_IMAGE_U8, K_PACK_DEPTH_U8,
   K_PRUNE_MARK, K_PRUNE_SCAN, K_PRUNE_RANK, K_PRUNE_COMPACT, K_COUNT
 };

@@ -181,6 +181,23 @@ PruneMarks prune_mark(const torch::Tensor& xyz, const torch::Tensor& scaling_raw
 std::vector<torch::Tensor> prune_rows(const std::vector<torch::Tensor>& tensors, const torch::Tensor& reasons,
                                       const torch::Tensor& row_map, int64_t P_new);
 
+// ---- adaptive density control (an extension: the reference carries densification_postfix and never runs the loop) ------
+// Thin tensor-level hosts of csrc/densify.hip; include/gsraster.h has the contract (the rule, the generator, what is
+// written and what is not).  All device tensors, nothing waits.  (Not part of the oracle/ref_link link check either.)
+// stats [P,3] f32 {grad_sum, views, max_radius} is updated in place from one view's radii [P] int32 and dL_dmean2D [P,3].
+void density_accumulate(const torch::Tensor& radii, const torch::Tensor& dL_dmean2D, torch::Tensor stats);
+struct DensifyMarks {
+  torch::Tensor kinds, offsets, counts;  // [P] uint8 (0 none, 1 clone, 2 split), [P+1] int32, [3] int32 {n_new, clones, splits}
+};
+DensifyMarks densify_mark(const torch::Tensor& stats, const torch::Tensor& scaling_raw, float grad_threshold,
+                          float size_threshold, int64_t max_new = -1);
+// In place on capacity buffers of at least P + n_new rows: params6 in the order xyz, features_dc, features_rest, scaling,
+// rotation, opacity; exp_avg6 / exp_avg_sq6 six buffers each or empty vectors; stats [., 3] or undefined.  n_new =
+// offsets[P], which the caller has fetched.
+void densify_apply(int64_t P, int64_t n_new, const torch::Tensor& kinds, const torch::Tensor& offsets, uint64_t seed,
+                   const std::vector<torch::Tensor>& params6, const std::vector<torch::Tensor>& exp_avg6,
+                   const std::vector<torch::Tensor>& exp_avg_sq6, const torch::Tensor& stats = torch::Tensor());
+
 // ---- row 4: map growth and PLY export ---------------------------------------------------------------------------
 // The tensor construction of GaussianModel::addNewPointcloud (src/gs/gaussian.cu:241-313) for n new points -- xyz
 // [n,3], covs [n,3,3], rgbs [n,3] in 0..255 -- written IN PLACE into n-row views (normally the tail rows of capacity

@@ -515,6 +515,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("min_opacity") = 1.0f / 255.0f, py::arg("max_scale") = 0.3f, py::arg("drop_nonfinite") = true,
         py::arg("drop") = py::none());
   n.def("prune_rows", &nx::prune_rows, py::arg("tensors"), py::arg("reasons"), py::arg("row_map"), py::arg("P_new"));
+  n.def("density_accumulate", &nx::density_accumulate, py::arg("radii"), py::arg("dL_dmean2D"), py::arg("stats"));
+  n.def("densify_mark",
+        [](torch::Tensor stats, torch::Tensor s, float grad_threshold, float size_threshold, int64_t max_new) {
+          const nx::DensifyMarks d = nx::densify_mark(stats, s, grad_threshold, size_threshold, max_new);
+          return std::make_tuple(d.kinds, d.offsets, d.counts);
+        },
+        py::arg("stats"), py::arg("scaling_raw"), py::arg("grad_threshold"), py::arg("size_threshold"),
+        py::arg("max_new") = -1);
+  n.def("densify_apply",
+        [opt](int64_t P, int64_t n_new, torch::Tensor kinds, torch::Tensor offsets, uint64_t seed,
+              std::vector<torch::Tensor> params6, std::vector<torch::Tensor> exp_avg6,
+              std::vector<torch::Tensor> exp_avg_sq6, py::object stats) {
+          nx::densify_apply(P, n_new, kinds, offsets, seed, params6, exp_avg6, exp_avg_sq6, opt(stats));
+        },
+        py::arg("P"), py::arg("n_new"), py::arg("kinds"), py::arg("offsets"), py::arg("seed"), py::arg("params6"),
+        py::arg("exp_avg6") = std::vector<torch::Tensor>(), py::arg("exp_avg_sq6") = std::vector<torch::Tensor>(),
+        py::arg("stats") = py::none());
   n.def("init_gaussians", &nx::init_gaussians);
   n.def("pack_ply_rows", &nx::pack_ply_rows);
   n.def("write_ply", &nx::write_ply);

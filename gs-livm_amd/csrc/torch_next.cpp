@@ -534,6 +534,70 @@ PruneMarks prune_mark(const torch::Tensor& xyz, const torch::Tensor& scaling_raw
   return out;
 }
 
+void density_accumulate(const torch::Tensor& radii, const torch::Tensor& dL_dmean2D, torch::Tensor stats) {
+  torch::NoGradGuard no_grad;
+  const int64_t P = radii.numel();
+  if (!radii.is_cuda() || radii.scalar_type() != torch::kInt32 || !radii.is_contiguous())
+    throw std::invalid_argument("density_accumulate: radii is a contiguous int32 device tensor");
+  const torch::Tensor g = dev_f32(dL_dmean2D, "dL_dmean2D");
+  if (!stats.defined() || !stats.is_cuda() || stats.scalar_type() != torch::kFloat32 || !stats.is_contiguous() ||
+      stats.numel() != 3 * P || g.numel() != 3 * P)
+    throw std::invalid_argument("density_accumulate: dL_dmean2D [P,3], stats [P,3] contiguous f32 on the device");
+  check(gsr_density_accumulate(static_cast<int>(P), P ? radii.data_ptr<int>() : nullptr, fp(g), fp(stats),
+                               current_stream()),
+        "gsr_density_accumulate");
+}
+
+DensifyMarks densify_mark(const torch::Tensor& stats, const torch::Tensor& scaling_raw, float grad_threshold,
+                          float size_threshold, int64_t max_new) {
+  torch::NoGradGuard no_grad;
+  const torch::Tensor st = dev_f32(stats, "stats"), s = dev_f32(scaling_raw, "_scaling");
+  const int64_t P = st.size(0);
+  if (st.numel() != 3 * P || s.numel() != 3 * P) throw std::invalid_argument("densify_mark: stats [P,3], scaling [P,3]");
+  const auto bytes = st.options().dtype(torch::kByte), ints = st.options().dtype(torch::kInt32);
+  DensifyMarks out{torch::empty({P}, bytes), torch::empty({P + 1}, ints), torch::empty({3}, ints)};
+  const size_t nbytes = gsr_densify_workspace(static_cast<int>(P));
+  torch::Tensor ws = torch::empty({static_cast<long long>(nbytes ? nbytes : 1)}, bytes);
+  check(gsr_densify_mark(static_cast<int>(P), fp(st), fp(s), grad_threshold, size_threshold,
+                         max_new < 0 ? -1 : static_cast<int>(std::min<int64_t>(max_new, 0x7fffffff)),
+                         P ? out.kinds.data_ptr<unsigned char>() : nullptr, out.offsets.data_ptr<int>(),
+                         out.counts.data_ptr<int>(), reinterpret_cast<char*>(ws.data_ptr()), nbytes, current_stream()),
+        "gsr_densify_mark");
+  return out;
+}
+
+void densify_apply(int64_t P, int64_t n_new, const torch::Tensor& kinds, const torch::Tensor& offsets, uint64_t seed,
+                   const std::vector<torch::Tensor>& params6, const std::vector<torch::Tensor>& exp_avg6,
+                   const std::vector<torch::Tensor>& exp_avg_sq6, const torch::Tensor& stats) {
+  torch::NoGradGuard no_grad;
+  if (P < 0 || n_new < 0 || P + n_new > GSR_PRUNE_MAX_ROWS) throw std::invalid_argument("densify_apply: bad P / n_new");
+  if (!kinds.is_cuda() || kinds.scalar_type() != torch::kByte || !kinds.is_contiguous() || kinds.numel() != P ||
+      !offsets.is_cuda() || offsets.scalar_type() != torch::kInt32 || !offsets.is_contiguous() || offsets.numel() != P + 1)
+    throw std::invalid_argument("densify_apply: kinds [P] uint8 and offsets [P+1] int32 on the device, from densify_mark");
+  if (params6.size() != 6 || (!exp_avg6.empty() && exp_avg6.size() != 6) ||
+      (!exp_avg_sq6.empty() && exp_avg_sq6.size() != 6))
+    throw std::invalid_argument("densify_apply: six leaves; six moments of a kind or none");
+  // the surgery is in place: a buffer is taken as it is, never copied
+  auto buffer = [&](const torch::Tensor& t) {
+    if (!t.defined() || !t.is_cuda() || t.scalar_type() != torch::kFloat32 || !t.is_contiguous() ||
+        (t.numel() && t.size(0) < P + n_new))
+      throw std::invalid_argument("densify_apply: expected contiguous float32 device buffers of at least P + n_new rows");
+    return fp(t);
+  };
+  float *p[6], *m[6], *v[6];
+  for (int k = 0; k < 6; k++) {
+    p[k] = buffer(params6[k]);
+    m[k] = exp_avg6.empty() ? nullptr : buffer(exp_avg6[k]);
+    v[k] = exp_avg_sq6.empty() ? nullptr : buffer(exp_avg_sq6[k]);
+  }
+  const int M = 1 + static_cast<int>(params6[2].numel() ? params6[2].size(1) : 0);
+  check(gsr_densify_apply(static_cast<int>(P), M, static_cast<int>(n_new), P ? kinds.data_ptr<unsigned char>() : nullptr,
+                          offsets.data_ptr<int>(), seed, p[0], p[1], p[2], p[3], p[4], p[5],
+                          exp_avg6.empty() ? nullptr : m, exp_avg_sq6.empty() ? nullptr : v,
+                          stats.defined() ? buffer(stats) : nullptr, current_stream()),
+        "gsr_densify_apply");
+}
+
 namespace {
 // dst[k][row_map[i]] = src[k][i] where reasons[i] == 0, at most eighteen tensors: one launch
 void compact18(const std::vector<torch::Tensor>& src, const std::vector<torch::Tensor>& dst, const torch::Tensor& reasons,

@@ -13,6 +13,9 @@ kernels of csrc/optimizer.hip (SURVEY.md section 8(f) "next" row 1):
   * `GrowableGaussians.prune` / `prune_rows` -- the shrinking half, GaussianModel::prune_optimizer (gaussian.cu:430-449,
     which the reference carries and never calls): rows that are dead to the rasterizer for good leave the leaves, the
     Adam moments and the voxel index by a stable compaction (csrc/prune.hip);
+  * `GrowableGaussians.enable_density_stats` / `accumulate_density` / `densify` -- adaptive density control, upstream's
+    clone and split (N = 2) of which the reference carries the remains (densification_postfix, gaussian.cu:521-540) and
+    never runs: in place on the capacity buffers, existing rows keeping their numbers (csrc/densify.hip);
   * `VoxelIndex` -- gs_hash_indexes_ (voxel key -> rows of its Gaussians, gaussian.cu:257-263) and the selection
     of calcSimiLoss (:201-228) on row RANGES, which feeds the fused similarity loss (csrc/simi.hip, loss.py).
 """
@@ -316,6 +319,7 @@ class GrowableGaussians(GaussianParameters):
         self.M, self.P, self.capacity, self.device = int(M), 0, 0, torch.device(device)
         self._buf, self._m, self._v = {}, {}, {}
         self._optimizer = None
+        self._stats = None  # [capacity, 3] {grad_sum, views, max_radius}: enable_density_stats()
         self.voxel_index = VoxelIndex(self.device)  # gs_hash_indexes_
         self._reserve(max(1, int(capacity)))
         self._bind()
@@ -331,6 +335,10 @@ class GrowableGaussians(GaussianParameters):
                 if name in store and self.P:
                     new[:self.P].copy_(store[name][:self.P])
                 store[name] = new
+        if self._stats is not None:
+            new = torch.zeros((capacity, 3), dtype=torch.float32, device=self.device)
+            new[:self.P].copy_(self._stats[:self.P])
+            self._stats = new
         self.capacity = capacity
 
     def _bind(self):
@@ -421,10 +429,76 @@ class GrowableGaussians(GaussianParameters):
                 src.append(store[name][:P])
                 dst.append(new[name])
         _capi.prune_compact(src, dst, reasons, row_map)
+        if self._stats is not None:  # the statistics follow their rows (a second launch: the first carries 18 tensors)
+            stats = torch.zeros((self.capacity, 3), dtype=torch.float32, device=self.device)
+            _capi.prune_compact([self._stats[:P]], [stats], reasons, row_map)
+            self._stats = stats
         self._buf, self._m, self._v = fresh
         self.P = P_new
         self._bind()
         self.voxel_index.remap(row_map_host)
+        return out
+
+    @torch.no_grad()
+    def enable_density_stats(self):
+        """Creates the zero [capacity, 3] statistics buffer {grad_sum, views, max_radius} that accumulate_density
+        fills and densify reads.  A model that never calls this runs none of the density-control code."""
+        if self._stats is None:
+            self._stats = torch.zeros((self.capacity, 3), dtype=torch.float32, device=self.device)
+
+    def density_stats(self):
+        """The statistics of the P rows, a [P, 3] view (None before enable_density_stats)."""
+        return None if self._stats is None else self._stats[:self.P]
+
+    @torch.no_grad()
+    def accumulate_density(self, radii, means2D_grad):
+        """One view's statistics, one launch, after that view's backward: radii [P] int32 as the forward returned them,
+        means2D_grad [P,3] = the .grad of the means2D leaf (render_utils.render_full), unscaled.  Rows the view did
+        not see (radii <= 0) and rows with a non-finite gradient norm are not touched."""
+        if self._stats is None:
+            raise RuntimeError("accumulate_density: call enable_density_stats() first")
+        if int(radii.numel()) != self.P or tuple(means2D_grad.shape) != (self.P, 3):
+            raise ValueError("accumulate_density: the model has %d rows" % self.P)
+        if self.P:
+            _capi.density_accumulate(radii.contiguous(), means2D_grad.contiguous(), self._stats[:self.P])
+
+    @torch.no_grad()
+    def densify(self, grad_threshold, size_threshold, max_new=None, seed=0):
+        """Adaptive density control, the growing counterpart of prune (upstream's densify_and_clone and
+        densify_and_split with N = 2; include/gsraster.h has the full contract).  A row whose mean view-space gradient
+        norm grad_sum / views is >= grad_threshold (in the units of gsr_backward's dL_dmean2D, unscaled) is a candidate:
+        with max exp(_scaling) <= size_threshold it is CLONED -- the copy is appended, the parent keeps its Adam
+        moments, the copy starts with zeros --, above it it is SPLIT -- the parent becomes the first child in place, the
+        second child is appended, both 1.6 times smaller, displaced by normal samples of the parent's own shape, with
+        zero moments.  Every candidate appends exactly one row; max_new caps the rows added (the first max_new
+        candidates in row order win); the samples depend on (seed, row, child) only.
+        Existing rows keep their numbers, so a `sel` taken from `voxel_index.select` BEFORE densify remains valid and
+        `voxel_index` is unchanged.  The appended rows belong to NO voxel of `voxel_index`: the similarity loss never
+        selects them, and a later prune moves them like any other row.
+        Cost: four launches and ONE host wait (the copy of the offsets, which carries the count); when the capacity is
+        exceeded the buffers grow first, as in add_new_pointcloud.  The statistics are zero afterwards.  When nothing is
+        added nothing is re-bound: leaf objects and cached activations survive; otherwise the leaves are new Parameter
+        objects and cached activations and parked gradients are dropped.
+        Returns {"P_before", "P_after", "n_new", "n_clone", "n_split", "kinds": [P] uint8 on the device (0 none,
+        1 clone, 2 split), "offsets": [P+1] int32 on the host, row i's new row is P_before + offsets[i]}."""
+        if self._stats is None:
+            raise RuntimeError("densify: call enable_density_stats() first")
+        P, b = self.P, self._buf
+        kinds, offsets, _, both = _capi.densify_mark(self._stats[:P], b["_scaling"][:P], grad_threshold, size_threshold,
+                                                     max_new, packed=True)
+        host = both.cpu()  # the one host wait
+        n_new, n_clone, n_split = (int(c) for c in host[P + 1:])
+        out = dict(P_before=P, P_after=P + n_new, n_new=n_new, n_clone=n_clone, n_split=n_split, kinds=kinds,
+                   offsets=host[:P + 1])
+        if n_new:
+            if P + n_new > self.capacity:
+                self._reserve(max(2 * self.capacity, P + n_new))
+            b = self._buf
+            _capi.densify_apply(P, n_new, kinds, offsets, seed, [b[n] for n in self._NAMES],
+                                [self._m[n] for n in self._NAMES], [self._v[n] for n in self._NAMES], self._stats)
+            self.P = P + n_new
+            self._bind()
+        self._stats[:self.P].zero_()
         return out
 
     def calc_simi_loss(self, losses, lambda_=0.2, scaling=None, max_points=500, generator=None):

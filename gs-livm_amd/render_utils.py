@@ -61,6 +61,14 @@ def render(viewpoint_camera, gaussian_model, bg_color, scaling_modifier=1.0, ove
     """-> (color [3,H,W], depth [1,H,W], depth_acc [1,H,W]); render_utils.cuh:13-56.
     depth_gradient=True (an extension): a loss on `depth` trains the Gaussians; by default its gradient stops at the
     rasterizer, as in the reference."""
+    return render_full(viewpoint_camera, gaussian_model, bg_color, scaling_modifier, override_color, depth_gradient)[:3]
+
+
+def render_full(viewpoint_camera, gaussian_model, bg_color, scaling_modifier=1.0, override_color=None,
+                depth_gradient=False):
+    """`render` with the two outputs adaptive density control needs (upstream's render returns them too):
+    -> (color, depth, depth_acc, radii [P] int32, means2D).  means2D is the [P,3] zero leaf whose .grad the backward
+    fills with dL_dmean2D, unscaled: after loss.backward(), GrowableGaussians.accumulate_density(radii, means2D.grad)."""
     cam = viewpoint_camera
     dev = gaussian_model.Get_xyz().device
     settings = GaussianRasterizationSettings(
@@ -83,4 +91,4 @@ def render(viewpoint_camera, gaussian_model, bg_color, scaling_modifier=1.0, ove
     else:
         color, radii, depth, depth_acc = rasterizer(means3D, means2D, opacity, shs=shs, scales=scales,
                                                     rotations=rotations)
-    return color, depth, depth_acc
+    return color, depth, depth_acc, radii, means2D

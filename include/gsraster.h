@@ -564,6 +564,75 @@ int gsr_prune_mark(int P, const float* xyz, const float* scaling_raw, const floa
 int gsr_prune_compact(int P, int n_tensors, const float* const* src, float* const* dst, const int* widths,
                       const unsigned char* reasons, const int* row_map, void* stream);
 
+/* ---- adaptive density control: clone and split where the photometric gradient asks for it (an extension) ----
+ * The growing counterpart of pruning.  The reference carries the remains of it (densification_postfix,
+ * src/gs/gaussian.cu:521-540; the commented _xyz_gradient_accum / _max_radii2D, :362, :398, :535-537;
+ * cat_tensors_to_optimizer, :451-472) and never runs the loop; the rule is upstream 3D Gaussian splatting's
+ * densify_and_clone / densify_and_split with N = 2.  When to densify and with which thresholds stays with the caller.
+ *
+ * stats [P][3] f32, one row per Gaussian: {grad_sum, views, max_radius} -- all floats, so that gsr_prune_compact moves
+ * the row as one tensor of width 3 (counts and radii stay far below 2^24).
+ *
+ * gsr_density_accumulate (ONE launch per view, after that view's gsr_backward): for a row with radii[i] > 0 and a
+ * finite n = sqrtf(gx * gx + gy * gy): grad_sum += n, views += 1, max_radius = max(max_radius, (float)radii[i]); any
+ * other row is not touched.  gx, gy are dL_dmean2D[i][0], [i][1] exactly as gsr_backward writes them -- the quantity
+ * upstream's viewspace_point_tensor.grad carries; NO rescaling (by the image size or otherwise) is applied, and
+ * grad_threshold below is in those units.  radii [P] int32 is the forward's output.  The products, the sum, the square
+ * root and the additions are single float32 operations (no contraction), so a host restates the row bit for bit.
+ *
+ * gsr_densify_mark (three launches).  Per row: avg = views > 0 ? grad_sum / views : 0.  The row is a CANDIDATE iff
+ * avg >= grad_threshold (upstream's >=; a NaN compares false) and all three scaling_raw entries are finite.  A
+ * candidate is BIG iff max_k expf(scaling_raw[k]) > size_threshold -- gsr_activate's expf bit for bit, the comparison
+ * strict as in the prune rule (a scale ON the threshold is not big).
+ *   kinds [P] uint8: 0 = none, 1 = clone (candidate, not big), 2 = split (candidate, big).
+ *   Every candidate adds exactly ONE row.  offsets [P + 1] int32: the exclusive prefix sum of "candidate", capped at
+ *   max_new (max_new < 0: unlimited); offsets[P] = n_new.  A candidate whose uncapped offset is >= max_new gets kind 0:
+ *   THE FIRST max_new CANDIDATES IN ROW ORDER WIN.
+ *   counts3 [3] int32 = {n_new, clones accepted, splits accepted}.
+ * workspace: gsr_densify_workspace(P) bytes -- two int32 per 256 rows, nothing per row beyond the two outputs.
+ *
+ * gsr_densify_apply (ONE launch, one thread per source row), in place on capacity buffers that the caller guarantees
+ * to hold P + n_new rows; kinds / offsets / n_new = offsets[P] are gsr_densify_mark's.  The six leaves are the raw
+ * parameters xyz [.][3], features_dc [.][1][3], features_rest [.][M-1][3], scaling_raw [.][3], rotation_raw [.][4],
+ * opacity_raw [.][1]; exp_avg6 / exp_avg_sq6 are HOST arrays of six device pointers in that order (each array may be
+ * null as a whole: no moments of that kind), stats may be null.  At M = 1 features_rest and entry [2] of the moment
+ * arrays are not looked at.  With j = P + offsets[i]:
+ *   kind 1, clone: row j of all six leaves = row i, bit for bit; both moments of row j are WRITTEN as zeros in all six
+ *     groups; stats row j = 0; row i, its moments and its stats row are untouched (upstream's clone: the parent keeps its
+ *     optimiser state, the copy starts fresh).
+ *   kind 2, split (upstream's N = 2, laid out without a compaction): the parent row i becomes child 0 IN PLACE -- every
+ *     existing row keeps its number and child 0 stays inside its voxel's row range -- and child 1 is written to row j.
+ *     xyz_c = xyz_i + R (sigma * z_c), sigma_k = expf(scaling_raw[i][k]), R the rotation matrix of the quaternion as
+ *     gsr_activate normalises it (q / max(|q|, 1e-12), component order w, x, y, z); scaling_c = scaling_raw[i] -
+ *     0.47000363f (ln 1.6 = upstream's log(scale / (0.8 N)) with one rounding); rotation, opacity and all SH rows are
+ *     copied; both moments of rows i AND j are zero in all six groups (upstream's children are fresh parameters); the
+ *     stats rows i and j are zero.
+ *   kind 0: the row is not read beyond kinds[i].  No row >= P + n_new is written.
+ * The normals z_c come from a counter-based generator, so that any host can restate them: Philox4x32-10 (multipliers
+ * D2511F53, CD9E8D57; key increments 9E3779B9, BB67AE85) with key = (seed & 0xffffffff, seed >> 32) and counter =
+ * (i, c, 0, 0) gives o_0..o_3; u_k = ((o_k >> 9) + 0.5) * 2^-23 -- exact in float32 (2n + 1 < 2^24) and strictly inside
+ * (0, 1), u >= 2^-24; r1 = sqrtf(-2 logf(u_0)), t1 = 6.2831855f * u_1, r2 = sqrtf(-2 logf(u_2)), t2 = 6.2831855f * u_3;
+ * z = (r1 cosf(t1), r1 sinf(t1), r2 cosf(t2)).  (23 bits rather than 24: with 24, n + 0.5 needs 25 significant bits
+ * for n >= 2^23 and would be rounded.)  A child depends on (seed, i, c) and its own row only: bitwise reproducible,
+ * independent of P, of the launch shape and of which other rows are marked.
+ * Alignment: contiguous tensors at their element's alignment, 4 bytes (kinds: 1); any other offset is refused.
+ * Refused (GSR_ERR_INVALID_ARGUMENT, nothing enqueued or written), in this order: shape (P < 0, P or P + n_new beyond
+ * GSR_PRUNE_MAX_ROWS, n_new < 0, M outside 1..16); a null required pointer; a misaligned pointer; workspace_bytes
+ * below the query (the message names the bytes needed).  P == 0 and n_new == 0 are legal and touch no row:
+ * gsr_densify_mark then writes offsets[0] = 0 and counts3 = {0, 0, 0} (only those two are required), the other two
+ * return at once.  The query returns 0 for P <= 0 and for a refused P.
+ * Deterministic (no atomics, no workgroup waits for another), no host synchronisation, no allocation, the caller's
+ * stream only. */
+int gsr_density_accumulate(int P, const int* radii, const float* dL_dmean2D, float* stats, void* stream);
+size_t gsr_densify_workspace(int P);
+int gsr_densify_mark(int P, const float* stats, const float* scaling_raw, float grad_threshold, float size_threshold,
+                     int max_new, unsigned char* kinds, int* offsets, int* counts3, char* workspace,
+                     size_t workspace_bytes, void* stream);
+int gsr_densify_apply(int P, int M, int n_new, const unsigned char* kinds, const int* offsets, unsigned long long seed,
+                      float* xyz, float* features_dc, float* features_rest, float* scaling_raw, float* rotation_raw,
+                      float* opacity_raw, float* const* exp_avg6, float* const* exp_avg_sq6, float* stats,
+                      void* stream);
+
 /* Optional per-kernel device timing (hipEvent pairs recorded on the launch stream around every
  * kernel launch while enabled).  Measurement aid for bench.py's roofline line; the reference has only
  * host wall-clock timers (include/common/timer/timer.h:36-52).  Not thread-safe; off by default.
