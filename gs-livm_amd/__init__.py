@@ -18,7 +18,7 @@ The directory is named `gs-livm_amd`; import it as `gs_livm_amd` (alias module a
 from . import multiview, synthetic  # noqa: F401
 from ._capi import (GsrError, LIB_PATH, NumRendered, emit_guard_trips, last_num_rendered, lib, mailbox_slow_path_last, mark_visible,
                     set_binning_capacity_hint, speculation_stats, set_near_far, set_near_far_thread, set_reference_rects_thread, async_outcomes_pending, set_near_far_hints, last_near_far, set_far_speculation, last_far_skipped, profile_enable, profile_read,  # noqa: F401
-                    rasterize_backward, rasterize_forward, reference_rects, set_reference_rects, state_views)
+                    pose_gradient, rasterize_backward, rasterize_forward, reference_rects, set_reference_rects, state_views)
 from .loss import (DeltaDepthLoss, LidarDepthLoss, PhotometricLoss, SimilarityLoss, delta_depth_loss, delta_pose,  # noqa: F401
                    lidar_depth_image, lidar_depth_loss, photometric_loss, raster_K, reference_window_1d, similarity_loss,
                    world_to_camera)
@@ -27,7 +27,7 @@ from .model import FusedActivations, FusedAdam, GaussianParameters, GrowableAdam
 from . import ply  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer,  # noqa: F401
                          rasterize_gaussians)
-from .render_utils import Camera, get_projection_matrix, render  # noqa: F401
+from .render_utils import Camera, get_projection_matrix, render, render_full, se3_exp  # noqa: F401
 
 
 
@@ -47,5 +47,5 @@ def torch_ops():
     return mod
 
 
-__all__ = ["LidarDepthLoss", "lidar_depth_image", "lidar_depth_loss", "raster_K", "world_to_camera", "prune_rows", "image_metrics", "psnr", "to_u8", "side_by_side", "depth_to_u8", "evaluate_keyframes", "DeltaDepthLoss", "delta_depth_loss", "delta_pose", "SimilarityLoss", "similarity_loss", "VoxelIndex", "PhotometricLoss", "photometric_loss", "reference_window_1d", "FusedActivations", "FusedAdam", "GaussianParameters", "GrowableAdam", "GrowableGaussians", "ply", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "Camera", "render", "get_projection_matrix", "rasterize_forward",
+__all__ = ["LidarDepthLoss", "lidar_depth_image", "lidar_depth_loss", "raster_K", "world_to_camera", "prune_rows", "image_metrics", "psnr", "to_u8", "side_by_side", "depth_to_u8", "evaluate_keyframes", "DeltaDepthLoss", "delta_depth_loss", "delta_pose", "SimilarityLoss", "similarity_loss", "VoxelIndex", "PhotometricLoss", "photometric_loss", "reference_window_1d", "FusedActivations", "FusedAdam", "GaussianParameters", "GrowableAdam", "GrowableGaussians", "ply", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "Camera", "render", "render_full", "se3_exp", "pose_gradient", "get_projection_matrix", "rasterize_forward",
            "rasterize_backward", "mark_visible", "state_views", "set_reference_rects", "reference_rects", "last_num_rendered", "set_binning_capacity_hint", "speculation_stats", "emit_guard_trips", "mailbox_slow_path_last", "set_near_far", "set_near_far_thread", "set_reference_rects_thread", "async_outcomes_pending", "set_near_far_hints", "last_near_far", "set_far_speculation", "last_far_skipped", "NumRendered", "lib", "torch_ops", "synthetic", "multiview", "GsrError", "LIB_PATH"]

@@ -71,7 +71,7 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_image_metrics_workspace", "gsr_pack_image_u8", "gsr_pack_depth_u8", "gsr_prune_workspace",
            "gsr_prune_mark", "gsr_prune_compact", "gsr_lidar_depth_image", "gsr_lidar_depth_loss",
            "gsr_lidar_depth_loss_workspace", "gsr_density_accumulate", "gsr_densify_workspace", "gsr_densify_mark",
-           "gsr_densify_apply")
+           "gsr_densify_apply", "gsr_pose_gradient", "gsr_pose_gradient_workspace")
 
 
 def lib():
@@ -96,6 +96,10 @@ def lib():
     L.gsr_backward_depth.argtypes = L.gsr_backward.argtypes[:25] + [vp] + L.gsr_backward.argtypes[25:34] + [vp, ci, vp]
     L.gsr_mark_visible.restype = ci
     L.gsr_mark_visible.argtypes = [ci, vp, vp, vp, vp, vp]
+    L.gsr_pose_gradient_workspace.restype = sz
+    L.gsr_pose_gradient_workspace.argtypes = [ci]
+    L.gsr_pose_gradient.restype = ci
+    L.gsr_pose_gradient.argtypes = [ci, ci, ci, vp, vp, cf, vp, vp, vp, vp, cf, cf, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     for n in ("gsr_geometry_bytes", "gsr_binning_bytes"):
         getattr(L, n).restype = sz
         getattr(L, n).argtypes = [ci]
@@ -354,6 +358,28 @@ def rasterize_backward(background, means3D, radii, colors, scales, rotations, sc
     if return_conic:
         out = out + (dL_dconic,)
     return out + (dL_ddepths,) if grad_depth is not None else out
+
+
+def pose_gradient(means3D, radii, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx,
+                  tan_fovy, image_height, image_width, dL_dmeans2D, dL_dconic, dL_dmeans3D, dL_ddepths=None,
+                  workspace=None):
+    """gsr_pose_gradient behind a rasterize_backward(..., return_conic=True) over the same inputs: dL/dxi [6] float32
+    (device) of the left perturbation T_cw <- Exp(xi^) T_cw at xi = 0, [0:3] translation, [3:6] rotation, camera axes
+    (include/gsraster.h).  dL_ddepths: that backward's last output when it was given grad_depth, else None."""
+    dev = means3D.device
+    P = int(means3D.size(0))
+    L = lib()
+    need = int(L.gsr_pose_gradient_workspace(P))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty(6, dtype=torch.float32, device=dev)
+    rotations = _rot16(rotations)
+    _check(L.gsr_pose_gradient(P, int(image_width), int(image_height), _ptr(means3D), _ptr(scales),
+                               float(scale_modifier), _ptr(rotations), _ptr(cov3D_precomp), _ptr(viewmatrix),
+                               _ptr(projmatrix), float(tan_fovx), float(tan_fovy), _ptr(radii), _ptr(dL_dmeans2D),
+                               _ptr(dL_dconic), _ptr(dL_ddepths), _ptr(dL_dmeans3D), _ptr(out), _ptr(workspace),
+                               workspace.numel(), _stream()))
+    return out
 
 
 def last_num_rendered():

@@ -25,6 +25,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
+#include <cmath>
 #include <unordered_map>
 #include <vector>
 
@@ -134,6 +135,7 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_lidar_clear", "k_lidar_splat", "k_lidar_convert", "k_lidar_loss_forward", "k_lidar_loss_finish",
     "k_lidar_loss_grads",
     "k_density_accumulate", "k_densify_mark", "k_densify_scan", "k_densify_rank", "k_densify_apply",
+    "k_pose_partials", "k_pose_finish",
     "k_metrics_forward", "k_metrics_finalize", "k_pack_image_u8", "k_pack_depth_u8",
     "k_prune_mark", "k_prune_scan", "k_prune_rank", "k_prune_compact"};
 
@@ -1503,6 +1505,36 @@ int gsr_backward_depth(int P, int D, int M, int R, const float* background, int 
                        rotations, cov3D_precomp, viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, radii, geom_buffer,
                        binning_buffer, image_buffer, dL_dpix, dL_dacc, dL_ddepth, dL_dmean2D, dL_dconic, dL_dopacity,
                        dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot, dL_ddepths, debug, stream_);
+}
+
+size_t gsr_pose_gradient_workspace(int P) { return P < 0 ? 0 : pose_workspace_bytes(P); }
+
+int gsr_pose_gradient(int P, int width, int height, const float* means3D, const float* scales, float scale_modifier,
+                      const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                      const float* projmatrix, float tan_fovx, float tan_fovy, const int* radii,
+                      const float* dL_dmean2D, const float* dL_dconic, const float* dL_ddepths,
+                      const float* dL_dmean3D, float* dL_dpose, char* workspace, size_t workspace_bytes,
+                      void* stream_) {
+  g_err[0] = 0;
+  if (P < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P (%d)", P);
+  if (width <= 0 || height <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad width/height (%d x %d)", width, height);
+  if (!(tan_fovx > 0.f) || !(tan_fovy > 0.f) || !std::isfinite(tan_fovx) || !std::isfinite(tan_fovy))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "tan_fovx / tan_fovy must be finite and positive");
+  if (!dL_dpose) return fail(GSR_ERR_INVALID_ARGUMENT, "null dL_dpose");
+  if (!workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null workspace");
+  if (P > 0) {
+    if (!means3D || !viewmatrix || !projmatrix || !radii) return fail(GSR_ERR_INVALID_ARGUMENT, "null required input");
+    if (!dL_dmean2D || !dL_dconic || !dL_dmean3D) return fail(GSR_ERR_INVALID_ARGUMENT, "null gradient input");
+    if (cov3D_precomp ? (scales || rotations) : (!scales || !rotations))
+      return fail(GSR_ERR_INVALID_ARGUMENT, "provide either scales+rotations or a precomputed 3D covariance");
+    if (!cov3D_precomp && misaligned16(rotations)) return fail_rotations(rotations);
+  }
+  if (workspace_bytes < pose_workspace_bytes(P))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes", pose_workspace_bytes(P));
+  const FrameParams fp = make_params(P, 0, 0, width, height, tan_fovx, tan_fovy, scale_modifier);
+  HIP_TRY(launch_pose_gradient(fp, radii, means3D, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, dL_dmean2D,
+                               dL_dconic, dL_ddepths, dL_dmean3D, dL_dpose, workspace, (hipStream_t)stream_));
+  return GSR_OK;
 }
 
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,

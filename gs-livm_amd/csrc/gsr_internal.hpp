@@ -421,6 +421,14 @@ hipError_t launch_gaussian_backward(const FrameParams& fp, GeomState g, BinningS
                                     float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_ddepths,
                                     hipStream_t s);
 hipError_t launch_mark_visible(int P, const float* means3D, const float* view, unsigned char* present, hipStream_t s);
+// the camera pose gradient behind a backward (preprocess.hip: it shares the backward's device functions); two launches,
+// one double[6] per 256 Gaussians in the workspace, which needs no alignment
+size_t pose_workspace_bytes(int P);
+hipError_t launch_pose_gradient(const FrameParams& fp, const int* radii, const float* means3D, const float* scales,
+                                const float* rotations, const float* cov3D_precomp, const float* view,
+                                const float* proj, const float* dL_dmean2D, const float* dL_dconic,
+                                const float* dL_ddepths, const float* dL_dmean3D, float* dL_dpose, char* workspace,
+                                hipStream_t s);
 // optimizer.hip ("next" row: fused activations + Adam)
 hipError_t launch_activate(int P, int M, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
                            const float* f_dc, const float* f_rest, float* scales, float* rotations, float* opacities,
@@ -511,6 +519,7 @@ enum KernelId {
   // (beside the other depth term; ids are looked up by name, and the prune kernels stay the last four)
   K_LIDAR_CLEAR, K_LIDAR_SPLAT, K_LIDAR_CONVERT, K_LIDAR_LOSS_FWD, K_LIDAR_LOSS_FINISH, K_LIDAR_LOSS_GRADS,
   K_DENSITY_ACCUMULATE, K_DENSIFY_MARK, K_DENSIFY_SCAN, K_DENSIFY_RANK, K_DENSIFY_APPLY,
+  K_POSE_PARTIALS, K_POSE_FINISH,
   K_METRICS_FWD, K_METRICS_FINALIZE, K_PACK_IMAGE_U8, K_PACK_DEPTH_U8,
   K_PRUNE_MARK, K_PRUNE_SCAN, K_PRUNE_RANK, K_PRUNE_COMPACT, K_COUNT
 };

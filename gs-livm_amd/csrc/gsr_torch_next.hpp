@@ -227,6 +227,24 @@ std::vector<std::string> ply_attribute_names(int M);  // construct_list_of_attri
 // Off by default.  Returns the previous value.
 bool set_depth_gradient(bool on);
 
+// ---- camera pose gradient (torch_next.cpp; an extension, the reference's poses are constants) ---------------------------
+// gsr_pose_gradient with tensors: dL/dxi [6] f32 of the left perturbation T_cw <- Exp(xi^) T_cw at xi = 0 ([0:3]
+// translation, [3:6] rotation, camera axes; include/gsraster.h has the convention), from what a backward was given and
+// wrote.  scales / rotations or cov3D_precomp: size-0 or undefined = not provided; dL_ddepths undefined = none.  All
+// device tensors, nothing waits.
+torch::Tensor pose_gradient(const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& scales,
+                            const torch::Tensor& rotations, float scale_modifier, const torch::Tensor& cov3D_precomp,
+                            const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, float tan_fovx,
+                            float tan_fovy, int image_height, int image_width, const torch::Tensor& dL_dmeans2D,
+                            const torch::Tensor& dL_dconic, const torch::Tensor& dL_dmeans3D,
+                            const torch::Tensor& dL_ddepths = torch::Tensor());
+// T_cw <- Exp(xi^) T_cw IN PLACE in a camera's device tensors (world_view_transform, full_proj_transform, camera_center;
+// `projection` is read), then xi <- 0: the addresses stay, which keeps the library's per-view history.  Composed in
+// float64 on the device and rounded once; no host wait.
+void retract_camera(torch::Tensor view, torch::Tensor full_proj, torch::Tensor centre, const torch::Tensor& projection,
+                    torch::Tensor xi);
+torch::Tensor se3_exp(const torch::Tensor& xi);  // Exp(xi^) [4,4] in xi's dtype, on its device
+
 }  // namespace gsr_torch
 
 // RasterizeGaussiansBackwardCUDA with the gradient of the depth output (gsr_backward_depth): the same arguments plus
@@ -243,3 +261,19 @@ RasterizeGaussiansBackwardDepthCUDA(const torch::Tensor& background, const torch
                                     const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
                                     const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
                                     const bool debug);
+
+// The backward and the camera pose gradient behind it (gsr_pose_gradient), for a C++ host: the arguments of
+// RasterizeGaussiansBackwardDepthCUDA -- an undefined dL_dout_depth selects the plain backward, dL_ddepths then comes back
+// undefined -- and its nine tensors plus dL_dpose [6].
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor, torch::Tensor, torch::Tensor>
+RasterizeGaussiansBackwardPoseCUDA(const torch::Tensor& background, const torch::Tensor& means3D,
+                                   const torch::Tensor& radii, const torch::Tensor& colors, const torch::Tensor& scales,
+                                   const torch::Tensor& rotations, const float scale_modifier,
+                                   const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
+                                   const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+                                   const torch::Tensor& dL_dout_color, const torch::Tensor& dL_dout_acc,
+                                   const torch::Tensor& dL_dout_depth, const torch::Tensor& sh, const int degree,
+                                   const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
+                                   const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
+                                   const bool debug);

@@ -13,6 +13,7 @@
 //   B2a k_compact_touched / k_gather_records   per-Gaussian sums of the per-instance gradient records (no atomics,
 //                           fixed order)
 //   B2b k_gaussian_backward EWA / projection / SH / covariance chain rule
+//   PP  k_pose_partials / k_pose_finish   camera pose gradient behind a backward: six float64 sums in a fixed order
 //   V1  k_mark_visible;  debug only: k_point_offsets
 //
 // THIS FILE IS COMPILED WITH -ffp-contract=off.  radii, tile rectangles and the depth bits of the
@@ -1566,6 +1567,79 @@ __global__ __launch_bounds__(PRE_BLOCK) __attribute__((amdgpu_num_vgpr(96))) voi
 }
 
 // ------------------------------------------------------------------------------------------------
+// The geometric part of the per-Gaussian backward: from the gradients of the conic (gca, gcb, gcc) and of the NDC
+// position (gmx, gmy) to the gradient of the 3-D covariance 6-vector and the part of dL_dmean3D that comes through the
+// EWA projection (B2, backward.cu:140-275) and the projection Jacobian (B3, backward.cu:389-407) -- everything of the
+// mean's gradient but the SH view direction and the depth term.  ONE definition, inlined into k_gaussian_backward and
+// k_pose_partials: the pose gradient recomputes exactly the bits the backward used.
+// ------------------------------------------------------------------------------------------------
+// dcov[6], dm0..2: the caller's locals, written here (dcov zero where denom2inv is 0).
+__device__ __forceinline__ void geometric_backward(const float mx, const float my, const float mz,
+                                                   const FrameParams& fp, const float* c6,
+                                                   const float* __restrict__ V, const float* __restrict__ Pm,
+                                                   const float gmx, const float gmy, const float gca,
+                                                   const float gcb, const float gcc, float* __restrict__ dL_dcov3D_row,
+                                                   float* dcov, float& dm0, float& dm1, float& dm2) {
+  // ---- B2: conic -> cov2D -> cov3D and mean (backward.cu:140-275) ----
+  const Ewa e = ewa_project(mx, my, mz, fp, c6, V);
+  const float limx = 1.3f * fp.tan_fovx, limy = 1.3f * fp.tan_fovy;
+  const float xmul = (e.txtz < -limx || e.txtz > limx) ? 0.f : 1.f;
+  const float ymul = (e.tytz < -limy || e.tytz > limy) ? 0.f : 1.f;
+  const float a = e.cxx + 0.3f, b = e.cxy, c = e.cyy + 0.3f;
+  const float denom = a * c - b * b;
+  float dL_da = 0, dL_db = 0, dL_dc = 0;
+  const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
+#pragma unroll
+  for (int k = 0; k < 6; k++) dcov[k] = 0.f;
+  if (denom2inv != 0) {
+    dL_da = denom2inv * (-c * c * gca + 2 * b * c * gcb + (denom - a * c) * gcc);
+    dL_dc = denom2inv * (-a * a * gcc + 2 * a * b * gcb + (denom - a * c) * gca);
+    dL_db = denom2inv * 2 * (b * c * gca - (denom + 2 * b * b) * gcb + a * b * gcc);
+    dcov[0] = (e.T00 * e.T00 * dL_da + e.T00 * e.T10 * dL_db + e.T10 * e.T10 * dL_dc);
+    dcov[3] = (e.T01 * e.T01 * dL_da + e.T01 * e.T11 * dL_db + e.T11 * e.T11 * dL_dc);
+    dcov[5] = (e.T02 * e.T02 * dL_da + e.T02 * e.T12 * dL_db + e.T12 * e.T12 * dL_dc);
+    dcov[1] = 2 * e.T00 * e.T01 * dL_da + (e.T00 * e.T11 + e.T01 * e.T10) * dL_db + 2 * e.T10 * e.T11 * dL_dc;
+    dcov[2] = 2 * e.T00 * e.T02 * dL_da + (e.T00 * e.T12 + e.T02 * e.T10) * dL_db + 2 * e.T10 * e.T12 * dL_dc;
+    dcov[4] = 2 * e.T02 * e.T01 * dL_da + (e.T01 * e.T12 + e.T02 * e.T11) * dL_db + 2 * e.T11 * e.T12 * dL_dc;
+  }
+  if (dL_dcov3D_row) {  // (the backward's output row, written here as it always was; null: not wanted)
+#pragma unroll
+    for (int k = 0; k < 6; k++) dL_dcov3D_row[k] = dcov[k];
+  }
+  // Vrk[c][r] symmetric: S(c,r)
+  const float S00 = c6[0], S01 = c6[1], S02 = c6[2], S11 = c6[3], S12 = c6[4], S22 = c6[5];
+  const float u0 = e.T00 * S00 + e.T01 * S01 + e.T02 * S02, u1 = e.T00 * S01 + e.T01 * S11 + e.T02 * S12,
+              u2 = e.T00 * S02 + e.T01 * S12 + e.T02 * S22;
+  const float v0 = e.T10 * S00 + e.T11 * S01 + e.T12 * S02, v1 = e.T10 * S01 + e.T11 * S11 + e.T12 * S12,
+              v2 = e.T10 * S02 + e.T11 * S12 + e.T12 * S22;
+  const float dT00 = 2 * u0 * dL_da + v0 * dL_db, dT01 = 2 * u1 * dL_da + v1 * dL_db, dT02 = 2 * u2 * dL_da + v2 * dL_db;
+  const float dT10 = 2 * v0 * dL_dc + u0 * dL_db, dT11 = 2 * v1 * dL_dc + u1 * dL_db, dT12 = 2 * v2 * dL_dc + u2 * dL_db;
+  // W[k][r] = V[k + 4r]
+  const float dJ00 = V[0] * dT00 + V[4] * dT01 + V[8] * dT02;
+  const float dJ02 = V[2] * dT00 + V[6] * dT01 + V[10] * dT02;
+  const float dJ11 = V[1] * dT10 + V[5] * dT11 + V[9] * dT12;
+  const float dJ12 = V[2] * dT10 + V[6] * dT11 + V[10] * dT12;
+  const float tz = 1.f / e.tz, tz2 = tz * tz, tz3 = tz2 * tz;
+  const float hx = fp.focal_x, hy = fp.focal_y;
+  const float dtx = xmul * -hx * tz2 * dJ02;
+  const float dty = ymul * -hy * tz2 * dJ12;
+  const float dtz = -hx * tz2 * dJ00 - hy * tz2 * dJ11 + (2 * hx * e.tx) * tz3 * dJ02 + (2 * hy * e.ty) * tz3 * dJ12;
+  dm0 = V[0] * dtx + V[1] * dty + V[2] * dtz;
+  dm1 = V[4] * dtx + V[5] * dty + V[6] * dtz;
+  dm2 = V[8] * dtx + V[9] * dty + V[10] * dtz;
+  // ---- B3: projection Jacobian (backward.cu:389-407) ----
+  {
+    const float mh3 = Pm[3] * mx + Pm[7] * my + Pm[11] * mz + Pm[15];
+    const float m_w = 1.0f / (mh3 + 0.0000001f);
+    const float mul1 = (Pm[0] * mx + Pm[4] * my + Pm[8] * mz + Pm[12]) * m_w * m_w;
+    const float mul2 = (Pm[1] * mx + Pm[5] * my + Pm[9] * mz + Pm[13]) * m_w * m_w;
+    dm0 += (Pm[0] * m_w - Pm[3] * mul1) * gmx + (Pm[1] * m_w - Pm[3] * mul2) * gmy;
+    dm1 += (Pm[4] * m_w - Pm[7] * mul1) * gmx + (Pm[5] * m_w - Pm[7] * mul2) * gmy;
+    dm2 += (Pm[8] * m_w - Pm[11] * mul1) * gmx + (Pm[9] * m_w - Pm[11] * mul2) * gmy;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // B2 + B3, fused with the gradient gather.  One thread per Gaussian.  Replaces computeCov2DCUDA
 // (reference backward.cu:140-275), preprocessCUDA backward (:371-435), computeColorFromSH backward
 // (:20-135) and computeCov3D backward (:279-366), and the 9 atomicAdds per (pixel, Gaussian) of the
@@ -1657,62 +1731,11 @@ __device__ __forceinline__ void gaussian_backward_one(
   // dL_dcolor outputs as well; the unused third / fourth components are zeroed)
   dL_dmean2D[3 * idx + 2] = 0.f;
   dL_dconic[4 * idx + 2] = 0.f;
-  // ---- B2: conic -> cov2D -> cov3D and mean (backward.cu:140-275) ----
-  const Ewa e = ewa_project(mx, my, mz, fp, c6, V);
-  const float limx = 1.3f * fp.tan_fovx, limy = 1.3f * fp.tan_fovy;
-  const float xmul = (e.txtz < -limx || e.txtz > limx) ? 0.f : 1.f;
-  const float ymul = (e.tytz < -limy || e.tytz > limy) ? 0.f : 1.f;
-  const float a = e.cxx + 0.3f, b = e.cxy, c = e.cyy + 0.3f;
-  const float denom = a * c - b * b;
-  float dL_da = 0, dL_db = 0, dL_dc = 0;
-  const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
-  float dcov[6] = {0, 0, 0, 0, 0, 0};
-  if (denom2inv != 0) {
-    dL_da = denom2inv * (-c * c * gca + 2 * b * c * gcb + (denom - a * c) * gcc);
-    dL_dc = denom2inv * (-a * a * gcc + 2 * a * b * gcb + (denom - a * c) * gca);
-    dL_db = denom2inv * 2 * (b * c * gca - (denom + 2 * b * b) * gcb + a * b * gcc);
-    dcov[0] = (e.T00 * e.T00 * dL_da + e.T00 * e.T10 * dL_db + e.T10 * e.T10 * dL_dc);
-    dcov[3] = (e.T01 * e.T01 * dL_da + e.T01 * e.T11 * dL_db + e.T11 * e.T11 * dL_dc);
-    dcov[5] = (e.T02 * e.T02 * dL_da + e.T02 * e.T12 * dL_db + e.T12 * e.T12 * dL_dc);
-    dcov[1] = 2 * e.T00 * e.T01 * dL_da + (e.T00 * e.T11 + e.T01 * e.T10) * dL_db + 2 * e.T10 * e.T11 * dL_dc;
-    dcov[2] = 2 * e.T00 * e.T02 * dL_da + (e.T00 * e.T12 + e.T02 * e.T10) * dL_db + 2 * e.T10 * e.T12 * dL_dc;
-    dcov[4] = 2 * e.T02 * e.T01 * dL_da + (e.T01 * e.T12 + e.T02 * e.T11) * dL_db + 2 * e.T11 * e.T12 * dL_dc;
-  }
-  if (dL_dcov3D) {
-#pragma unroll
-    for (int k = 0; k < 6; k++) dL_dcov3D[6 * (size_t)idx + k] = dcov[k];
-  }
-  // Vrk[c][r] symmetric: S(c,r)
-  const float S00 = c6[0], S01 = c6[1], S02 = c6[2], S11 = c6[3], S12 = c6[4], S22 = c6[5];
-  const float u0 = e.T00 * S00 + e.T01 * S01 + e.T02 * S02, u1 = e.T00 * S01 + e.T01 * S11 + e.T02 * S12,
-              u2 = e.T00 * S02 + e.T01 * S12 + e.T02 * S22;
-  const float v0 = e.T10 * S00 + e.T11 * S01 + e.T12 * S02, v1 = e.T10 * S01 + e.T11 * S11 + e.T12 * S12,
-              v2 = e.T10 * S02 + e.T11 * S12 + e.T12 * S22;
-  const float dT00 = 2 * u0 * dL_da + v0 * dL_db, dT01 = 2 * u1 * dL_da + v1 * dL_db, dT02 = 2 * u2 * dL_da + v2 * dL_db;
-  const float dT10 = 2 * v0 * dL_dc + u0 * dL_db, dT11 = 2 * v1 * dL_dc + u1 * dL_db, dT12 = 2 * v2 * dL_dc + u2 * dL_db;
-  // W[k][r] = V[k + 4r]
-  const float dJ00 = V[0] * dT00 + V[4] * dT01 + V[8] * dT02;
-  const float dJ02 = V[2] * dT00 + V[6] * dT01 + V[10] * dT02;
-  const float dJ11 = V[1] * dT10 + V[5] * dT11 + V[9] * dT12;
-  const float dJ12 = V[2] * dT10 + V[6] * dT11 + V[10] * dT12;
-  const float tz = 1.f / e.tz, tz2 = tz * tz, tz3 = tz2 * tz;
-  const float hx = fp.focal_x, hy = fp.focal_y;
-  const float dtx = xmul * -hx * tz2 * dJ02;
-  const float dty = ymul * -hy * tz2 * dJ12;
-  const float dtz = -hx * tz2 * dJ00 - hy * tz2 * dJ11 + (2 * hx * e.tx) * tz3 * dJ02 + (2 * hy * e.ty) * tz3 * dJ12;
-  float dm0 = V[0] * dtx + V[1] * dty + V[2] * dtz;
-  float dm1 = V[4] * dtx + V[5] * dty + V[6] * dtz;
-  float dm2 = V[8] * dtx + V[9] * dty + V[10] * dtz;
-  // ---- B3: projection Jacobian (backward.cu:389-407) ----
-  {
-    const float mh3 = Pm[3] * mx + Pm[7] * my + Pm[11] * mz + Pm[15];
-    const float m_w = 1.0f / (mh3 + 0.0000001f);
-    const float mul1 = (Pm[0] * mx + Pm[4] * my + Pm[8] * mz + Pm[12]) * m_w * m_w;
-    const float mul2 = (Pm[1] * mx + Pm[5] * my + Pm[9] * mz + Pm[13]) * m_w * m_w;
-    dm0 += (Pm[0] * m_w - Pm[3] * mul1) * gmx + (Pm[1] * m_w - Pm[3] * mul2) * gmy;
-    dm1 += (Pm[4] * m_w - Pm[7] * mul1) * gmx + (Pm[5] * m_w - Pm[7] * mul2) * gmy;
-    dm2 += (Pm[8] * m_w - Pm[11] * mul1) * gmx + (Pm[9] * m_w - Pm[11] * mul2) * gmy;
-  }
+  // ---- B2 + B3 (geometric_backward, shared with k_pose_partials) ----
+  float dcov[6];
+  float dm0, dm1, dm2;
+  geometric_backward(mx, my, mz, fp, c6, V, Pm, gmx, gmy, gca, gcb, gcc,
+                     dL_dcov3D ? dL_dcov3D + 6 * (size_t)idx : nullptr, dcov, dm0, dm1, dm2);
   // ---- SH backward (backward.cu:20-135) ----
   if (shs && !colors_are_precomp) {
     const uint8_t cb = clamped_in;
@@ -1881,6 +1904,132 @@ __global__ __launch_bounds__(PRE_BLOCK) void k_mark_visible(int P, const float* 
   if (idx >= P) return;
   const float z = V[2] * means3D[3 * idx] + V[6] * means3D[3 * idx + 1] + V[10] * means3D[3 * idx + 2] + V[14];
   present[idx] = !(z <= 0.2f);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Camera pose gradient (gsr_pose_gradient): dL/dxi of the left perturbation T_cw <- Exp(xi^) T_cw at xi = 0, from what a
+// backward was given and wrote.  With t = R p + T (R[r][k] = V[r + 4k]) a Gaussian depends on the pose through t and
+// through Sigma_cam = R Sigma R^T only (the SH view direction R^T t does not turn with the camera), so
+//   dL/drho = R sum_i dL_dmean3D_i
+//   dL/dphi = sum_i t_i x (R dm_geo,i) + 2 sum_i axial(G_cam,i Sigma_cam,i - Sigma_cam,i G_cam,i)
+// dm_geo = geometric_backward's mean gradient + the depth term; G the symmetric form of that function's dcov.
+// PP1 k_pose_partials: one thread per Gaussian; the row's six f32 terms are widened to f64 and summed in a fixed order:
+//     butterfly over the wave's 64 lanes, the block's four waves through LDS in wave order, one double[6] per block.
+// PP2 k_pose_finish: one workgroup; thread j sums partials j, j + 256, ... serially, then a tree over the 256 threads.
+// No atomics, and the number of partials depends on P alone: the result is the same bits on every run and machine.
+// ------------------------------------------------------------------------------------------------
+constexpr int POSE_ROWS = PRE_BLOCK;  // rows per workgroup of k_pose_partials = partials per POSE_ROWS Gaussians
+constexpr int POSE_FINISH = 256;      // threads of k_pose_finish's one workgroup
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(POSE_ROWS) void k_pose_partials(
+    const FrameParams fp, const int* __restrict__ radii, const float* __restrict__ means3D,
+    const float* __restrict__ scales, const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp,
+    const float* __restrict__ V, const float* __restrict__ Pm, const float* __restrict__ dL_dmean2D,
+    const float* __restrict__ dL_dconic, const float* __restrict__ dL_ddepths, const float* __restrict__ dL_dmean3D,
+    double* __restrict__ partials) {
+  __shared__ double s_wave[POSE_ROWS / 64][6];
+  const size_t idx = (size_t)blockIdx.x * POSE_ROWS + threadIdx.x;
+  float term[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  // a row that is not visible reads nothing else: its gradient rows may hold anything
+  if (idx < (size_t)fp.P && radii[idx] > 0) {
+    const float mx = means3D[3 * idx], my = means3D[3 * idx + 1], mz = means3D[3 * idx + 2];
+    const float gmx = dL_dmean2D[3 * idx], gmy = dL_dmean2D[3 * idx + 1];
+    const float gca = dL_dconic[4 * idx], gcb = dL_dconic[4 * idx + 1], gcc = dL_dconic[4 * idx + 3];
+    const float gz = dL_ddepths ? dL_ddepths[idx] : 0.f;
+    const float g0 = dL_dmean3D[3 * idx], g1 = dL_dmean3D[3 * idx + 1], g2 = dL_dmean3D[3 * idx + 2];
+    float c6[6];
+    if (cov3D_precomp) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) c6[k] = cov3D_precomp[6 * idx + k];
+    } else {
+      const float4 q = reinterpret_cast<const float4*>(rotations)[idx];
+      cov3d_from_scale_rot(fp.scale_modifier * scales[3 * idx], fp.scale_modifier * scales[3 * idx + 1],
+                           fp.scale_modifier * scales[3 * idx + 2], q, c6);
+    }
+    float dcov[6];
+    float gm0, gm1, gm2;
+    geometric_backward(mx, my, mz, fp, c6, V, Pm, gmx, gmy, gca, gcb, gcc, nullptr, dcov, gm0, gm1, gm2);
+    // dm_geo: the depth term dL/dz (third row of R) on top
+    const float d0 = gm0 + V[2] * gz, d1 = gm1 + V[6] * gz, d2 = gm2 + V[10] * gz;
+    // rho: R g
+    term[0] = V[0] * g0 + V[4] * g1 + V[8] * g2;
+    term[1] = V[1] * g0 + V[5] * g1 + V[9] * g2;
+    term[2] = V[2] * g0 + V[6] * g1 + V[10] * g2;
+    // phi, first part: t x (R dm_geo)
+    const float t0 = V[0] * mx + V[4] * my + V[8] * mz + V[12];
+    const float t1 = V[1] * mx + V[5] * my + V[9] * mz + V[13];
+    const float t2 = V[2] * mx + V[6] * my + V[10] * mz + V[14];
+    const float r0 = V[0] * d0 + V[4] * d1 + V[8] * d2;
+    const float r1 = V[1] * d0 + V[5] * d1 + V[9] * d2;
+    const float r2 = V[2] * d0 + V[6] * d1 + V[10] * d2;
+    // phi, second part: A = G_cam Sigma_cam - Sigma_cam G_cam with X_cam = R X R^T
+    const float Rm[3][3] = {{V[0], V[4], V[8]}, {V[1], V[5], V[9]}, {V[2], V[6], V[10]}};  // Rm[r][k]
+    const float Sw[3][3] = {{c6[0], c6[1], c6[2]}, {c6[1], c6[3], c6[4]}, {c6[2], c6[4], c6[5]}};
+    const float Gw[3][3] = {{dcov[0], 0.5f * dcov[1], 0.5f * dcov[2]},
+                            {0.5f * dcov[1], dcov[3], 0.5f * dcov[4]},
+                            {0.5f * dcov[2], 0.5f * dcov[4], dcov[5]}};
+    float Sc[3][3], Gc[3][3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+      float rs[3], rg[3];  // rows of R S and R G
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        rs[k] = Rm[i][0] * Sw[0][k] + Rm[i][1] * Sw[1][k] + Rm[i][2] * Sw[2][k];
+        rg[k] = Rm[i][0] * Gw[0][k] + Rm[i][1] * Gw[1][k] + Rm[i][2] * Gw[2][k];
+      }
+#pragma unroll
+      for (int j = 0; j < 3; j++) {
+        Sc[i][j] = rs[0] * Rm[j][0] + rs[1] * Rm[j][1] + rs[2] * Rm[j][2];
+        Gc[i][j] = rg[0] * Rm[j][0] + rg[1] * Rm[j][1] + rg[2] * Rm[j][2];
+      }
+    }
+#define POSE_COMM(i, j) ((Gc[i][0] * Sc[0][j] + Gc[i][1] * Sc[1][j] + Gc[i][2] * Sc[2][j]) - \
+                         (Sc[i][0] * Gc[0][j] + Sc[i][1] * Gc[1][j] + Sc[i][2] * Gc[2][j]))
+    term[3] = (t1 * r2 - t2 * r1) + 2.f * POSE_COMM(2, 1);
+    term[4] = (t2 * r0 - t0 * r2) + 2.f * POSE_COMM(0, 2);
+    term[5] = (t0 * r1 - t1 * r0) + 2.f * POSE_COMM(1, 0);
+#undef POSE_COMM
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    const double w = wave_sum_f64((double)term[k]);
+    if (lane == 0) s_wave[wave][k] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < 6) {
+    double acc = s_wave[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < POSE_ROWS / 64; w++) acc += s_wave[w][threadIdx.x];
+    partials[(size_t)blockIdx.x * 6 + threadIdx.x] = acc;
+  }
+}
+
+__global__ __launch_bounds__(POSE_FINISH) void k_pose_finish(const int npart, const double* __restrict__ partials,
+                                                             float* __restrict__ dL_dpose) {
+  __shared__ double s_sum[POSE_FINISH][6];
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int b = threadIdx.x; b < npart; b += POSE_FINISH) {
+#pragma unroll
+    for (int k = 0; k < 6; k++) acc[k] += partials[(size_t)b * 6 + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 6; k++) s_sum[threadIdx.x][k] = acc[k];
+  __syncthreads();
+  for (int o = POSE_FINISH / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) s_sum[threadIdx.x][k] += s_sum[threadIdx.x + o][k];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 6) dL_dpose[threadIdx.x] = (float)s_sum[0][threadIdx.x];
 }
 
 // ---------------------------------- launchers ----------------------------------------------------
@@ -2084,6 +2233,29 @@ hipError_t launch_mark_visible(int P, const float* means3D, const float* view, u
   const int nb = (P + PRE_BLOCK - 1) / PRE_BLOCK;
   ProfScope ps_k_mark_visible(K_MARK_VISIBLE, s);
   hipLaunchKernelGGL(k_mark_visible, dim3(nb), dim3(PRE_BLOCK), 0, s, P, means3D, view, present);
+  return hipGetLastError();
+}
+
+// one double[6] per POSE_ROWS Gaussians + the slack to align the doubles inside a workspace of any address
+static inline size_t pose_partials(int P) { return ((size_t)P + POSE_ROWS - 1) / POSE_ROWS; }
+size_t pose_workspace_bytes(int P) { return pose_partials(P) * 6 * sizeof(double) + 16; }
+
+hipError_t launch_pose_gradient(const FrameParams& fp, const int* radii, const float* means3D, const float* scales,
+                                const float* rotations, const float* cov3D_precomp, const float* view,
+                                const float* proj, const float* dL_dmean2D, const float* dL_dconic,
+                                const float* dL_ddepths, const float* dL_dmean3D, float* dL_dpose, char* workspace,
+                                hipStream_t s) {
+  double* partials = reinterpret_cast<double*>((reinterpret_cast<uintptr_t>(workspace) + 15u) & ~(uintptr_t)15u);
+  const int nb = (int)pose_partials(fp.P);
+  if (nb > 0) {
+    ProfScope ps(K_POSE_PARTIALS, s);
+    hipLaunchKernelGGL(k_pose_partials, dim3(nb), dim3(POSE_ROWS), 0, s, fp, radii, means3D, scales, rotations,
+                       cov3D_precomp, view, proj, dL_dmean2D, dL_dconic, dL_ddepths, dL_dmean3D, partials);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  ProfScope ps(K_POSE_FINISH, s);
+  hipLaunchKernelGGL(k_pose_finish, dim3(1), dim3(POSE_FINISH), 0, s, nb, partials, dL_dpose);
   return hipGetLastError();
 }
 

@@ -135,7 +135,8 @@ rasterize_backward_impl(const torch::Tensor& background, const torch::Tensor& me
                         const torch::Tensor& dL_dout_color, const torch::Tensor& dL_dout_acc, const torch::Tensor& sh,
                         const int degree, const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
                         const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer, const bool debug,
-                        const bool want_cov3D, const torch::Tensor& dL_dout_depth = torch::Tensor()) {
+                        const bool want_cov3D, const torch::Tensor& dL_dout_depth = torch::Tensor(),
+                        torch::Tensor* dL_dconic_out = nullptr) {
   const int P = means3D.size(0);
   const int H = dL_dout_color.size(1);
   const int W = dL_dout_color.size(2);
@@ -190,6 +191,7 @@ rasterize_backward_impl(const torch::Tensor& background, const torch::Tensor& me
                        dL_drotations.data_ptr<float>(), debug ? 1 : 0, current_stream()),
           "gsr_backward");
   }
+  if (dL_dconic_out) *dL_dconic_out = dL_dconic;  // (an intermediate of the reference's surface: the pose gradient reads it)
   return std::make_tuple(dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
                          dL_drotations, dL_ddepths);
 }
@@ -228,6 +230,30 @@ RasterizeGaussiansBackwardDepthCUDA(const torch::Tensor& background, const torch
   return rasterize_backward_impl(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
                                  viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_acc, sh, degree, campos,
                                  geomBuffer, R, binningBuffer, imageBuffer, debug, /*want_cov3D=*/true, dL_dout_depth);
+}
+
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
+           torch::Tensor, torch::Tensor, torch::Tensor>
+RasterizeGaussiansBackwardPoseCUDA(const torch::Tensor& background, const torch::Tensor& means3D,
+                                   const torch::Tensor& radii, const torch::Tensor& colors, const torch::Tensor& scales,
+                                   const torch::Tensor& rotations, const float scale_modifier,
+                                   const torch::Tensor& cov3D_precomp, const torch::Tensor& viewmatrix,
+                                   const torch::Tensor& projmatrix, const float tan_fovx, const float tan_fovy,
+                                   const torch::Tensor& dL_dout_color, const torch::Tensor& dL_dout_acc,
+                                   const torch::Tensor& dL_dout_depth, const torch::Tensor& sh, const int degree,
+                                   const torch::Tensor& campos, const torch::Tensor& geomBuffer, const int R,
+                                   const torch::Tensor& binningBuffer, const torch::Tensor& imageBuffer,
+                                   const bool debug) {
+  torch::Tensor conic;
+  auto [g0, g1, g2, g3, g4, g5, g6, g7, g8] =
+      rasterize_backward_impl(background, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp,
+                              viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_acc, sh, degree, campos,
+                              geomBuffer, R, binningBuffer, imageBuffer, debug, /*want_cov3D=*/true, dL_dout_depth, &conic);
+  const torch::Tensor pose =
+      gsr_torch::pose_gradient(means3D, radii, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+                               tan_fovx, tan_fovy, static_cast<int>(dL_dout_color.size(1)),
+                               static_cast<int>(dL_dout_color.size(2)), g0, conic, g3, g8);
+  return std::make_tuple(g0, g1, g2, g3, g4, g5, g6, g7, g8, pose);
 }
 
 torch::Tensor markVisible(torch::Tensor& means3D, torch::Tensor& viewmatrix, torch::Tensor& projmatrix) {
@@ -384,6 +410,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("RasterizeGaussiansCUDA", &RasterizeGaussiansCUDA);
   m.def("RasterizeGaussiansBackwardCUDA", &RasterizeGaussiansBackwardCUDA);
   m.def("RasterizeGaussiansBackwardDepthCUDA", &RasterizeGaussiansBackwardDepthCUDA);
+  m.def("RasterizeGaussiansBackwardPoseCUDA",
+        [](torch::Tensor bg, torch::Tensor means3D, torch::Tensor radii, torch::Tensor colors, torch::Tensor scales,
+           torch::Tensor rotations, float scale_modifier, torch::Tensor cov3D_precomp, torch::Tensor viewmatrix,
+           torch::Tensor projmatrix, float tan_fovx, float tan_fovy, torch::Tensor dL_dout_color,
+           torch::Tensor dL_dout_acc, const py::object& dL_dout_depth, torch::Tensor sh, int degree, torch::Tensor campos,
+           torch::Tensor geomBuffer, int R, torch::Tensor binningBuffer, torch::Tensor imageBuffer, bool debug) {
+          return RasterizeGaussiansBackwardPoseCUDA(
+              bg, means3D, radii, colors, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix,
+              tan_fovx, tan_fovy, dL_dout_color, dL_dout_acc,
+              dL_dout_depth.is_none() ? torch::Tensor() : dL_dout_depth.cast<torch::Tensor>(), sh, degree, campos,
+              geomBuffer, R, binningBuffer, imageBuffer, debug);
+        });
   m.def("set_depth_gradient", &gsr_torch::set_depth_gradient, py::arg("on"));
   m.def("markVisible", [](torch::Tensor a, torch::Tensor b, torch::Tensor c) { return markVisible(a, b, c); });
   // exact instance count of this thread's last forward (RasterizeGaussiansCUDA's first element is the binning key:
@@ -515,6 +553,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("min_opacity") = 1.0f / 255.0f, py::arg("max_scale") = 0.3f, py::arg("drop_nonfinite") = true,
         py::arg("drop") = py::none());
   n.def("prune_rows", &nx::prune_rows, py::arg("tensors"), py::arg("reasons"), py::arg("row_map"), py::arg("P_new"));
+  n.def("pose_gradient",
+        [opt](torch::Tensor means3D, torch::Tensor radii, py::object scales, py::object rotations, float scale_modifier,
+              py::object cov3D_precomp, torch::Tensor viewmatrix, torch::Tensor projmatrix, float tan_fovx, float tan_fovy,
+              int image_height, int image_width, torch::Tensor dL_dmeans2D, torch::Tensor dL_dconic,
+              torch::Tensor dL_dmeans3D, py::object dL_ddepths) {
+          return nx::pose_gradient(means3D, radii, opt(scales), opt(rotations), scale_modifier, opt(cov3D_precomp),
+                                   viewmatrix, projmatrix, tan_fovx, tan_fovy, image_height, image_width, dL_dmeans2D,
+                                   dL_dconic, dL_dmeans3D, opt(dL_ddepths));
+        },
+        py::arg("means3D"), py::arg("radii"), py::arg("scales"), py::arg("rotations"), py::arg("scale_modifier"),
+        py::arg("cov3D_precomp"), py::arg("viewmatrix"), py::arg("projmatrix"), py::arg("tan_fovx"), py::arg("tan_fovy"),
+        py::arg("image_height"), py::arg("image_width"), py::arg("dL_dmeans2D"), py::arg("dL_dconic"),
+        py::arg("dL_dmeans3D"), py::arg("dL_ddepths") = py::none());
+  n.def("retract_camera", &nx::retract_camera, py::arg("view"), py::arg("full_proj"), py::arg("centre"),
+        py::arg("projection"), py::arg("xi"));
+  n.def("se3_exp", &nx::se3_exp, py::arg("xi"));
   n.def("density_accumulate", &nx::density_accumulate, py::arg("radii"), py::arg("dL_dmean2D"), py::arg("stats"));
   n.def("densify_mark",
         [](torch::Tensor stats, torch::Tensor s, float grad_threshold, float size_threshold, int64_t max_new) {

@@ -721,4 +721,69 @@ size_t write_ply(const std::string& file_path, const torch::Tensor& xyz, const t
   return header.size() + nbytes;
 }
 
+// ---- camera pose gradient ------------------------------------------------------------------------------------------
+torch::Tensor pose_gradient(const torch::Tensor& means3D, const torch::Tensor& radii, const torch::Tensor& scales,
+                            const torch::Tensor& rotations, float scale_modifier, const torch::Tensor& cov3D_precomp,
+                            const torch::Tensor& viewmatrix, const torch::Tensor& projmatrix, float tan_fovx,
+                            float tan_fovy, int image_height, int image_width, const torch::Tensor& dL_dmeans2D,
+                            const torch::Tensor& dL_dconic, const torch::Tensor& dL_dmeans3D,
+                            const torch::Tensor& dL_ddepths) {
+  const torch::Tensor m3 = dev_f32(means3D, "means3D");
+  const int64_t P = m3.size(0);
+  auto given = [](const torch::Tensor& t) { return t.defined() && t.numel() != 0; };
+  auto c = [&](const torch::Tensor& t) { return given(t) ? t.contiguous() : torch::Tensor(); };
+  const torch::Tensor sc = c(scales), cov = c(cov3D_precomp), view = c(viewmatrix), proj = c(projmatrix), rad = c(radii),
+                      g2 = c(dL_dmeans2D), gc = c(dL_dconic), g3 = c(dL_dmeans3D), gz = c(dL_ddepths);
+  torch::Tensor rot = c(rotations);
+  if (given(rot) && (reinterpret_cast<uintptr_t>(rot.data_ptr()) & 15u) != 0) rot = rot.clone();  // read as float4
+  if (given(rad) && rad.scalar_type() != torch::kInt32) throw std::invalid_argument("pose_gradient: radii is int32");
+  const size_t nbytes = gsr_pose_gradient_workspace(static_cast<int>(P));
+  torch::Tensor ws = torch::empty({static_cast<long long>(nbytes)}, m3.options().dtype(torch::kByte));
+  torch::Tensor out = torch::empty({6}, m3.options());
+  check(gsr_pose_gradient(static_cast<int>(P), image_width, image_height, fp(m3), fp(sc), scale_modifier, fp(rot), fp(cov),
+                          fp(view), fp(proj), tan_fovx, tan_fovy, given(rad) ? rad.data_ptr<int>() : nullptr, fp(g2),
+                          fp(gc), fp(gz), fp(g3), out.data_ptr<float>(), reinterpret_cast<char*>(ws.data_ptr()), nbytes,
+                          current_stream()),
+        "gsr_pose_gradient");
+  return out;
+}
+
+// Exp(xi^) = [[R, V rho], [0, 1]]: below |phi| = 0.5 the three coefficients by their series in |phi|^2 (no cancellation,
+// analytic at 0), above it in closed form; tensor ops only, so nothing waits (render_utils.py: se3_exp, the same terms).
+torch::Tensor se3_exp(const torch::Tensor& xi) {
+  if (xi.dim() != 1 || xi.size(0) != 6) throw std::invalid_argument("se3_exp: xi is a tensor of shape (6,)");
+  const torch::Tensor rho = xi.slice(0, 0, 3), phi = xi.slice(0, 3, 6);
+  const torch::Tensor t2 = (phi * phi).sum();
+  const torch::Tensor one = torch::ones_like(t2);
+  const torch::Tensor big = t2 > 0.25;
+  const torch::Tensor t = torch::sqrt(torch::where(big, t2, one));
+  const torch::Tensor h = torch::sin(0.5 * t) / (0.5 * t);
+  const torch::Tensor sA = 1.0 + t2 * (-1.0 / 6.0 + t2 * (1.0 / 120.0 + t2 * (-1.0 / 5040.0 + t2 * (1.0 / 362880.0 + t2 * (-1.0 / 39916800.0 + t2 * (1.0 / 6227020800.0))))));
+  const torch::Tensor sB = 0.5 + t2 * (-1.0 / 24.0 + t2 * (1.0 / 720.0 + t2 * (-1.0 / 40320.0 + t2 * (1.0 / 3628800.0 + t2 * (-1.0 / 479001600.0 + t2 * (1.0 / 87178291200.0))))));
+  const torch::Tensor sC = 1.0 / 6.0 + t2 * (-1.0 / 120.0 + t2 * (1.0 / 5040.0 + t2 * (-1.0 / 362880.0 + t2 * (1.0 / 39916800.0 + t2 * (-1.0 / 6227020800.0)))));
+  const torch::Tensor A = torch::where(big, torch::sin(t) / t, sA);
+  const torch::Tensor B = torch::where(big, 0.5 * h * h, sB);
+  const torch::Tensor C = torch::where(big, (t - torch::sin(t)) / (t * t * t), sC);
+  const torch::Tensor z = torch::zeros_like(t2);
+  const torch::Tensor K = torch::stack({torch::stack({z, -phi[2], phi[1]}), torch::stack({phi[2], z, -phi[0]}),
+                                        torch::stack({-phi[1], phi[0], z})});
+  const torch::Tensor K2 = torch::matmul(K, K);
+  const torch::Tensor eye = torch::eye(3, xi.options());
+  const torch::Tensor Rm = eye + A * K + B * K2, V = eye + B * K + C * K2;
+  const torch::Tensor top = torch::cat({Rm, torch::matmul(V, rho).unsqueeze(1)}, 1);
+  const torch::Tensor bottom = torch::cat({z.expand({3}), one.unsqueeze(0)}).unsqueeze(0);
+  return torch::cat({top, bottom}, 0);
+}
+
+void retract_camera(torch::Tensor view, torch::Tensor full_proj, torch::Tensor centre, const torch::Tensor& projection,
+                    torch::Tensor xi) {
+  torch::NoGradGuard no_grad;
+  const torch::Tensor E = se3_exp(xi.detach().to(view.device(), torch::kFloat64));
+  const torch::Tensor v64 = torch::matmul(view.to(torch::kFloat64), E.t());   // view = T_cw^T: (E T_cw)^T = view E^T
+  view.copy_(v64);
+  full_proj.copy_(torch::matmul(v64, projection.to(torch::kFloat64)));
+  centre.copy_(-torch::matmul(v64.slice(0, 0, 3).slice(1, 0, 3), v64[3].slice(0, 0, 3)));
+  xi.zero_();
+}
+
 }  // namespace gsr_torch

@@ -249,6 +249,43 @@ int gsr_backward_depth(int P, int D, int M, int R, const float* background, int 
                        float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D,
                        float* dL_dsh, float* dL_dscale, float* dL_drot, float* dL_ddepths, int debug, void* stream);
 
+/* The camera pose gradient (an extension, the reference's poses are constants): six numbers from what gsr_backward or
+ * gsr_backward_depth was given and wrote.  Call it after either, on the same stream, with the same inputs and that
+ * call's dL_dmean2D, dL_dconic, dL_dmean3D and (after gsr_backward_depth; else NULL) dL_ddepths.
+ *
+ * Convention.  The pose is the world-to-camera transform T_cw = [R | T]; the view matrix is its transpose in memory
+ * (column-major: R[r][k] = viewmatrix[r + 4k], t = R p + (viewmatrix[12], [13], [14])).  The tangent is a LEFT
+ * perturbation in the camera frame, T_cw(xi) = Exp(xi^) T_cw with xi = (rho, phi): rho the translation part, phi the
+ * rotation part, both in camera axes.  dL_dpose[6] = dL/dxi at xi = 0, [0:3] = rho, [3:6] = phi, where viewmatrix(xi)
+ * is the transpose of T_cw(xi), projmatrix(xi) = viewmatrix(xi) . P with the caller's pose-independent projection P,
+ * and campos(xi) = -R(xi)^T T(xi).  The visible set, the tile lists, the SH clamp flags and the per-pixel cuts are held
+ * fixed and the backward's departures from the exact derivative apply unchanged: it is the gradient gsr_backward would
+ * hand out were the camera one of its leaves:
+ *   dL/drho = R sum_i dL_dmean3D_i
+ *   dL/dphi = sum_i t_i x (R dm_geo,i) + 2 sum_i axial(G_cam,i Sigma_cam,i - Sigma_cam,i G_cam,i)
+ * (dm_geo: dL_dmean3D without its SH view-direction part, which a rotation about the camera centre leaves alone; G the
+ * symmetric form of dL_dcov3D; X_cam = R X R^T; axial(A) = (A[2][1], A[0][2], A[1][0])).  dm_geo and G are recomputed
+ * with the backward's own arithmetic, the same bits; no SH coefficient is read and dL_dcov3D is not needed.
+ *
+ * Rows with radii <= 0 contribute nothing and nothing but their radius is read: their gradient rows may hold anything.
+ * The per-row terms are float32, widened to float64 and summed in a fixed order that depends on P alone (no atomics):
+ * the result is bitwise reproducible from run to run and from machine to machine.  A non-finite value in a visible
+ * row makes the affected components non-finite.  P == 0 writes six zeros.
+ *
+ * No host wait, no allocation: two launches on `stream`.  `workspace` holds gsr_pose_gradient_workspace(P) bytes
+ * (0 only for P < 0) and needs no alignment (the size includes the slack).  GSR_ERR_INVALID_ARGUMENT, before anything
+ * is enqueued or written, for: P < 0, a non-positive width / height, a non-finite or non-positive tan_fov, a null
+ * dL_dpose / workspace / required input, scales without rotations (or the reverse), either of them together with
+ * cov3D_precomp or none of the three, rotations not 16-byte aligned, workspace_bytes below the query (the message
+ * names the bytes needed). */
+size_t gsr_pose_gradient_workspace(int P);
+int gsr_pose_gradient(int P, int width, int height, const float* means3D, const float* scales, float scale_modifier,
+                      const float* rotations, const float* cov3D_precomp, const float* viewmatrix,
+                      const float* projmatrix, float tan_fovx, float tan_fovy, const int* radii,
+                      const float* dL_dmean2D, const float* dL_dconic, const float* dL_ddepths /* nullable */,
+                      const float* dL_dmean3D, float* dL_dpose /* [6] */, char* workspace, size_t workspace_bytes,
+                      void* stream);
+
 /* Replaces CudaRasterizer::Rasterizer::markVisible (rasterizer.h:21,
  * rasterizer_impl.cu:128-135): present[i] = z_view > 0.2 (1-byte bool). */
 int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const float* projmatrix,
