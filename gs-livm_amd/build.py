@@ -42,6 +42,7 @@ UNITS = {
     "api.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "gsr_internal.hpp"), os.path.join(CSRC, "sort_core.hpp"),
+           os.path.join(CSRC, "gsr_workgroup.hpp"), os.path.join(CSRC, "gsr_window.hpp"),
            os.path.join(ROOT, "include", "gsraster.h")]
 
 

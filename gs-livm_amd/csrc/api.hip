@@ -43,7 +43,25 @@ static int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                                             \
+// Input checks that several entry points share: GSR_OK, or the error as fail() left it.
+// H W >= limit: the pixel offsets (0x7fffffff) or pixel indices (0x80000000) of a plane are 32-bit.
+static int check_plane(int height, int width, unsigned long long limit) {
+  if ((unsigned long long)height * (unsigned long long)width >= limit)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  return GSR_OK;
+}
+static int check_workspace(size_t workspace_bytes, size_t need) {
+  if (workspace_bytes < need) return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes", need);
+  return GSR_OK;
+}
+static const char* const kMisaligned = "misaligned pointer: float and int32 arrays need 4-byte alignment";
+// bits: the OR of the pointers
+static int check_aligned4(uintptr_t bits) {
+  if (bits & 3u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned);
+  return GSR_OK;
+}
+
+#define HIP_TRY(expr)                                                                            \
   do {                                                                                            \
     hipError_t e_ = (expr);                                                                       \
     if (e_ != hipSuccess) return fail(GSR_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));       \
@@ -1529,8 +1547,7 @@ int gsr_pose_gradient(int P, int width, int height, const float* means3D, const 
       return fail(GSR_ERR_INVALID_ARGUMENT, "provide either scales+rotations or a precomputed 3D covariance");
     if (!cov3D_precomp && misaligned16(rotations)) return fail_rotations(rotations);
   }
-  if (workspace_bytes < pose_workspace_bytes(P))
-    return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes", pose_workspace_bytes(P));
+  if (int e = check_workspace(workspace_bytes, pose_workspace_bytes(P))) return e;
   const FrameParams fp = make_params(P, 0, 0, width, height, tan_fovx, tan_fovy, scale_modifier);
   HIP_TRY(launch_pose_gradient(fp, radii, means3D, scales, rotations, cov3D_precomp, viewmatrix, projmatrix, dL_dmean2D,
                                dL_dconic, dL_ddepths, dL_dmean3D, dL_dpose, workspace, (hipStream_t)stream_));
@@ -1604,12 +1621,9 @@ int gsr_photometric_loss(int channels, int height, int width, const float* img, 
                          char* workspace, size_t workspace_bytes, void* stream_) {
   g_err[0] = 0;
   if (channels <= 0 || height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if ((unsigned long long)height * (unsigned long long)width >= 0x7fffffffull)  // (32-bit offsets inside a plane)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  if (int e = check_plane(height, width, 0x7fffffffull)) return e;  // (32-bit offsets inside a plane)
   if (!img || !gt || !window11_host || !loss_out3 || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (workspace_bytes < loss_workspace_bytes(channels, height, width))
-    return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes",
-                loss_workspace_bytes(channels, height, width));
+  if (int e = check_workspace(workspace_bytes, loss_workspace_bytes(channels, height, width))) return e;
   HIP_TRY(launch_photometric_loss(channels, height, width, img, gt, window11_host, lambda_dssim, loss_out3, dL_dimg,
                                   workspace, (hipStream_t)stream_));
   return GSR_OK;
@@ -1630,8 +1644,7 @@ int gsr_similarity_loss(int P, int m, int n, const float* points, const int* sel
   if (!out3) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
   if (m > 0 && n > 0) {
     if (!points || !sel || !xyz || !scaling || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-    if (workspace_bytes < simi_workspace_bytes(m, n))
-      return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes", simi_workspace_bytes(m, n));
+    if (int e = check_workspace(workspace_bytes, simi_workspace_bytes(m, n))) return e;
   }
   HIP_TRY(launch_similarity_loss(P, m, n, points, sel, xyz, scaling, lambda, out3, grad_xyz, grad_scaling,
                                  accumulate ? 1 : 0, workspace, (hipStream_t)stream_));
@@ -1650,12 +1663,10 @@ int gsr_delta_depth_loss(int height, int width, const float* depth_src, const fl
   g_err[0] = 0;
   if (height < 2 || width < 2)  // (the reference divides by W - 1 and H - 1)
     return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape: at least 2 x 2");
-  if ((unsigned long long)height * (unsigned long long)width >= 0x80000000ull)  // (32-bit pixel indices)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  if (int e = check_plane(height, width, 0x80000000ull)) return e;  // (32-bit pixel indices)
   if (!depth_src || !acc_src || !depth_ref || !acc_ref || !inv_K_src9 || !K_ref9 || !T_rel12 || !out3 || !workspace)
     return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (workspace_bytes < delta_workspace_bytes(height, width))
-    return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes", delta_workspace_bytes(height, width));
+  if (int e = check_workspace(workspace_bytes, delta_workspace_bytes(height, width))) return e;
   HIP_TRY(launch_delta_depth_loss(height, width, depth_src, acc_src, depth_ref, acc_ref, inv_K_src9, K_ref9, T_rel12,
                                   lambda, out3, warped, dL_ddepth_src, dL_ddepth_ref, workspace,
                                   (hipStream_t)stream_));
@@ -1667,8 +1678,7 @@ int gsr_lidar_depth_image(int n, const float* points_world, const float* T_cw12,
   g_err[0] = 0;
   if (n < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad n");
   if (height < 1 || width < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if ((unsigned long long)height * (unsigned long long)width >= 0x80000000ull)  // (32-bit pixel indices)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  if (int e = check_plane(height, width, 0x80000000ull)) return e;  // (32-bit pixel indices)
   if ((n > 0 && !points_world) || !T_cw12 || !K9 || !lidar_depth) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
   if (!(min_depth >= 0.f && min_depth <= 3.402823466e38f))  // (false for NaN and +inf)
     return fail(GSR_ERR_INVALID_ARGUMENT, "bad min_depth: finite and >= 0");
@@ -1688,14 +1698,11 @@ int gsr_lidar_depth_loss(int height, int width, const float* depth, const float*
                          size_t workspace_bytes, void* stream_) {
   g_err[0] = 0;
   if (height < 1 || width < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if ((unsigned long long)height * (unsigned long long)width >= 0x80000000ull)  // (32-bit pixel indices)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  if (int e = check_plane(height, width, 0x80000000ull)) return e;  // (32-bit pixel indices)
   if (!depth || !acc || !lidar_depth || !out3 || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
   if (!(acc_min > 0.f && acc_min <= 3.402823466e38f))  // (false for NaN and +inf)
     return fail(GSR_ERR_INVALID_ARGUMENT, "bad acc_min: finite and > 0");
-  if (workspace_bytes < lidar_loss_workspace_bytes(height, width))
-    return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes",
-                lidar_loss_workspace_bytes(height, width));
+  if (int e = check_workspace(workspace_bytes, lidar_loss_workspace_bytes(height, width))) return e;
   HIP_TRY(launch_lidar_depth_loss(height, width, depth, acc, lidar_depth, acc_min, lambda, out3, dL_ddepth, dL_dacc,
                                   workspace, (hipStream_t)stream_));
   return GSR_OK;
@@ -1713,12 +1720,9 @@ int gsr_image_metrics(int channels, int height, int width, const float* img, con
                       void* stream_) {
   g_err[0] = 0;
   if (channels <= 0 || height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if ((unsigned long long)height * (unsigned long long)width >= 0x7fffffffull)  // (32-bit offsets inside a plane)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  if (int e = check_plane(height, width, 0x7fffffffull)) return e;  // (32-bit offsets inside a plane)
   if (!img || !gt || !window11_host || !out4 || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (workspace_bytes < metrics_workspace_bytes(channels, height, width))
-    return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes",
-                metrics_workspace_bytes(channels, height, width));
+  if (int e = check_workspace(workspace_bytes, metrics_workspace_bytes(channels, height, width))) return e;
   HIP_TRY(launch_image_metrics(channels, height, width, img, gt, window11_host, out4, totals, workspace,
                                (hipStream_t)stream_));
   return GSR_OK;
@@ -1728,8 +1732,7 @@ int gsr_pack_image_u8(int height, int width, const float* img3, int bgr, unsigne
                       void* stream_) {
   g_err[0] = 0;
   if (height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if ((unsigned long long)height * (unsigned long long)width >= 0x7fffffffull)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  if (int e = check_plane(height, width, 0x7fffffffull)) return e;
   if (!img3 || !out) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
   if (pitch_bytes < 3 * (size_t)width)
     return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: a row has %zu bytes", 3 * (size_t)width);
@@ -1741,8 +1744,7 @@ int gsr_pack_depth_u8(int height, int width, const float* depth, float max_depth
                       size_t pitch_bytes, void* stream_) {
   g_err[0] = 0;
   if (height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if ((unsigned long long)height * (unsigned long long)width >= 0x7fffffffull)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
+  if (int e = check_plane(height, width, 0x7fffffffull)) return e;
   if (!depth || !out) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
   if (pitch_bytes < (size_t)width)
     return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: a row has %zu bytes", (size_t)width);
@@ -1814,11 +1816,10 @@ int gsr_prune_mark(int P, const float* xyz, const float* scaling_raw, const floa
   if (!row_map || !counts5) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
   if (P > 0 && (!xyz || !scaling_raw || !rotation_raw || !opacity_raw || !reasons || !workspace))
     return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (((uintptr_t)xyz | (uintptr_t)scaling_raw | (uintptr_t)rotation_raw | (uintptr_t)opacity_raw |
-       (uintptr_t)row_map | (uintptr_t)counts5 | (uintptr_t)workspace) & 3u)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "misaligned pointer: float and int32 arrays need 4-byte alignment");
-  if (workspace_bytes < prune_workspace_bytes(P))
-    return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes", prune_workspace_bytes(P));
+  if (int e = check_aligned4((uintptr_t)xyz | (uintptr_t)scaling_raw | (uintptr_t)rotation_raw | (uintptr_t)opacity_raw |
+                             (uintptr_t)row_map | (uintptr_t)counts5 | (uintptr_t)workspace))
+    return e;
+  if (int e = check_workspace(workspace_bytes, prune_workspace_bytes(P))) return e;
   HIP_TRY(launch_prune_mark(P, xyz, scaling_raw, rotation_raw, opacity_raw, drop, min_opacity, max_scale,
                             drop_nonfinite ? 1 : 0, reasons, row_map, counts5, workspace, (hipStream_t)stream_));
   return GSR_OK;
@@ -1839,24 +1840,20 @@ int gsr_prune_compact(int P, int n_tensors, const float* const* src, float* cons
   if (!src || !dst || !reasons || !row_map) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
   for (int k = 0; k < n_tensors; k++)
     if (widths[k] > 0 && (!src[k] || !dst[k])) return fail(GSR_ERR_INVALID_ARGUMENT, "null tensor pointer (tensor %d)", k);
-  if ((uintptr_t)row_map & 3u)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "misaligned pointer: float and int32 arrays need 4-byte alignment");
+  if (int e = check_aligned4((uintptr_t)row_map)) return e;
   for (int k = 0; k < n_tensors; k++)
     if (widths[k] > 0 && (((uintptr_t)src[k] | (uintptr_t)dst[k]) & 3u))
-      return fail(GSR_ERR_INVALID_ARGUMENT, "misaligned pointer: float and int32 arrays need 4-byte alignment (tensor %d)", k);
+      return fail(GSR_ERR_INVALID_ARGUMENT, "%s (tensor %d)", kMisaligned, k);
   HIP_TRY(launch_prune_compact(P, n_tensors, src, dst, widths, reasons, row_map, (hipStream_t)stream_));
   return GSR_OK;
 }
-
-static const char* const kMisaligned = "misaligned pointer: float and int32 arrays need 4-byte alignment";
 
 int gsr_density_accumulate(int P, const int* radii, const float* dL_dmean2D, float* stats, void* stream_) {
   g_err[0] = 0;
   if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
   if (P == 0) return GSR_OK;
   if (!radii || !dL_dmean2D || !stats) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (((uintptr_t)radii | (uintptr_t)dL_dmean2D | (uintptr_t)stats) & 3u)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned);
+  if (int e = check_aligned4((uintptr_t)radii | (uintptr_t)dL_dmean2D | (uintptr_t)stats)) return e;
   HIP_TRY(launch_density_accumulate(P, radii, dL_dmean2D, stats, (hipStream_t)stream_));
   return GSR_OK;
 }
@@ -1873,10 +1870,10 @@ int gsr_densify_mark(int P, const float* stats, const float* scaling_raw, float 
   if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
   if (!offsets || !counts3) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
   if (P > 0 && (!stats || !scaling_raw || !kinds || !workspace)) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (((uintptr_t)stats | (uintptr_t)scaling_raw | (uintptr_t)offsets | (uintptr_t)counts3 | (uintptr_t)workspace) & 3u)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned);
-  if (workspace_bytes < densify_workspace_bytes(P))
-    return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes", densify_workspace_bytes(P));
+  if (int e = check_aligned4((uintptr_t)stats | (uintptr_t)scaling_raw | (uintptr_t)offsets | (uintptr_t)counts3 |
+                             (uintptr_t)workspace))
+    return e;
+  if (int e = check_workspace(workspace_bytes, densify_workspace_bytes(P))) return e;
   HIP_TRY(launch_densify_mark(P, stats, scaling_raw, grad_threshold, size_threshold, max_new, kinds, offsets, counts3,
                               workspace, (hipStream_t)stream_));
   return GSR_OK;
@@ -1904,7 +1901,7 @@ int gsr_densify_apply(int P, int M, int n_new, const unsigned char* kinds, const
     bits |= (uintptr_t)params6[k] | (uintptr_t)(exp_avg6 ? exp_avg6[k] : nullptr) |
             (uintptr_t)(exp_avg_sq6 ? exp_avg_sq6[k] : nullptr);
   }
-  if (bits & 3u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned);
+  if (int e = check_aligned4(bits)) return e;
   HIP_TRY(launch_densify_apply(P, M, kinds, offsets, seed, params6, exp_avg6, exp_avg_sq6, stats,
                                (hipStream_t)stream_));
   return GSR_OK;

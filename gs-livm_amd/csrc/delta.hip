@@ -51,6 +51,7 @@
 //   k_delta_scatter  thread = pixel: the four fixed-point contributions; workgroup 0 sums the partials and writes out3
 //   k_delta_convert  thread = destination pixel: accumulator back to float, times r_z, plus the coordinate term, times c
 #include "gsr_internal.hpp"
+#include "gsr_workgroup.hpp"
 
 namespace gsr {
 
@@ -91,23 +92,12 @@ struct DeltaWorkspace {
   }
 };
 
-// (the same fixed-order workgroup sum as simi.hip's: xor-butterfly inside each wave, then the four wave sums)
-__device__ __forceinline__ double delta_block_sum(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-constexpr float DELTA_COORD_MAX_ = 1073741824.f;  // 2^30: beyond it (or not finite) a sample coordinate is "outside"
 constexpr float DELTA_MIN_DEPTH_ = 0.01f;         // inv_depth's clamp (loss_utils.cuh:15-21)
 
 // The cell of a sample coordinate: false = outside (no tap can lie in the image); else the integer corner (ix, iy) in
 // [-1, W) x [-1, H) and the fractions.  The comparison is false for NaN, so nothing non-finite reaches the conversion.
 __device__ __forceinline__ bool delta_cell(float X, float Y, int W, int H, int& ix, int& iy, float& fx, float& fy) {
-  if (!(fabsf(X) <= DELTA_COORD_MAX_) || !(fabsf(Y) <= DELTA_COORD_MAX_)) return false;
+  if (!(fabsf(X) <= COORD_MAX_) || !(fabsf(Y) <= COORD_MAX_)) return false;
   const float x0 = floorf(X), y0 = floorf(Y);
   ix = (int)x0; iy = (int)y0;
   fx = X - x0; fy = Y - y0;
@@ -192,22 +182,15 @@ __global__ __launch_bounds__(256) void k_delta_sample(const int N, const int W, 
       absu = fabsf(ui);
     }
   }
-  const double gs = delta_block_sum((double)gap, shsum);
-  int cnt = on;
+  double gs = (double)gap;
+  block_sum_pair(gs, on, shsum, shcnt);
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    cnt += __shfl_xor(cnt, o, 64);
-    absu = fmaxf(absu, __shfl_xor(absu, o, 64));
-  }
-  if ((threadIdx.x & 63) == 0) {
-    shcnt[threadIdx.x >> 6] = cnt;
-    // non-negative floats order like their bits; a maximum does not depend on the order it is taken in
-    if (absu > 0.f) atomicMax(maxbits, __float_as_uint(absu));
-  }
-  __syncthreads();
+  for (int o = 32; o > 0; o >>= 1) absu = fmaxf(absu, __shfl_xor(absu, o, 64));
+  // non-negative floats order like their bits; a maximum does not depend on the order it is taken in
+  if ((threadIdx.x & 63) == 0 && absu > 0.f) atomicMax(maxbits, __float_as_uint(absu));
   if (threadIdx.x == 0) {
     gap_part[blockIdx.x] = gs;
-    cnt_part[blockIdx.x] = (shcnt[0] + shcnt[1]) + (shcnt[2] + shcnt[3]);
+    cnt_part[blockIdx.x] = on;
   }
 }
 
@@ -228,13 +211,8 @@ __global__ __launch_bounds__(256) void k_delta_scatter(const int N, const int W,
                                                        float* __restrict__ out3) {
   __shared__ double shsum[4];
   if (blockIdx.x == 0) {  // the scalars: thread-strided over the partials, then the workgroup tree -- one fixed order
-    double gs = 0.0, cs = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 256) {
-      gs += gap_part[b];
-      cs += (double)cnt_part[b];
-    }
-    gs = delta_block_sum(gs, shsum);
-    cs = delta_block_sum(cs, shsum);
+    double gs, cs;
+    partial_pairs_sum(gap_part, cnt_part, nblocks, shsum, gs, cs);
     if (threadIdx.x == 0) {
       const float mean_gap = (float)(gs / (double)N);
       out3[0] = lambda * mean_gap;

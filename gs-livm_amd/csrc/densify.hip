@@ -23,19 +23,16 @@
 // P + offsets[i] >= P, which no other thread reads or writes.  The parent of a split becomes its first child in place,
 // so every existing row keeps its number (VoxelIndex needs no remap) and nothing is compacted.
 #include "gsr_internal.hpp"
+#include "gsr_workgroup.hpp"
 
 namespace gsr {
 
-constexpr int DENSIFY_BLOCK = 256;  // rows per workgroup (4 waves)
-constexpr int DENSIFY_WAVES = DENSIFY_BLOCK / 64;
-constexpr int DENSIFY_SCAN_ITEMS = 4;  // consecutive workgroup totals per thread of k_densify_scan: 1024 per pass
+constexpr int DENSIFY_BLOCK = WG_THREADS;  // rows per workgroup (4 waves)
 constexpr float LN_1_6 = 0.47000363f;  // log(0.8 * 2): a child's scale is the parent's / 1.6
 
 inline size_t densify_blocks(int P) { return ((size_t)P + DENSIFY_BLOCK - 1) / DENSIFY_BLOCK; }
 // [2][nblocks] int32: [0] candidates per workgroup -> their exclusive scan; [1] splits per workgroup
 size_t densify_workspace_bytes(int P) { return P > 0 ? 2 * densify_blocks(P) * sizeof(int) : 0; }
-
-__device__ __forceinline__ bool nonfinite_(float x) { return (__float_as_uint(x) & 0x7F800000u) == 0x7F800000u; }
 
 __global__ __launch_bounds__(DENSIFY_BLOCK) void k_density_accumulate(const int P, const int* __restrict__ radii,
                                                                       const float* __restrict__ dL_dmean2D,
@@ -59,7 +56,7 @@ __global__ __launch_bounds__(DENSIFY_BLOCK) void k_densify_mark(const int P, con
                                                                 const float grad_threshold, const float size_threshold,
                                                                 unsigned char* __restrict__ kinds,
                                                                 int* __restrict__ totals, const int nblocks) {
-  __shared__ int sh[DENSIFY_WAVES][2];
+  __shared__ int sh[WG_WAVES][2];
   const int i = blockIdx.x * DENSIFY_BLOCK + threadIdx.x;
   unsigned kind = 0;
   if (i < P) {
@@ -71,79 +68,25 @@ __global__ __launch_bounds__(DENSIFY_BLOCK) void k_densify_mark(const int P, con
       kind = (expf(s0) > size_threshold || expf(s1) > size_threshold || expf(s2) > size_threshold) ? 2u : 1u;
     kinds[i] = (unsigned char)kind;
   }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n_cand = __popcll(__ballot(kind != 0)), n_split = __popcll(__ballot(kind == 2));
-  if (lane == 0) { sh[wave][0] = n_cand; sh[wave][1] = n_split; }
-  __syncthreads();
-  if (threadIdx.x < 2) {
-    int t = 0;
-#pragma unroll
-    for (int w = 0; w < DENSIFY_WAVES; w++) t += sh[w][threadIdx.x];
-    totals[(size_t)threadIdx.x * nblocks + blockIdx.x] = t;
-  }
+  const int n[2] = {(int)__popcll(__ballot(kind != 0)), (int)__popcll(__ballot(kind == 2))};  // candidates, splits
+  store_block_totals(n, sh, totals, nblocks);
 }
 
-// rank of a marked row among the marked rows of its workgroup; `sh`: DENSIFY_WAVES ints.  All 256 threads call it.
-__device__ __forceinline__ int rank_in_block(bool marked, int* sh) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const unsigned long long b = __ballot(marked);
-  if (lane == 0) sh[wave] = __popcll(b);
-  __syncthreads();
-  int before = __popcll(b & ((1ull << lane) - 1ull));
-#pragma unroll
-  for (int w = 0; w < DENSIFY_WAVES; w++)
-    if (w < wave) before += sh[w];
-  return before;
-}
-
-// ONE workgroup.  totals[0][.] -> exclusive scan in place, 1024 workgroup totals per pass of the loop with the running
-// sum carried in a register.  cap: max_new, or INT_MAX for "unlimited".  A workgroup that ends at or below the cap
-// contributes its split total; at most one workgroup starts below the cap and ends beyond it, and its accepted splits
-// are counted from its kinds.  nblocks == 0 (P == 0) writes zeros.
+// ONE workgroup.  totals[0][.] -> exclusive scan in place (scan_totals).  cap: max_new, or INT_MAX for "unlimited".
+// A workgroup that ends at or below the cap contributes its split total; at most one workgroup starts below the cap
+// and ends beyond it, and its accepted splits are counted from its kinds.  nblocks == 0 (P == 0) writes zeros.
 __global__ __launch_bounds__(DENSIFY_BLOCK) void k_densify_scan(const int P, const unsigned char* __restrict__ kinds,
                                                                 int* __restrict__ totals, const int nblocks,
                                                                 const int cap, int* __restrict__ counts3,
                                                                 int* __restrict__ offsets_end) {
-  __shared__ int sh[DENSIFY_WAVES];
+  __shared__ int sh[WG_WAVES];
   __shared__ int sh_cut[2];  // the workgroup the cap cuts through and its first offset
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (threadIdx.x == 0) sh_cut[0] = -1;
-  int carry = 0, splits = 0;
-  for (int base = 0; base < nblocks; base += DENSIFY_BLOCK * DENSIFY_SCAN_ITEMS) {  // (uniform trip count)
-    const int j0 = base + (int)threadIdx.x * DENSIFY_SCAN_ITEMS;
-    int v[DENSIFY_SCAN_ITEMS], mine = 0;
-#pragma unroll
-    for (int k = 0; k < DENSIFY_SCAN_ITEMS; k++) {
-      v[k] = j0 + k < nblocks ? totals[j0 + k] : 0;
-      mine += v[k];
-    }
-    int incl = mine;  // inclusive scan of the threads' sums inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d);
-      if (lane >= d) incl += up;
-    }
-    __syncthreads();  // the previous pass has read sh; sh_cut[0] = -1 is visible
-    if (lane == 63) sh[wave] = incl;
-    __syncthreads();
-    int before = carry, all = 0;
-#pragma unroll
-    for (int w = 0; w < DENSIFY_WAVES; w++) {
-      if (w < wave) before += sh[w];
-      all += sh[w];
-    }
-    int run = before + incl - mine;
-#pragma unroll
-    for (int k = 0; k < DENSIFY_SCAN_ITEMS; k++) {
-      if (j0 + k < nblocks) {
-        totals[j0 + k] = run;
-        if (run + v[k] <= cap) splits += totals[(size_t)nblocks + j0 + k];
-        else if (run < cap) { sh_cut[0] = j0 + k; sh_cut[1] = run; }
-      }
-      run += v[k];
-    }
-    carry += all;
-  }
+  if (threadIdx.x == 0) sh_cut[0] = -1;  // (visible to the items: they run behind the barriers of their pass)
+  int splits = 0;
+  const int carry = scan_totals(totals, nblocks, sh, [&](int j, int base, int total) {
+    if (base + total <= cap) splits += totals[(size_t)nblocks + j];
+    else if (base < cap) { sh_cut[0] = j; sh_cut[1] = base; }
+  });
   __syncthreads();
   const int cut = sh_cut[0];
   if (cut >= 0) {  // (uniform)
@@ -152,15 +95,8 @@ __global__ __launch_bounds__(DENSIFY_BLOCK) void k_densify_scan(const int P, con
     const int rank = rank_in_block(kind != 0, sh);
     if (kind == 2 && sh_cut[1] + rank < cap) splits++;
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) splits += __shfl_xor(splits, d);
-  __syncthreads();
-  if (lane == 0) sh[wave] = splits;
-  __syncthreads();
+  const int n_split = block_sum(splits, sh);
   if (threadIdx.x == 0) {
-    int n_split = 0;
-#pragma unroll
-    for (int w = 0; w < DENSIFY_WAVES; w++) n_split += sh[w];
     const int n_new = carry < cap ? carry : cap;
     counts3[0] = n_new;
     counts3[1] = n_new - n_split;
@@ -172,7 +108,7 @@ __global__ __launch_bounds__(DENSIFY_BLOCK) void k_densify_scan(const int P, con
 __global__ __launch_bounds__(DENSIFY_BLOCK) void k_densify_rank(const int P, unsigned char* __restrict__ kinds,
                                                                 const int* __restrict__ bases, const int cap,
                                                                 int* __restrict__ offsets) {
-  __shared__ int sh[DENSIFY_WAVES];
+  __shared__ int sh[WG_WAVES];
   const int i = blockIdx.x * DENSIFY_BLOCK + threadIdx.x;
   const bool cand = i < P && kinds[i] != 0;
   const int at = bases[blockIdx.x] + rank_in_block(cand, sh);

@@ -25,14 +25,15 @@
 //   e = D / A - z_L,  L = lambda sum|e| / max(n_sup, 1)
 //   dL/dD = c sign(e) / A,  dL/dA = -c sign(e) D / A^2,  c = lambda / n_sup,  sign(0) = 0 as loss.hip; 0 elsewhere
 // The normaliser is the supervised count, known on the device only, so the gradients are a launch of their own behind
-// the finish.  The sums are per-workgroup f64 partials added in one fixed order (delta_block_sum's tree) and narrowed
-// once: bitwise reproducible.  Three launches (two without gradients), no host synchronisation, no allocation:
+// the finish.  The sums are per-workgroup f64 partials added in one fixed order (block_sum's tree, gsr_workgroup.hpp)
+// and narrowed once: bitwise reproducible.  Three launches (two without gradients), no host synchronisation, no allocation:
 //   k_lidar_loss_forward  thread = pixel: |e| and the mask; per-workgroup f64 sums and counts into the workspace
 //   k_lidar_loss_finish   one workgroup: the partials in a fixed order; out3; c into the workspace
 //   k_lidar_loss_grads    thread = pixel: both gradients, every element written
 // Bounds: every thread tests its index against the count; a pixel index comes from coordinates that were tested
 // against +-2^30 and then against the image before the atomic.
 #include "gsr_internal.hpp"
+#include "gsr_workgroup.hpp"
 
 namespace gsr {
 
@@ -61,23 +62,6 @@ struct LidarWorkspace {
   }
 };
 
-// (delta_block_sum's fixed-order workgroup sum: xor-butterfly inside each wave, then the four wave sums)
-__device__ __forceinline__ double lidar_block_sum(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-__device__ __forceinline__ int lidar_wave_count(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-constexpr float LIDAR_COORD_MAX_ = 1073741824.f;  // 2^30: beyond it (or not finite) a coordinate is never converted
 constexpr unsigned int LIDAR_EMPTY_ = 0xFFFFFFFFu;
 
 __global__ __launch_bounds__(256) void k_lidar_clear(const int N, const unsigned int word,
@@ -102,7 +86,7 @@ __global__ __launch_bounds__(256) void k_lidar_splat(const int n, const int W, c
     const float X = nx / nz, Y = ny / nz;
     // every comparison is false for NaN; z <= max_depth with z finite (max_depth may be +inf)
     const bool fin = fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(w) < INFINITY && fabsf(z) < INFINITY;
-    if (fin && z > min_depth && z <= max_depth && fabsf(X) <= LIDAR_COORD_MAX_ && fabsf(Y) <= LIDAR_COORD_MAX_) {
+    if (fin && z > min_depth && z <= max_depth && fabsf(X) <= COORD_MAX_ && fabsf(Y) <= COORD_MAX_) {
       const int ix = (int)floorf(X + 0.5f), iy = (int)floorf(Y + 0.5f);
       if (ix >= 0 && ix < W && iy >= 0 && iy < H) {
         kept = 1;
@@ -112,7 +96,7 @@ __global__ __launch_bounds__(256) void k_lidar_splat(const int n, const int W, c
     }
   }
   if (counts2) {
-    kept = lidar_wave_count(kept);
+    kept = wave_sum(kept);
     if ((threadIdx.x & 63) == 0 && kept) atomicAdd(&counts2[0], kept);
   }
 }
@@ -126,7 +110,7 @@ __global__ __launch_bounds__(256) void k_lidar_convert(const int N, unsigned int
     else hit = 1;
   }
   if (counts2) {
-    hit = lidar_wave_count(hit);
+    hit = wave_sum(hit);
     if ((threadIdx.x & 63) == 0 && hit) atomicAdd(&counts2[1], hit);
   }
 }
@@ -146,13 +130,11 @@ __global__ __launch_bounds__(256) void k_lidar_loss_forward(const int N, const f
     on = (zl > 0.f && a >= acc_min) ? 1 : 0;
     if (on) ae = fabsf(depth[i] / a - zl);
   }
-  const double s = lidar_block_sum((double)ae, shsum);
-  const int cnt = lidar_wave_count(on);
-  if ((threadIdx.x & 63) == 0) shcnt[threadIdx.x >> 6] = cnt;
-  __syncthreads();
+  double s = (double)ae;
+  block_sum_pair(s, on, shsum, shcnt);
   if (threadIdx.x == 0) {
     abs_part[blockIdx.x] = s;
-    cnt_part[blockIdx.x] = (shcnt[0] + shcnt[1]) + (shcnt[2] + shcnt[3]);
+    cnt_part[blockIdx.x] = on;
   }
 }
 
@@ -162,13 +144,8 @@ __global__ __launch_bounds__(256) void k_lidar_loss_finish(const int N, const in
                                                            float* __restrict__ scale) {
   __shared__ double shsum[4];
   // thread-strided over the partials, then the workgroup tree -- one fixed order (the counts are exact in double)
-  double as = 0.0, cs = 0.0;
-  for (int b = threadIdx.x; b < nblocks; b += 256) {
-    as += abs_part[b];
-    cs += (double)cnt_part[b];
-  }
-  as = lidar_block_sum(as, shsum);
-  cs = lidar_block_sum(cs, shsum);
+  double as, cs;
+  partial_pairs_sum(abs_part, cnt_part, nblocks, shsum, as, cs);
   if (threadIdx.x == 0) {
     const float mean_abs = cs > 0.0 ? (float)(as / cs) : 0.f;
     out3[0] = cs > 0.0 ? lambda * mean_abs : 0.f;

@@ -17,108 +17,51 @@
 // (x - window_size)/2, loss_utils.cuh:24-31), so correlation (forward) and its transpose (backward) are kept
 // apart.  Zero padding of window/2, as conv2d(padding = window_size / 2).
 #include "gsr_internal.hpp"
+#include "gsr_window.hpp"
 
 namespace gsr {
-
-constexpr int LW_ = 11;          // window taps
-constexpr int LR_ = LW_ / 2;     // halo
-// Work unit of one 256-thread workgroup: 54 x 32 outputs.  Wave w owns the 8 output rows 8w .. 8w+7, lane l the input
-// column x0 - 5 + l (64 columns = 54 outputs + the halo), so every global load of the vertical pass is one coalesced
-// 256-byte row segment and the pass runs in registers straight from those loads (18 rows -> 8 outputs per moment, taps
-// in the order of a plain 11-tap sum); its results cross the workgroup's ONE barrier through LDS and the horizontal pass
-// is register-blocked seven outputs to a thread (17 staged values per moment).
-constexpr int LTX_ = 54, LTY_ = 32;
-constexpr int LSEG_ = 8;                    // output rows per wave
-constexpr int LIN_ = LSEG_ + 2 * LR_;       // 18 input rows per wave
-constexpr int LHO_ = 7;                     // horizontal pass: outputs per thread (8 threads x 7 >= 54)
-constexpr int LFLAT_ = (LTX_ * LTY_ + 255) / 256;  // 7 elements per thread in the tile's flattened order
-constexpr int LSTRIDE_ = 72;                // LDS row stride: (8 r + 7 g + k) mod 64 is conflict-free over a wave's 8 x 8
-constexpr float SSIM_C1 = 0.01f * 0.01f, SSIM_C2 = 0.03f * 0.03f;  // loss_utils.cuh:8-9
-
-struct LossWindow { float w[LW_]; };
 
 // mu(q) = sum_k w[k] * f(q + k - 5)   (cross-correlation, zero padded): what conv2d computes.  SSIM needs the two
 // variances only through their sum (d2 = sigma1^2 + sigma2^2 + C2), so four windowed moments are carried, not five:
 // E[x], E[y], E[x^2 + y^2], E[xy].
 __global__ __launch_bounds__(256) void k_loss_forward(const int C, const int H, const int W,
                                                       const float* __restrict__ img, const float* __restrict__ gt,
-                                                      const LossWindow win, float* __restrict__ mapA,
+                                                      const Window win, float* __restrict__ mapA,
                                                       float* __restrict__ mapB, float* __restrict__ mapC,
                                                       float* __restrict__ partials) {
-  __shared__ float hv[4][LTY_][LSTRIDE_];  // vertically filtered moments
+  __shared__ WindowLds hv[4];  // vertically filtered moments
   __shared__ float red[2][4];
   const int c = blockIdx.z;
-  const int x0 = blockIdx.x * LTX_, y0 = blockIdx.y * LTY_;
+  const int x0 = blockIdx.x * WIN_TX, y0 = blockIdx.y * WIN_TY;
   const size_t plane = (size_t)c * H * W;
-  const float* X = img + plane;
-  const float* Y = gt + plane;
   const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
-  float l1 = 0.f, ss = 0.f;
+  float sums[2] = {0.f, 0.f};  // |x - y|, SSIM
   {
-    const int gx = x0 - LR_ + lane;
-    const bool col_in = gx >= 0 && gx < W;
-    const int gxc = min(max(gx, 0), W - 1);
-    float vx[LIN_], vy[LIN_];
+    const float* const planes[2] = {img + plane, gt + plane};
+    float v[2][WIN_IN];
+    const bool col_in = window_load_columns(planes, H, W, x0, y0, v);
+    window_vertical<4, false>(win, hv, [&](int i, float(&m)[4]) {
+      const float x = v[0][i], y = v[1][i];
+      m[0] = x; m[1] = y; m[2] = __builtin_fmaf(y, y, x * x); m[3] = x * y;
+    });
+    if (lane >= WIN_HALO && lane < WIN_HALO + WIN_TX && col_in) {  // the L1 term of this thread's own eight output pixels
 #pragma unroll
-    for (int i = 0; i < LIN_; i++) {  // all 36 loads are in flight before the first is consumed: clamped addresses,
-      const int gy = y0 + LSEG_ * seg - LR_ + i;  // unconditional loads, zero padding by select (no branch per load)
-      const int off = min(max(gy, 0), H - 1) * W + gxc;
-      const float a = X[off], b = Y[off];
-      const bool in = col_in && gy >= 0 && gy < H;
-      vx[i] = in ? a : 0.f;
-      vy[i] = in ? b : 0.f;
-    }
-    float acc[LSEG_][4];
-#pragma unroll
-    for (int o = 0; o < LSEG_; o++) acc[o][0] = acc[o][1] = acc[o][2] = acc[o][3] = 0.f;
-#pragma unroll
-    for (int i = 0; i < LIN_; i++) {
-      const float x = vx[i], y = vy[i];
-      const float p2 = __builtin_fmaf(y, y, x * x), p3 = x * y;
-#pragma unroll
-      for (int o = 0; o < LSEG_; o++) {
-        const int k = i - o;
-        if (k >= 0 && k < LW_) {
-          const float wk = win.w[k];
-          acc[o][0] += wk * x; acc[o][1] += wk * y; acc[o][2] += wk * p2; acc[o][3] += wk * p3;
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 0; o < LSEG_; o++) {
-#pragma unroll
-      for (int q = 0; q < 4; q++) hv[q][LSEG_ * seg + o][lane] = acc[o][q];
-    }
-    if (lane >= LR_ && lane < LR_ + LTX_ && col_in) {  // the L1 term of this thread's own eight output pixels
-#pragma unroll
-      for (int o = 0; o < LSEG_; o++)
-        if (y0 + LSEG_ * seg + o < H) l1 += fabsf(vx[o + LR_] - vy[o + LR_]);
+      for (int o = 0; o < WIN_SEG; o++)
+        if (y0 + WIN_SEG * seg + o < H) sums[0] += fabsf(v[0][o + WIN_HALO] - v[1][o + WIN_HALO]);
     }
   }
   __syncthreads();
   {
-    const int r = threadIdx.x >> 3, c0 = (threadIdx.x & 7) * LHO_;
-    float m[4][LHO_];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      float v[LHO_ + LW_ - 1];
-#pragma unroll
-      for (int k = 0; k < LHO_ + LW_ - 1; k++) v[k] = hv[q][r][c0 + k];  // (the last group reads into the row padding)
-#pragma unroll
-      for (int o = 0; o < LHO_; o++) {
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < LW_; k++) a += win.w[k] * v[o + k];
-        m[q][o] = a;
-      }
-    }
+    const int r = threadIdx.x >> 3, c0 = (threadIdx.x & 7) * WIN_HO;
+    float m[4][WIN_HO];
+    window_horizontal<4, false>(win, hv, m);
     const int gy = y0 + r;
-    float oa[LHO_], ob[LHO_], oc[LHO_];
+    float oa[WIN_HO], ob[WIN_HO], oc[WIN_HO];
 #pragma unroll
-    for (int o = 0; o < LHO_; o++) {
+    for (int o = 0; o < WIN_HO; o++) {
       const int gx = x0 + c0 + o;
       oa[o] = ob[o] = oc[o] = 0.f;
-      if (c0 + o < LTX_ && gx < W && gy < H) {
+      if (c0 + o < WIN_TX && gx < W && gy < H) {
         const float mu1 = m[0][o], mu2 = m[1][o], e_sum = m[2][o], e12 = m[3][o];
         const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
         const float s12 = e12 - mu12;
@@ -135,7 +78,7 @@ __global__ __launch_bounds__(256) void k_loss_forward(const int C, const int H, 
         oa[o] = ds_dmu1 - 2.f * mu1 * ds_ds1 - mu2 * ds_ds12;
         ob[o] = ds_ds1;
         oc[o] = ds_ds12;
-        ss += sv;
+        sums[1] += sv;
       }
     }
     // A thread's seven outputs are adjacent in a row: stored from here, a wave's store would be 64 separate 4-byte
@@ -143,54 +86,37 @@ __global__ __launch_bounds__(256) void k_loss_forward(const int C, const int H, 
     // and leave in the flattened order of the tile, 54-float row segments to consecutive lanes.
     __syncthreads();  // (everyone has read hv)
 #pragma unroll
-    for (int o = 0; o < LHO_; o++) { hv[0][r][c0 + o] = oa[o]; hv[1][r][c0 + o] = ob[o]; hv[2][r][c0 + o] = oc[o]; }
+    for (int o = 0; o < WIN_HO; o++) { hv[0][r][c0 + o] = oa[o]; hv[1][r][c0 + o] = ob[o]; hv[2][r][c0 + o] = oc[o]; }
   }
   __syncthreads();
 #pragma unroll
-  for (int it = 0; it < LFLAT_; it++) {
+  for (int it = 0; it < WIN_FLAT; it++) {
     const int e = it * 256 + (int)threadIdx.x;
-    const int row = e / LTX_, col = e - row * LTX_;
+    const int row = e / WIN_TX, col = e - row * WIN_TX;
     const int gx = x0 + col, gy = y0 + row;
-    if (e < LTX_ * LTY_ && gx < W && gy < H) {
+    if (e < WIN_TX * WIN_TY && gx < W && gy < H) {
       const size_t oidx = plane + (size_t)gy * W + gx;
       mapA[oidx] = hv[0][row][col];
       mapB[oidx] = hv[1][row][col];
       mapC[oidx] = hv[2][row][col];
     }
   }
-  // fixed-order workgroup reduction -> one partial pair per workgroup
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    l1 += __shfl_xor(l1, o, 64);
-    ss += __shfl_xor(ss, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = l1; red[1][threadIdx.x >> 6] = ss; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const size_t b = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partials[2 * b] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    partials[2 * b + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-  }
+  window_store_partials(sums, red, partials);  // one partial pair per workgroup
 }
 
 __global__ __launch_bounds__(1024) void k_loss_finalize(const float* __restrict__ partials, const int nblocks,
                                                         const float inv_n, const float lambda,
                                                         float* __restrict__ out3) {
   // one workgroup, fixed association order (thread-strided partial sums in f64, then a tree): deterministic
-  __shared__ double r1[1024], r2[1024];
-  double a = 0.0, b = 0.0;
+  __shared__ double r[2][1024];
+  double t[2] = {0.0, 0.0};
   for (int i = threadIdx.x; i < nblocks; i += 1024) {
     const float2 v = reinterpret_cast<const float2*>(partials)[i];
-    a += v.x; b += v.y;
+    t[0] += v.x; t[1] += v.y;
   }
-  r1[threadIdx.x] = a; r2[threadIdx.x] = b;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { r1[threadIdx.x] += r1[threadIdx.x + o]; r2[threadIdx.x] += r2[threadIdx.x + o]; }
-    __syncthreads();
-  }
+  tree_sum_1024(t, r);
   if (threadIdx.x == 0) {
-    const float l1 = (float)(r1[0] * inv_n), ssim = (float)(r2[0] * inv_n);
+    const float l1 = (float)(t[0] * inv_n), ssim = (float)(t[1] * inv_n);
     out3[0] = (1.f - lambda) * l1 + lambda * (1.f - ssim);
     out3[1] = l1;
     out3[2] = ssim;
@@ -202,90 +128,45 @@ __global__ __launch_bounds__(1024) void k_loss_finalize(const float* __restrict_
 // derivative maps.
 __global__ __launch_bounds__(256) void k_loss_backward(const int C, const int H, const int W,
                                                        const float* __restrict__ img, const float* __restrict__ gt,
-                                                       const LossWindow win, const float* __restrict__ mapA,
+                                                       const Window win, const float* __restrict__ mapA,
                                                        const float* __restrict__ mapB, const float* __restrict__ mapC,
                                                        const float inv_n, const float lambda,
                                                        float* __restrict__ dL_dimg) {
-  __shared__ float hv[3][LTY_][LSTRIDE_];
+  __shared__ WindowLds hv[3];
   const int c = blockIdx.z;
-  const int x0 = blockIdx.x * LTX_, y0 = blockIdx.y * LTY_;
+  const int x0 = blockIdx.x * WIN_TX, y0 = blockIdx.y * WIN_TY;
   const size_t plane = (size_t)c * H * W;
-  const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
-  const int r = threadIdx.x >> 3, c0 = (threadIdx.x & 7) * LHO_;
-  float px[LFLAT_], py[LFLAT_];  // img / gt at this thread's output pixels (flattened order), requested with the maps
+  const int r = threadIdx.x >> 3, c0 = (threadIdx.x & 7) * WIN_HO;
+  float px[WIN_FLAT], py[WIN_FLAT];  // img / gt at this thread's output pixels (flattened order), requested with the maps
   {
-    const int gx = x0 - LR_ + lane;
-    const bool col_in = gx >= 0 && gx < W;
-    const int gxc = min(max(gx, 0), W - 1);
-    const float* MA = mapA + plane;
-    const float* MB = mapB + plane;
-    const float* MC = mapC + plane;
-    float va[LIN_], vb[LIN_], vc[LIN_];
+    const float* const planes[3] = {mapA + plane, mapB + plane, mapC + plane};
+    float v[3][WIN_IN];
+    window_load_columns(planes, H, W, x0, y0, v);
 #pragma unroll
-    for (int i = 0; i < LIN_; i++) {  // (clamped addresses, unconditional loads, zero padding by select)
-      const int gy = y0 + LSEG_ * seg - LR_ + i;
-      const int off = min(max(gy, 0), H - 1) * W + gxc;
-      const float a = MA[off], b = MB[off], cc = MC[off];
-      const bool in = col_in && gy >= 0 && gy < H;
-      va[i] = in ? a : 0.f;
-      vb[i] = in ? b : 0.f;
-      vc[i] = in ? cc : 0.f;
-    }
-#pragma unroll
-    for (int it = 0; it < LFLAT_; it++) {  // (pixels outside the image or the tile are never stored: any valid address)
+    for (int it = 0; it < WIN_FLAT; it++) {  // (pixels outside the image or the tile are never stored: any valid address)
       const int e = it * 256 + (int)threadIdx.x;
-      const int row = e / LTX_, col = e - row * LTX_;
+      const int row = e / WIN_TX, col = e - row * WIN_TX;
       const int off = min(y0 + row, H - 1) * W + min(x0 + col, W - 1);
       px[it] = img[plane + off];
       py[it] = gt[plane + off];
     }
-    float acc[LSEG_][3];
-#pragma unroll
-    for (int o = 0; o < LSEG_; o++) acc[o][0] = acc[o][1] = acc[o][2] = 0.f;
-#pragma unroll
-    for (int i = 0; i < LIN_; i++) {
-#pragma unroll
-      for (int o = 0; o < LSEG_; o++) {
-        const int k = i - o;
-        if (k >= 0 && k < LW_) {
-          const float wk = win.w[LW_ - 1 - k];  // flipped taps
-          acc[o][0] += wk * va[i]; acc[o][1] += wk * vb[i]; acc[o][2] += wk * vc[i];
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 0; o < LSEG_; o++) {
-#pragma unroll
-      for (int q = 0; q < 3; q++) hv[q][LSEG_ * seg + o][lane] = acc[o][q];
-    }
+    window_vertical<3, true>(win, hv, [&](int i, float(&m)[3]) { m[0] = v[0][i]; m[1] = v[1][i]; m[2] = v[2][i]; });
   }
   __syncthreads();
-  float t[3][LHO_];
-#pragma unroll
-  for (int q = 0; q < 3; q++) {
-    float v[LHO_ + LW_ - 1];
-#pragma unroll
-    for (int k = 0; k < LHO_ + LW_ - 1; k++) v[k] = hv[q][r][c0 + k];
-#pragma unroll
-    for (int o = 0; o < LHO_; o++) {
-      float a = 0.f;
-#pragma unroll
-      for (int k = 0; k < LW_; k++) a += win.w[LW_ - 1 - k] * v[o + k];
-      t[q][o] = a;
-    }
-  }
+  float t[3][WIN_HO];
+  window_horizontal<3, true>(win, hv, t);
   // the filtered maps change hands through LDS (as the forward's outputs do): the image is read and the gradient
   // written in the flattened order of the tile, 54-float row segments to consecutive lanes
   __syncthreads();  // (everyone has read hv)
 #pragma unroll
-  for (int o = 0; o < LHO_; o++) { hv[0][r][c0 + o] = t[0][o]; hv[1][r][c0 + o] = t[1][o]; hv[2][r][c0 + o] = t[2][o]; }
+  for (int o = 0; o < WIN_HO; o++) { hv[0][r][c0 + o] = t[0][o]; hv[1][r][c0 + o] = t[1][o]; hv[2][r][c0 + o] = t[2][o]; }
   __syncthreads();
 #pragma unroll
-  for (int it = 0; it < LFLAT_; it++) {
+  for (int it = 0; it < WIN_FLAT; it++) {
     const int e = it * 256 + (int)threadIdx.x;
-    const int row = e / LTX_, col = e - row * LTX_;
+    const int row = e / WIN_TX, col = e - row * WIN_TX;
     const int gx = x0 + col, gy = y0 + row;
-    if (e < LTX_ * LTY_ && gx < W && gy < H) {
+    if (e < WIN_TX * WIN_TY && gx < W && gy < H) {
       const float x = px[it], y = py[it];
       const float d = x - y;
       const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);  // torch: abs'(0) = 0
@@ -298,8 +179,7 @@ __global__ __launch_bounds__(256) void k_loss_backward(const int C, const int H,
 
 size_t loss_workspace_bytes(int C, int H, int W) {
   const size_t maps = 3 * align_up((size_t)C * H * W * sizeof(float));
-  const size_t nblocks = (size_t)((W + LTX_ - 1) / LTX_) * ((H + LTY_ - 1) / LTY_) * C;
-  return maps + align_up(nblocks * 2 * sizeof(float)) + ALIGN;
+  return maps + align_up(WindowGrid(C, H, W).units * 2 * sizeof(float)) + ALIGN;
 }
 
 hipError_t launch_photometric_loss(int C, int H, int W, const float* img, const float* gt, const float* window11,
@@ -309,11 +189,11 @@ hipError_t launch_photometric_loss(int C, int H, int W, const float* img, const 
   float* mapA = cv.take<float>(n);
   float* mapB = cv.take<float>(n);
   float* mapC = cv.take<float>(n);
-  const dim3 grid((W + LTX_ - 1) / LTX_, (H + LTY_ - 1) / LTY_, C);
-  const int nblocks = (int)(grid.x * grid.y * grid.z);
+  const WindowGrid wg(C, H, W);
+  const dim3 grid = wg.grid;
+  const int nblocks = (int)wg.units;
   float* partials = cv.take<float>((size_t)nblocks * 2);
-  LossWindow win;
-  for (int k = 0; k < LW_; k++) win.w[k] = window11[k];
+  const Window win(window11);
   const float inv_n = (float)(1.0 / (double)n);
   {
     ProfScope ps(K_LOSS_FWD, s);

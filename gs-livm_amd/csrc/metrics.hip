@@ -18,130 +18,63 @@
 #include <math.h>
 
 #include "gsr_internal.hpp"
+#include "gsr_window.hpp"
 
 namespace gsr {
 
-// The work unit of loss.hip (its LW_ .. LSTRIDE_, restated: that file and its code object stay as they are).
-constexpr int MW_ = 11;                    // window taps
-constexpr int MR_ = MW_ / 2;               // halo
-constexpr int MTX_ = 54, MTY_ = 32;        // outputs of one 256-thread workgroup
-constexpr int MSEG_ = 8;                   // output rows per wave
-constexpr int MIN_ = MSEG_ + 2 * MR_;      // 18 input rows per wave
-constexpr int MHO_ = 7;                    // horizontal pass: outputs per thread
-constexpr int MSTRIDE_ = 72;               // LDS row stride (conflict-free over a wave's 8 x 8, see loss.hip)
-constexpr float M_SSIM_C1 = 0.01f * 0.01f, M_SSIM_C2 = 0.03f * 0.03f;  // loss_utils.cuh:8-9
-constexpr int MPART_ = 3;                  // partials per workgroup: sum|x - y|, sum SSIM, sum (x - y)^2
+constexpr int MPART_ = 3;  // partials per workgroup: sum|x - y|, sum SSIM, sum (x - y)^2
 
-struct MetricsWindow { float w[MW_]; };
-
-// Same passes and the same order of operations as k_loss_forward (vertical pass in registers from coalesced loads, one
-// trip through LDS, horizontal pass seven outputs to a thread); nothing is stored per pixel.
+// k_loss_forward's passes and order of operations (the window unit of gsr_window.hpp: vertical pass in registers from
+// coalesced loads, one trip through LDS, horizontal pass seven outputs to a thread); nothing is stored per pixel.
 __global__ __launch_bounds__(256) void k_metrics_forward(const int C, const int H, const int W,
                                                          const float* __restrict__ img, const float* __restrict__ gt,
-                                                         const MetricsWindow win, float* __restrict__ partials) {
-  __shared__ float hv[4][MTY_][MSTRIDE_];  // vertically filtered moments
+                                                         const Window win, float* __restrict__ partials) {
+  __shared__ WindowLds hv[4];  // vertically filtered moments
   __shared__ float red[MPART_][4];
   const int c = blockIdx.z;
-  const int x0 = blockIdx.x * MTX_, y0 = blockIdx.y * MTY_;
+  const int x0 = blockIdx.x * WIN_TX, y0 = blockIdx.y * WIN_TY;
   const size_t plane = (size_t)c * H * W;
-  const float* X = img + plane;
-  const float* Y = gt + plane;
   const int lane = threadIdx.x & 63, seg = threadIdx.x >> 6;
-  float l1 = 0.f, ss = 0.f, sq = 0.f;
+  float sums[MPART_] = {0.f, 0.f, 0.f};
   {
-    const int gx = x0 - MR_ + lane;
-    const bool col_in = gx >= 0 && gx < W;
-    const int gxc = min(max(gx, 0), W - 1);
-    float vx[MIN_], vy[MIN_];
+    const float* const planes[2] = {img + plane, gt + plane};
+    float v[2][WIN_IN];
+    const bool col_in = window_load_columns(planes, H, W, x0, y0, v);
+    window_vertical<4, false>(win, hv, [&](int i, float(&m)[4]) {
+      const float x = v[0][i], y = v[1][i];
+      m[0] = x; m[1] = y; m[2] = __builtin_fmaf(y, y, x * x); m[3] = x * y;
+    });
+    if (lane >= WIN_HALO && lane < WIN_HALO + WIN_TX && col_in) {  // the L1 and squared-error terms of this thread's own eight pixels
 #pragma unroll
-    for (int i = 0; i < MIN_; i++) {  // (clamped addresses, unconditional loads, zero padding by select)
-      const int gy = y0 + MSEG_ * seg - MR_ + i;
-      const int off = min(max(gy, 0), H - 1) * W + gxc;
-      const float a = X[off], b = Y[off];
-      const bool in = col_in && gy >= 0 && gy < H;
-      vx[i] = in ? a : 0.f;
-      vy[i] = in ? b : 0.f;
-    }
-    float acc[MSEG_][4];
-#pragma unroll
-    for (int o = 0; o < MSEG_; o++) acc[o][0] = acc[o][1] = acc[o][2] = acc[o][3] = 0.f;
-#pragma unroll
-    for (int i = 0; i < MIN_; i++) {
-      const float x = vx[i], y = vy[i];
-      const float p2 = __builtin_fmaf(y, y, x * x), p3 = x * y;
-#pragma unroll
-      for (int o = 0; o < MSEG_; o++) {
-        const int k = i - o;
-        if (k >= 0 && k < MW_) {
-          const float wk = win.w[k];
-          acc[o][0] += wk * x; acc[o][1] += wk * y; acc[o][2] += wk * p2; acc[o][3] += wk * p3;
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 0; o < MSEG_; o++) {
-#pragma unroll
-      for (int q = 0; q < 4; q++) hv[q][MSEG_ * seg + o][lane] = acc[o][q];
-    }
-    if (lane >= MR_ && lane < MR_ + MTX_ && col_in) {  // the L1 and squared-error terms of this thread's own eight pixels
-#pragma unroll
-      for (int o = 0; o < MSEG_; o++)
-        if (y0 + MSEG_ * seg + o < H) {
-          const float d = vx[o + MR_] - vy[o + MR_];
-          l1 += fabsf(d);
-          sq = __builtin_fmaf(d, d, sq);
+      for (int o = 0; o < WIN_SEG; o++)
+        if (y0 + WIN_SEG * seg + o < H) {
+          const float d = v[0][o + WIN_HALO] - v[1][o + WIN_HALO];
+          sums[0] += fabsf(d);
+          sums[2] = __builtin_fmaf(d, d, sums[2]);
         }
     }
   }
   __syncthreads();
   {
-    const int r = threadIdx.x >> 3, c0 = (threadIdx.x & 7) * MHO_;
-    float m[4][MHO_];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      float v[MHO_ + MW_ - 1];
-#pragma unroll
-      for (int k = 0; k < MHO_ + MW_ - 1; k++) v[k] = hv[q][r][c0 + k];  // (the last group reads into the row padding)
-#pragma unroll
-      for (int o = 0; o < MHO_; o++) {
-        float a = 0.f;
-#pragma unroll
-        for (int k = 0; k < MW_; k++) a += win.w[k] * v[o + k];
-        m[q][o] = a;
-      }
-    }
+    const int r = threadIdx.x >> 3, c0 = (threadIdx.x & 7) * WIN_HO;
+    float m[4][WIN_HO];
+    window_horizontal<4, false>(win, hv, m);
     const int gy = y0 + r;
 #pragma unroll
-    for (int o = 0; o < MHO_; o++) {
+    for (int o = 0; o < WIN_HO; o++) {
       const int gx = x0 + c0 + o;
-      if (c0 + o < MTX_ && gx < W && gy < H) {
+      if (c0 + o < WIN_TX && gx < W && gy < H) {
         const float mu1 = m[0][o], mu2 = m[1][o], e_sum = m[2][o], e12 = m[3][o];
         const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
         const float s12 = e12 - mu12;
-        const float n1 = 2.f * mu12 + M_SSIM_C1, n2 = 2.f * s12 + M_SSIM_C2;
-        const float d1 = mu1_sq + mu2_sq + M_SSIM_C1, d2 = (e_sum - mu1_sq - mu2_sq) + M_SSIM_C2;
+        const float n1 = 2.f * mu12 + SSIM_C1, n2 = 2.f * s12 + SSIM_C2;
+        const float d1 = mu1_sq + mu2_sq + SSIM_C1, d2 = (e_sum - mu1_sq - mu2_sq) + SSIM_C2;
         const float r1 = __builtin_amdgcn_rcpf(d1), r2 = __builtin_amdgcn_rcpf(d2);  // (1 ulp, as in k_loss_forward)
-        ss += n1 * n2 * (r1 * r2);
+        sums[1] += n1 * n2 * (r1 * r2);
       }
     }
   }
-  // fixed-order workgroup reduction -> three partials per workgroup
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    l1 += __shfl_xor(l1, o, 64);
-    ss += __shfl_xor(ss, o, 64);
-    sq += __shfl_xor(sq, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    red[0][threadIdx.x >> 6] = l1; red[1][threadIdx.x >> 6] = ss; red[2][threadIdx.x >> 6] = sq;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {  // ordered by channel (blockIdx.z major), as the partials of k_loss_forward
-    const size_t b = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-#pragma unroll
-    for (int q = 0; q < MPART_; q++)
-      partials[MPART_ * b + q] = (red[q][0] + red[q][1]) + (red[q][2] + red[q][3]);
-  }
+  window_store_partials(sums, red, partials);  // three partials per workgroup, in the block order of k_loss_forward's
 }
 
 // One workgroup, fixed association order (thread-strided sums in f64, then a tree): deterministic.  The squared error
@@ -149,38 +82,27 @@ __global__ __launch_bounds__(256) void k_metrics_forward(const int C, const int 
 __global__ __launch_bounds__(1024) void k_metrics_finalize(const float* __restrict__ partials, const int nper, const int C,
                                                            const float inv_n, const double plane_px,
                                                            float* __restrict__ out4, double* __restrict__ totals) {
-  __shared__ double r1[1024], r2[1024], r3[1024];
-  double a = 0.0, b = 0.0;
+  __shared__ double r12[2][1024], r3[1][1024];
+  double ab[2] = {0.0, 0.0};
   for (size_t i = threadIdx.x; i < (size_t)nper * C; i += 1024) {  // (the order of k_loss_finalize)
-    a += partials[MPART_ * i]; b += partials[MPART_ * i + 1];
+    ab[0] += partials[MPART_ * i]; ab[1] += partials[MPART_ * i + 1];
   }
   double psnr_sum = 0.0, mse_sum = 0.0;  // (thread 0's)
   for (int c = 0; c < C; c++) {
     const float* p = partials + (size_t)c * nper * MPART_;
-    double q = 0.0;
-    for (int i = threadIdx.x; i < nper; i += 1024) q += p[MPART_ * i + 2];
-    r3[threadIdx.x] = q;
-    __syncthreads();
-    for (int o = 512; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) r3[threadIdx.x] += r3[threadIdx.x + o];
-      __syncthreads();
-    }
+    double q[1] = {0.0};
+    for (int i = threadIdx.x; i < nper; i += 1024) q[0] += p[MPART_ * i + 2];
+    tree_sum_1024(q, r3);
     if (threadIdx.x == 0) {  // loss_utils.cuh:89-93 in float64; mse_c == 0 -> 1 / 0 = +inf, as there
-      const double mse_c = r3[0] / plane_px;
+      const double mse_c = q[0] / plane_px;
       psnr_sum += 20.0 * log10(1.0 / sqrt(mse_c));
       mse_sum += mse_c;
     }
-    __syncthreads();  // (r3 is refilled by the next channel)
   }
-  r1[threadIdx.x] = a; r2[threadIdx.x] = b;
-  __syncthreads();
-  for (int o = 512; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { r1[threadIdx.x] += r1[threadIdx.x + o]; r2[threadIdx.x] += r2[threadIdx.x + o]; }
-    __syncthreads();
-  }
+  tree_sum_1024(ab, r12);
   if (threadIdx.x == 0) {
     const float psnr = (float)(psnr_sum / (double)C);
-    const float ssim = (float)(r2[0] * inv_n), l1 = (float)(r1[0] * inv_n);  // (as k_loss_finalize narrows them)
+    const float ssim = (float)(ab[1] * inv_n), l1 = (float)(ab[0] * inv_n);  // (as k_loss_finalize narrows them)
     const float mse = (float)(mse_sum / (double)C);
     out4[0] = psnr; out4[1] = ssim; out4[2] = l1; out4[3] = mse;
     if (totals) {  // the values as stored, widened: the running sums are the float64 sum of the per-frame outputs
@@ -271,19 +193,14 @@ __global__ __launch_bounds__(256) void k_pack_depth_u8(const int H, const int W,
   }
 }
 
-static size_t metrics_units(int C, int H, int W) {
-  return (size_t)((W + MTX_ - 1) / MTX_) * ((H + MTY_ - 1) / MTY_) * C;
-}
-
 // the partials only: three floats per work unit, element alignment
-size_t metrics_workspace_bytes(int C, int H, int W) { return metrics_units(C, H, W) * MPART_ * sizeof(float); }
+size_t metrics_workspace_bytes(int C, int H, int W) { return WindowGrid(C, H, W).units * MPART_ * sizeof(float); }
 
 hipError_t launch_image_metrics(int C, int H, int W, const float* img, const float* gt, const float* window11,
                                 float* out4, double* totals, char* workspace, hipStream_t s) {
   float* partials = reinterpret_cast<float*>(workspace);
-  const dim3 grid((W + MTX_ - 1) / MTX_, (H + MTY_ - 1) / MTY_, C);
-  MetricsWindow win;
-  for (int k = 0; k < MW_; k++) win.w[k] = window11[k];
+  const dim3 grid = WindowGrid(C, H, W).grid;
+  const Window win(window11);
   const float inv_n = (float)(1.0 / (double)((size_t)C * H * W));
   {
     ProfScope ps(K_METRICS_FWD, s);

@@ -19,12 +19,11 @@
 // The compaction is out of place on purpose: an in-place stable compaction races between workgroups (one writes the
 // rows another has yet to read).  Rows [P', ...) of a destination are not written.
 #include "gsr_internal.hpp"
+#include "gsr_workgroup.hpp"
 
 namespace gsr {
 
-constexpr int PRUNE_BLOCK = 256;      // rows per workgroup of k_prune_mark / k_prune_rank (4 waves)
-constexpr int PRUNE_WAVES = PRUNE_BLOCK / 64;
-constexpr int PRUNE_SCAN_ITEMS = 4;   // consecutive workgroup totals per thread of k_prune_scan: 1024 per pass of its loop
+constexpr int PRUNE_BLOCK = WG_THREADS;  // rows per workgroup of k_prune_mark / k_prune_rank (4 waves)
 constexpr int COMPACT_ITEMS = 4;      // floats per thread of k_prune_compact, 256 apart: 1024 consecutive floats per workgroup
 constexpr int COMPACT_TILE = 256 * COMPACT_ITEMS;
 
@@ -34,8 +33,6 @@ constexpr unsigned R_OPACITY = 1u, R_SCALE = 2u, R_NONFINITE = 4u, R_MASK = 8u;
 inline size_t prune_blocks(int P) { return ((size_t)P + PRUNE_BLOCK - 1) / PRUNE_BLOCK; }
 // [5][nblocks] int32: [0] kept rows per workgroup -> their exclusive scan; [1..4] rows per workgroup with reason bit 0..3
 size_t prune_workspace_bytes(int P) { return P > 0 ? 5 * prune_blocks(P) * sizeof(int) : 0; }
-
-__device__ __forceinline__ bool nonfinite_(float x) { return (__float_as_uint(x) & 0x7F800000u) == 0x7F800000u; }
 
 // The activated values are those of k_activate / k_model_step bit for bit (same expf, same sigmoidf_), so "dropped for
 // scale" is exactly "k_preprocess' scale cull fires at scale_modifier 1", and the comparisons are the rasterizer's:
@@ -48,7 +45,7 @@ __global__ __launch_bounds__(PRUNE_BLOCK) void k_prune_mark(const int P, const f
                                                             const float min_opacity, const float max_scale,
                                                             const int drop_nonfinite, unsigned char* __restrict__ reasons,
                                                             int* __restrict__ totals, const int nblocks) {
-  __shared__ int sh[PRUNE_WAVES][5];
+  __shared__ int sh[WG_WAVES][5];
   const int i = blockIdx.x * PRUNE_BLOCK + threadIdx.x;
   const bool in = i < P;
   unsigned r = 0;
@@ -69,76 +66,19 @@ __global__ __launch_bounds__(PRUNE_BLOCK) void k_prune_mark(const int P, const f
     if (drop && drop[i]) r |= R_MASK;
     reasons[i] = (unsigned char)r;
   }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int n_keep = __popcll(__ballot(in && r == 0));
-  int n_r[4];
+  int n[5];  // kept, then the four reasons
+  n[0] = __popcll(__ballot(in && r == 0));
 #pragma unroll
-  for (int k = 0; k < 4; k++) n_r[k] = __popcll(__ballot((r >> k) & 1u));
-  if (lane == 0) {
-    sh[wave][0] = n_keep;
-#pragma unroll
-    for (int k = 0; k < 4; k++) sh[wave][1 + k] = n_r[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    int t = 0;
-#pragma unroll
-    for (int w = 0; w < PRUNE_WAVES; w++) t += sh[w][threadIdx.x];
-    totals[(size_t)threadIdx.x * nblocks + blockIdx.x] = t;
-  }
+  for (int k = 0; k < 4; k++) n[1 + k] = __popcll(__ballot((r >> k) & 1u));
+  store_block_totals(n, sh, totals, nblocks);
 }
 
-// sum over the workgroup (256 threads) of v, returned to every thread; `sh`: PRUNE_WAVES ints
-__device__ __forceinline__ int block_sum(int v, int* sh) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  __syncthreads();  // (sh may still be read from the previous use)
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int t = 0;
-#pragma unroll
-  for (int w = 0; w < PRUNE_WAVES; w++) t += sh[w];
-  return t;
-}
-
-// ONE workgroup.  totals[0][.] -> exclusive scan in place, 1024 workgroup totals per pass of the loop with the running
-// sum carried in a register; then the four reason totals, counts5 and row_map[P].  nblocks == 0 (P == 0) writes zeros.
+// ONE workgroup.  totals[0][.] -> exclusive scan in place (scan_totals); then the four reason totals, counts5 and
+// row_map[P].  nblocks == 0 (P == 0) writes zeros.
 __global__ __launch_bounds__(PRUNE_BLOCK) void k_prune_scan(int* __restrict__ totals, const int nblocks,
                                                             int* __restrict__ counts5, int* __restrict__ row_map_end) {
-  __shared__ int sh[PRUNE_WAVES];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  int carry = 0;
-  for (int base = 0; base < nblocks; base += PRUNE_BLOCK * PRUNE_SCAN_ITEMS) {  // (uniform trip count)
-    const int j0 = base + (int)threadIdx.x * PRUNE_SCAN_ITEMS;
-    int v[PRUNE_SCAN_ITEMS], mine = 0;
-#pragma unroll
-    for (int k = 0; k < PRUNE_SCAN_ITEMS; k++) {
-      v[k] = j0 + k < nblocks ? totals[j0 + k] : 0;
-      mine += v[k];
-    }
-    int incl = mine;  // inclusive scan of the threads' sums inside the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int up = __shfl_up(incl, d);
-      if (lane >= d) incl += up;
-    }
-    __syncthreads();  // the previous pass has read sh
-    if (lane == 63) sh[wave] = incl;
-    __syncthreads();
-    int before = carry, all = 0;
-#pragma unroll
-    for (int w = 0; w < PRUNE_WAVES; w++) {
-      if (w < wave) before += sh[w];
-      all += sh[w];
-    }
-    int run = before + incl - mine;
-#pragma unroll
-    for (int k = 0; k < PRUNE_SCAN_ITEMS; k++) {
-      if (j0 + k < nblocks) totals[j0 + k] = run;
-      run += v[k];
-    }
-    carry += all;
-  }
+  __shared__ int sh[WG_WAVES];
+  const int carry = scan_totals(totals, nblocks, sh);
   int n_r[4];
 #pragma unroll
   for (int k = 0; k < 4; k++) {
@@ -156,19 +96,10 @@ __global__ __launch_bounds__(PRUNE_BLOCK) void k_prune_scan(int* __restrict__ to
 
 __global__ __launch_bounds__(PRUNE_BLOCK) void k_prune_rank(const int P, const unsigned char* __restrict__ reasons,
                                                             const int* __restrict__ bases, int* __restrict__ row_map) {
-  __shared__ int sh[PRUNE_WAVES];
+  __shared__ int sh[WG_WAVES];
   const int i = blockIdx.x * PRUNE_BLOCK + threadIdx.x;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool keep = i < P && reasons[i] == 0;
-  const unsigned long long b = __ballot(keep);
-  const int rank = __popcll(b & ((1ull << lane) - 1ull));
-  if (lane == 0) sh[wave] = __popcll(b);
-  __syncthreads();
-  int before = bases[blockIdx.x];
-#pragma unroll
-  for (int w = 0; w < PRUNE_WAVES; w++)
-    if (w < wave) before += sh[w];
-  if (i < P) row_map[i] = before + rank;
+  const int rank = rank_in_block(i < P && reasons[i] == 0, sh);
+  if (i < P) row_map[i] = bases[blockIdx.x] + rank;
 }
 
 struct CompactArgs {

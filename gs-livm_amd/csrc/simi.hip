@@ -23,6 +23,7 @@
 // at exactly d == r contributes nothing (the reference leaves both undefined).  m and n are bounded by int only: the
 // 500-point cap of the reference (MAX_SIMI, include/gs/gp3d/gp_types.h:15) is the host's policy.
 #include "gsr_internal.hpp"
+#include "gsr_workgroup.hpp"
 
 namespace gsr {
 
@@ -78,17 +79,6 @@ struct SimiWorkspace {
     return w;
   }
 };
-
-// Sum of one double per thread over a 256-thread workgroup, in a fixed order: xor-butterfly inside each wave, then the
-// four wave sums left to right.  Every thread receives the result.  `sh` holds 4 doubles; two barriers.
-__device__ __forceinline__ double block_sum_f64(double v, double* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();  // (sh may still be read from an earlier call)
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
 
 // A row index of `sel` as the kernels use it for READS: clamped into [0, P), so that a selection that breaks its
 // contract (each < P) reads a wrong row instead of foreign memory; writes test the unclamped index and are skipped.
@@ -154,7 +144,7 @@ __global__ __launch_bounds__(256) void k_simi_nearest(const int P, const int m, 
     part_k[o] = bk;
   }
   if (sums) {
-    const double s = block_sum_f64(ssum, shsum);
+    const double s = block_sum(ssum, shsum);
     if (threadIdx.x == 0) scale_part[blockIdx.y] = s;
   }
 }
@@ -170,9 +160,7 @@ __global__ __launch_bounds__(256) void k_simi_points(const int P, const int m, c
   __shared__ double shsum[4];
   __shared__ int shcnt[4];
   // r: every workgroup sums the chunk sums in the same fixed order (thread-strided, then the workgroup tree)
-  double s = 0.0;
-  for (int c = threadIdx.x; c < nchunks; c += 256) s += scale_part[c];
-  s = block_sum_f64(s, shsum);
+  const double s = partials_sum(scale_part, nchunks, shsum);
   const float r = (float)(s / (3.0 * (double)n));
   const int i = blockIdx.x * 256 + (int)threadIdx.x;
   float hinge = 0.f;
@@ -206,14 +194,11 @@ __global__ __launch_bounds__(256) void k_simi_points(const int P, const int m, c
     rec_k[i] = rk;
     rec_g[3 * (size_t)i] = gx; rec_g[3 * (size_t)i + 1] = gy; rec_g[3 * (size_t)i + 2] = gz;
   }
-  const double hs = block_sum_f64((double)hinge, shsum);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) active += __shfl_xor(active, o, 64);
-  if ((threadIdx.x & 63) == 0) shcnt[threadIdx.x >> 6] = active;
-  __syncthreads();
+  double hs = (double)hinge;
+  block_sum_pair(hs, active, shsum, shcnt);
   if (threadIdx.x == 0) {
     hinge_part[blockIdx.x] = hs;
-    count_part[blockIdx.x] = (shcnt[0] + shcnt[1]) + (shcnt[2] + shcnt[3]);
+    count_part[blockIdx.x] = active;
     if (blockIdx.x == 0) *r_out = r;
   }
 }
@@ -229,14 +214,9 @@ __global__ __launch_bounds__(256) void k_simi_grads(const int P, const int m, co
   __shared__ __attribute__((aligned(16))) int sk[SM_REC_TILE_];
   __shared__ double shsum[4];
   // number of points outside r (integers: exact in any order) and, for workgroup 0, the loss
-  double cnt = 0.0, hs = 0.0;
-  for (int b = threadIdx.x; b < nblocks2; b += 256) {
-    cnt += (double)count_part[b];
-    if (blockIdx.x == 0) hs += hinge_part[b];
-  }
-  cnt = block_sum_f64(cnt, shsum);
+  double hs, cnt;
+  partial_pairs_sum(hinge_part, count_part, nblocks2, shsum, hs, cnt);
   if (blockIdx.x == 0) {
-    hs = block_sum_f64(hs, shsum);
     if (threadIdx.x == 0) {
       const float mean_min = (float)(hs / (double)m);
       out3[0] = lambda * mean_min;

@@ -47,6 +47,24 @@ int coefficients(const torch::Tensor& features_rest) {  // M = SH coefficients p
   return 1 + (features_rest.defined() && features_rest.numel() ? static_cast<int>(features_rest.size(1)) : 0);
 }
 
+// a byte workspace on the device of `like`; never empty, so that an entry point that needs no bytes gets a pointer too
+torch::Tensor workspace(size_t nbytes, const torch::Tensor& like) {
+  return torch::empty({static_cast<long long>(nbytes ? nbytes : 1)}, like.options().dtype(torch::kByte));
+}
+
+// the first three rows of a 2-d matrix (3x3, 3x4 or 4x4; any device, any float type) as float32 on the host
+torch::Tensor host_rows3(const torch::Tensor& t, const char* name) {
+  if (!t.defined() || t.dim() != 2 || t.size(0) < 3)
+    throw std::invalid_argument(std::string(name) + ": a 2-d matrix of at least three rows");
+  return t.to(torch::kCPU, torch::kFloat64).slice(0, 0, 3).to(torch::kFloat32).contiguous();
+}
+
+// a loss node's backward: the gradient saved by its forward times the upstream scalar, or undefined where the forward
+// saved none (an empty tensor stands for "none")
+torch::Tensor scaled(const torch::Tensor& saved, const torch::Tensor& upstream) {
+  return saved.numel() ? saved * upstream : torch::Tensor();
+}
+
 void window_taps(const torch::Tensor& window1d, float out[11]) {
   const torch::Tensor w = (window1d.defined() ? window1d : reference_window_1d()).to(torch::kCPU, torch::kFloat32).contiguous();
   if (w.numel() != 11) throw std::invalid_argument("photometric_loss: the window has 11 taps");
@@ -62,7 +80,7 @@ std::pair<torch::Tensor, torch::Tensor> run_loss(const torch::Tensor& image, con
   float taps[11];
   window_taps(window1d, taps);
   const size_t nbytes = gsr_photometric_loss_workspace(C, H, W);
-  torch::Tensor ws = torch::empty({static_cast<long long>(nbytes)}, img.options().dtype(torch::kByte));
+  torch::Tensor ws = workspace(nbytes, img);
   torch::Tensor out3 = torch::empty({3}, img.options());
   torch::Tensor grad = want_grad ? torch::empty_like(img) : torch::Tensor();
   check(gsr_photometric_loss(C, H, W, fp(img), fp(ref), taps, lambda, out3.data_ptr<float>(), fp(grad),
@@ -81,7 +99,7 @@ struct PhotometricLossFn : public torch::autograd::Function<PhotometricLossFn> {
   static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx,
                                                torch::autograd::tensor_list grad_outputs) {
     const torch::Tensor grad = ctx->get_saved_variables()[0];
-    return {grad.numel() ? grad * grad_outputs[0] : torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor()};
+    return {scaled(grad, grad_outputs[0]), torch::Tensor(), torch::Tensor(), torch::Tensor()};
   }
 };
 
@@ -98,7 +116,7 @@ struct SimilarityLossFn : public torch::autograd::Function<SimilarityLossFn> {
     torch::Tensor gx = xyz.requires_grad() ? torch::zeros_like(x) : torch::Tensor();
     torch::Tensor gs = scaling.requires_grad() ? torch::zeros_like(s) : torch::Tensor();
     const size_t nbytes = gsr_similarity_loss_workspace(m, n);
-    torch::Tensor ws = torch::empty({static_cast<long long>(nbytes ? nbytes : 1)}, x.options().dtype(torch::kByte));
+    torch::Tensor ws = workspace(nbytes, x);
     torch::Tensor out3 = torch::empty({3}, x.options());
     check(gsr_similarity_loss(P, m, n, fp(p), n ? rows.data_ptr<int>() : nullptr, fp(x), fp(s),
                               static_cast<float>(lambda), out3.data_ptr<float>(), fp(gx), fp(gs), 0,
@@ -112,8 +130,7 @@ struct SimilarityLossFn : public torch::autograd::Function<SimilarityLossFn> {
                                                torch::autograd::tensor_list grad_outputs) {
     const auto saved = ctx->get_saved_variables();
     const torch::Tensor gx = saved[0], gs = saved[1], g = grad_outputs[0];
-    return {torch::Tensor(), torch::Tensor(), gx.numel() ? gx * g : torch::Tensor(),
-            gs.numel() ? gs * g : torch::Tensor(), torch::Tensor()};
+    return {torch::Tensor(), torch::Tensor(), scaled(gx, g), scaled(gs, g), torch::Tensor()};
   }
 };
 
@@ -127,18 +144,14 @@ struct DeltaDepthLossFn : public torch::autograd::Function<DeltaDepthLossFn> {
     const int64_t H = ds.size(-2), W = ds.size(-1);
     if (ds.numel() != H * W || as.numel() != H * W || dr.numel() != H * W || ar.numel() != H * W)
       throw std::invalid_argument("delta_depth_loss: four images of one shape [H,W] or [1,H,W]");
-    auto host = [](const torch::Tensor& t, int64_t rows, const char* name) {
-      if (!t.defined() || t.dim() != 2 || t.size(0) < rows)
-        throw std::invalid_argument(std::string(name) + ": a 2-d matrix of at least three rows");
-      return t.to(torch::kCPU, torch::kFloat64).slice(0, 0, rows).to(torch::kFloat32).contiguous();
-    };
-    const torch::Tensor ki = host(inv_K_src, 3, "inv_K_src"), kr = host(K_ref, 3, "K_ref"), tr = host(T_rel, 3, "T_rel");
+    const torch::Tensor ki = host_rows3(inv_K_src, "inv_K_src"), kr = host_rows3(K_ref, "K_ref"),
+                        tr = host_rows3(T_rel, "T_rel");
     if (ki.numel() != 9 || kr.numel() != 9 || tr.numel() != 12)
       throw std::invalid_argument("delta_depth_loss: inv_K_src and K_ref are 3x3, T_rel is 3x4 or 4x4");
     torch::Tensor gs = depth_src.requires_grad() ? torch::empty_like(ds) : torch::Tensor();
     torch::Tensor gr = depth_ref.requires_grad() ? torch::empty_like(dr) : torch::Tensor();
     const size_t nbytes = gsr_delta_depth_loss_workspace(static_cast<int>(H), static_cast<int>(W));
-    torch::Tensor ws = torch::empty({static_cast<long long>(nbytes ? nbytes : 1)}, ds.options().dtype(torch::kByte));
+    torch::Tensor ws = workspace(nbytes, ds);
     torch::Tensor out3 = torch::empty({3}, ds.options());
     check(gsr_delta_depth_loss(static_cast<int>(H), static_cast<int>(W), fp(ds), fp(as), fp(dr), fp(ar),
                                ki.data_ptr<float>(), kr.data_ptr<float>(), tr.data_ptr<float>(),
@@ -153,8 +166,8 @@ struct DeltaDepthLossFn : public torch::autograd::Function<DeltaDepthLossFn> {
                                                torch::autograd::tensor_list grad_outputs) {
     const auto saved = ctx->get_saved_variables();
     const torch::Tensor gs = saved[0], gr = saved[1], g = grad_outputs[0];
-    return {gs.numel() ? gs * g : torch::Tensor(), torch::Tensor(), gr.numel() ? gr * g : torch::Tensor(),
-            torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor()};
+    return {scaled(gs, g), torch::Tensor(), scaled(gr, g), torch::Tensor(), torch::Tensor(), torch::Tensor(),
+            torch::Tensor(), torch::Tensor()};
   }
 };
 
@@ -169,7 +182,7 @@ struct LidarDepthLossFn : public torch::autograd::Function<LidarDepthLossFn> {
     torch::Tensor gd = depth.requires_grad() ? torch::empty_like(d) : torch::Tensor();
     torch::Tensor ga = acc.requires_grad() ? torch::empty_like(d) : torch::Tensor();
     const size_t nbytes = gsr_lidar_depth_loss_workspace(static_cast<int>(H), static_cast<int>(W));
-    torch::Tensor ws = torch::empty({static_cast<long long>(nbytes ? nbytes : 1)}, d.options().dtype(torch::kByte));
+    torch::Tensor ws = workspace(nbytes, d);
     torch::Tensor out3 = torch::empty({3}, d.options());
     check(gsr_lidar_depth_loss(static_cast<int>(H), static_cast<int>(W), fp(d), fp(a), fp(zl),
                                static_cast<float>(acc_min), static_cast<float>(lambda), out3.data_ptr<float>(), fp(gd),
@@ -183,8 +196,7 @@ struct LidarDepthLossFn : public torch::autograd::Function<LidarDepthLossFn> {
                                                torch::autograd::tensor_list grad_outputs) {
     const auto saved = ctx->get_saved_variables();
     const torch::Tensor gd = saved[0], ga = saved[1], g = grad_outputs[0];
-    return {gd.numel() ? gd * g : torch::Tensor(), ga.numel() ? ga * g : torch::Tensor(), torch::Tensor(),
-            torch::Tensor(), torch::Tensor()};
+    return {scaled(gd, g), scaled(ga, g), torch::Tensor(), torch::Tensor(), torch::Tensor()};
   }
 };
 
@@ -265,12 +277,7 @@ torch::Tensor lidar_depth_image(const torch::Tensor& points_world, const torch::
   torch::NoGradGuard no_grad;
   const torch::Tensor p = dev_f32(points_world, "points_world");
   if (p.dim() != 2 || p.size(1) != 3) throw std::invalid_argument("lidar_depth_image: points_world is [n,3]");
-  auto host = [](const torch::Tensor& t, const char* name) {
-    if (!t.defined() || t.dim() != 2 || t.size(0) < 3)
-      throw std::invalid_argument(std::string(name) + ": a 2-d matrix of at least three rows");
-    return t.to(torch::kCPU, torch::kFloat64).slice(0, 0, 3).to(torch::kFloat32).contiguous();
-  };
-  const torch::Tensor tcw = host(T_cw, "T_cw"), k = host(K, "K");
+  const torch::Tensor tcw = host_rows3(T_cw, "T_cw"), k = host_rows3(K, "K");
   if (tcw.numel() != 12 || k.numel() != 9) throw std::invalid_argument("lidar_depth_image: T_cw is 3x4 or 4x4, K is 3x3");
   torch::Tensor image = torch::empty({std::max<int64_t>(height, 0), std::max<int64_t>(width, 0)}, p.options());
   torch::Tensor c2 = counts ? torch::empty({2}, p.options().dtype(torch::kInt32)) : torch::Tensor();
@@ -299,7 +306,7 @@ torch::Tensor image_metrics(const torch::Tensor& image, const torch::Tensor& gt,
   float taps[11];
   window_taps(window1d, taps);
   const size_t nbytes = gsr_image_metrics_workspace(C, H, W);
-  torch::Tensor ws = torch::empty({static_cast<long long>(nbytes ? nbytes : 1)}, img.options().dtype(torch::kByte));
+  torch::Tensor ws = workspace(nbytes, img);
   torch::Tensor out4 = torch::empty({4}, img.options());
   check(gsr_image_metrics(C, H, W, fp(img), fp(ref), taps, out4.data_ptr<float>(),
                           totals.defined() ? totals.data_ptr<double>() : nullptr,
@@ -524,7 +531,7 @@ PruneMarks prune_mark(const torch::Tensor& xyz, const torch::Tensor& scaling_raw
   const auto bytes = x.options().dtype(torch::kByte), ints = x.options().dtype(torch::kInt32);
   PruneMarks out{torch::empty({P}, bytes), torch::empty({P + 1}, ints), torch::empty({5}, ints)};
   const size_t nbytes = gsr_prune_workspace(static_cast<int>(P));
-  torch::Tensor ws = torch::empty({static_cast<long long>(nbytes ? nbytes : 1)}, bytes);
+  torch::Tensor ws = workspace(nbytes, x);
   check(gsr_prune_mark(static_cast<int>(P), fp(x), fp(s), fp(r), fp(o),
                        mask.defined() && P ? static_cast<const unsigned char*>(mask.data_ptr()) : nullptr, min_opacity,
                        max_scale, drop_nonfinite ? 1 : 0, P ? out.reasons.data_ptr<unsigned char>() : nullptr,
@@ -557,7 +564,7 @@ DensifyMarks densify_mark(const torch::Tensor& stats, const torch::Tensor& scali
   const auto bytes = st.options().dtype(torch::kByte), ints = st.options().dtype(torch::kInt32);
   DensifyMarks out{torch::empty({P}, bytes), torch::empty({P + 1}, ints), torch::empty({3}, ints)};
   const size_t nbytes = gsr_densify_workspace(static_cast<int>(P));
-  torch::Tensor ws = torch::empty({static_cast<long long>(nbytes ? nbytes : 1)}, bytes);
+  torch::Tensor ws = workspace(nbytes, st);
   check(gsr_densify_mark(static_cast<int>(P), fp(st), fp(s), grad_threshold, size_threshold,
                          max_new < 0 ? -1 : static_cast<int>(std::min<int64_t>(max_new, 0x7fffffff)),
                          P ? out.kinds.data_ptr<unsigned char>() : nullptr, out.offsets.data_ptr<int>(),
@@ -738,7 +745,7 @@ torch::Tensor pose_gradient(const torch::Tensor& means3D, const torch::Tensor& r
   if (given(rot) && (reinterpret_cast<uintptr_t>(rot.data_ptr()) & 15u) != 0) rot = rot.clone();  // read as float4
   if (given(rad) && rad.scalar_type() != torch::kInt32) throw std::invalid_argument("pose_gradient: radii is int32");
   const size_t nbytes = gsr_pose_gradient_workspace(static_cast<int>(P));
-  torch::Tensor ws = torch::empty({static_cast<long long>(nbytes)}, m3.options().dtype(torch::kByte));
+  torch::Tensor ws = workspace(nbytes, m3);
   torch::Tensor out = torch::empty({6}, m3.options());
   check(gsr_pose_gradient(static_cast<int>(P), image_width, image_height, fp(m3), fp(sc), scale_modifier, fp(rot), fp(cov),
                           fp(view), fp(proj), tan_fovx, tan_fovy, given(rad) ? rad.data_ptr<int>() : nullptr, fp(g2),
