@@ -71,7 +71,8 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_image_metrics_workspace", "gsr_pack_image_u8", "gsr_pack_depth_u8", "gsr_prune_workspace",
            "gsr_prune_mark", "gsr_prune_compact", "gsr_lidar_depth_image", "gsr_lidar_depth_loss",
            "gsr_lidar_depth_loss_workspace", "gsr_density_accumulate", "gsr_densify_workspace", "gsr_densify_mark",
-           "gsr_densify_apply", "gsr_pose_gradient", "gsr_pose_gradient_workspace")
+           "gsr_densify_apply", "gsr_pose_gradient", "gsr_pose_gradient_workspace", "gsr_exposure_loss",
+           "gsr_exposure_loss_workspace", "gsr_apply_exposure")
 
 
 def lib():
@@ -171,6 +172,12 @@ def lib():
     L.gsr_photometric_loss_workspace.argtypes = [ci, ci, ci]
     L.gsr_photometric_loss.restype = ci
     L.gsr_photometric_loss.argtypes = [ci, ci, ci, vp, vp, C.POINTER(cf), cf, vp, vp, vp, sz, vp]
+    L.gsr_exposure_loss_workspace.restype = sz
+    L.gsr_exposure_loss_workspace.argtypes = [ci, ci, ci]
+    L.gsr_exposure_loss.restype = ci
+    L.gsr_exposure_loss.argtypes = [ci, ci, ci, vp, vp, vp, C.POINTER(cf), cf, vp, vp, vp, vp, sz, vp]
+    L.gsr_apply_exposure.restype = ci
+    L.gsr_apply_exposure.argtypes = [ci, ci, ci, vp, vp, vp, vp]
     L.gsr_similarity_loss_workspace.restype = sz
     L.gsr_similarity_loss_workspace.argtypes = [ci, ci]
     L.gsr_similarity_loss.restype = ci
@@ -624,6 +631,38 @@ def photometric_loss(img, gt, window11, lambda_dssim, want_grad=True):
     _check(lib().gsr_photometric_loss(Cn, H, W, _ptr(img), _ptr(gt), win, float(lambda_dssim), _ptr(out3), _ptr(grad),
                                       _ptr(ws), nbytes, _stream()))
     return out3, grad
+
+
+def exposure_loss(img, gt, exposure, window11, lambda_dssim, want_grad=True):
+    """The photometric loss on x' = fma(g_c, img, b_c) in three launches (include/gsraster.h, gsr_exposure_loss).
+    exposure: [C,2] f32 on the device.  Returns (out3 = [loss, l1, ssim] device tensor, dL_dimg or None,
+    dL_dexposure [C,2] or None)."""
+    assert img.dim() == 3 and img.shape == gt.shape and img.is_cuda
+    Cn, H, W = (int(x) for x in img.shape)
+    assert exposure.is_cuda and exposure.dtype == torch.float32 and tuple(exposure.shape) == (Cn, 2)
+    img, gt, exposure = img.contiguous(), gt.contiguous(), exposure.contiguous()
+    nbytes = int(lib().gsr_exposure_loss_workspace(Cn, H, W))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=img.device)
+    out3 = torch.empty(3, dtype=torch.float32, device=img.device)
+    grad = torch.empty_like(img) if want_grad else None
+    grad_e = torch.empty_like(exposure) if want_grad else None
+    win = (C.c_float * 11)(*[float(x) for x in window11])
+    _check(lib().gsr_exposure_loss(Cn, H, W, _ptr(img), _ptr(gt), _ptr(exposure), win, float(lambda_dssim), _ptr(out3),
+                                   _ptr(grad), _ptr(grad_e), _ptr(ws), nbytes, _stream()))
+    return out3, grad, grad_e
+
+
+def apply_exposure(img, exposure, out=None):
+    """out = fma(g_c, img, b_c) in one launch (include/gsraster.h, gsr_apply_exposure).  img: [C,H,W] f32 on the device,
+    contiguous; exposure: [C,2]; out: a contiguous tensor of img's shape (img itself is allowed) or None = a new one."""
+    assert img.dim() == 3 and img.is_cuda and img.dtype == torch.float32 and img.is_contiguous()
+    Cn, H, W = (int(x) for x in img.shape)
+    assert exposure.is_cuda and exposure.dtype == torch.float32 and tuple(exposure.shape) == (Cn, 2)
+    if out is None:
+        out = torch.empty_like(img)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.shape == img.shape
+    _check(lib().gsr_apply_exposure(Cn, H, W, _ptr(img), _ptr(exposure.contiguous()), _ptr(out), _stream()))
+    return out
 
 
 def similarity_loss(points, sel, xyz, scaling, lambda_, grad_xyz=None, grad_scaling=None, accumulate=False):

@@ -31,6 +31,7 @@ UNITS = {
     "render.hip": ["-ffp-contract=fast", "-fno-slp-vectorize"],
     "optimizer.hip": [],
     "loss.hip": ["-fno-slp-vectorize"],  # (packing the 11-tap sums costs more moves than it saves: 944 -> 732 VALU in the backward)
+    "exposure.hip": ["-fno-slp-vectorize"],  # (the loss kernels' arithmetic on the compensated image: built like loss.hip)
     "growth.hip": [],
     "simi.hip": [],
     "delta.hip": [],

@@ -154,6 +154,7 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_lidar_loss_grads",
     "k_density_accumulate", "k_densify_mark", "k_densify_scan", "k_densify_rank", "k_densify_apply",
     "k_pose_partials", "k_pose_finish",
+    "k_exposure_loss_forward", "k_exposure_loss_backward", "k_exposure_loss_finish", "k_apply_exposure",
     "k_metrics_forward", "k_metrics_finalize", "k_pack_image_u8", "k_pack_depth_u8",
     "k_prune_mark", "k_prune_scan", "k_prune_rank", "k_prune_compact"};
 
@@ -1626,6 +1627,42 @@ int gsr_photometric_loss(int channels, int height, int width, const float* img, 
   if (int e = check_workspace(workspace_bytes, loss_workspace_bytes(channels, height, width))) return e;
   HIP_TRY(launch_photometric_loss(channels, height, width, img, gt, window11_host, lambda_dssim, loss_out3, dL_dimg,
                                   workspace, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+size_t gsr_exposure_loss_workspace(int channels, int height, int width) {
+  if (channels <= 0 || height <= 0 || width <= 0 ||
+      (unsigned long long)height * (unsigned long long)width >= 0x7fffffffull)
+    return 0;
+  return exposure_loss_workspace_bytes(channels, height, width);
+}
+
+int gsr_exposure_loss(int channels, int height, int width, const float* img, const float* gt, const float* exposure,
+                      const float* window11_host, float lambda_dssim, float* loss_out3, float* dL_dimg,
+                      float* dL_dexposure, char* workspace, size_t workspace_bytes, void* stream_) {
+  g_err[0] = 0;
+  if (channels <= 0 || height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if (int e = check_plane(height, width, 0x7fffffffull)) return e;  // (32-bit offsets inside a plane)
+  if (!img || !gt || !exposure || !window11_host || !loss_out3 || !workspace)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (!dL_dimg != !dL_dexposure)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "dL_dimg and dL_dexposure: both or neither");
+  if (int e = check_workspace(workspace_bytes, exposure_loss_workspace_bytes(channels, height, width))) return e;
+  HIP_TRY(launch_exposure_loss(channels, height, width, img, gt, exposure, window11_host, lambda_dssim, loss_out3,
+                               dL_dimg, dL_dexposure, workspace, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+int gsr_apply_exposure(int channels, int height, int width, const float* img, const float* exposure, float* out,
+                       void* stream_) {
+  g_err[0] = 0;
+  if (channels <= 0 || height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if (int e = check_plane(height, width, 0x7fffffffull)) return e;
+  if (!img || !exposure || !out) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (int e = check_aligned4(reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(exposure) |
+                             reinterpret_cast<uintptr_t>(out)))
+    return e;
+  HIP_TRY(launch_apply_exposure(channels, height, width, img, exposure, out, (hipStream_t)stream_));
   return GSR_OK;
 }
 

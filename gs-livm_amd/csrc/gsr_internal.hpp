@@ -442,6 +442,14 @@ hipError_t launch_activate_backward(int P, int M, const float* rotation_raw, con
 size_t loss_workspace_bytes(int C, int H, int W);
 hipError_t launch_photometric_loss(int C, int H, int W, const float* img, const float* gt, const float* window11,
                                    float lambda, float* loss_out3, float* dL_dimg, char* workspace, hipStream_t s);
+// exposure.hip (per-keyframe exposure compensation x' = fma(g_c, x, b_c) fused into the photometric loss, with the
+// gradients towards the image and the [C][2] exposure; the workspace may sit at any float-aligned address)
+size_t exposure_loss_workspace_bytes(int C, int H, int W);
+hipError_t launch_exposure_loss(int C, int H, int W, const float* img, const float* gt, const float* exposure,
+                                const float* window11, float lambda, float* loss_out3, float* dL_dimg,
+                                float* dL_dexposure, char* workspace, hipStream_t s);
+hipError_t launch_apply_exposure(int C, int H, int W, const float* img, const float* exposure, float* out,
+                                 hipStream_t s);
 // simi.hip (the LiDAR similarity loss: nearest selected Gaussian per point, one clamp, deterministic gradients)
 size_t simi_workspace_bytes(int m, int n);
 hipError_t launch_similarity_loss(int P, int m, int n, const float* points, const int* sel, const float* xyz,
@@ -520,6 +528,7 @@ enum KernelId {
   K_LIDAR_CLEAR, K_LIDAR_SPLAT, K_LIDAR_CONVERT, K_LIDAR_LOSS_FWD, K_LIDAR_LOSS_FINISH, K_LIDAR_LOSS_GRADS,
   K_DENSITY_ACCUMULATE, K_DENSIFY_MARK, K_DENSIFY_SCAN, K_DENSIFY_RANK, K_DENSIFY_APPLY,
   K_POSE_PARTIALS, K_POSE_FINISH,
+  K_EXPOSURE_LOSS_FWD, K_EXPOSURE_LOSS_BWD, K_EXPOSURE_LOSS_FINISH, K_APPLY_EXPOSURE,
   K_METRICS_FWD, K_METRICS_FINALIZE, K_PACK_IMAGE_U8, K_PACK_DEPTH_U8,
   K_PRUNE_MARK, K_PRUNE_SCAN, K_PRUNE_RANK, K_PRUNE_COMPACT, K_COUNT
 };

@@ -34,6 +34,20 @@ torch::Tensor photometric_loss(const torch::Tensor& image, const torch::Tensor& 
 torch::Tensor photometric_loss_parts(const torch::Tensor& image, const torch::Tensor& gt, float lambda_dssim = 0.2f,
                                      const torch::Tensor& window1d = torch::Tensor());
 
+// ---- per-keyframe exposure compensation (an extension; csrc/exposure.hip) -------------------------------------------
+// photometric_loss on x' = g_c * image + b_c as ONE autograd node, the compensated image never reaching memory:
+// exposure is [C,2] rows (g_c, b_c) or [2] shared by the channels (f32 on the device, typically a leaf per keyframe
+// beside its pose leaf); log_gain reads column 0 as log g (exp on C numbers, in Torch).  Gradients w.r.t. image and
+// exposure.  Returns the 0-dim loss.
+// (Like image_metrics, these two are not part of the oracle/ref_link link check, which stays as it is.)
+torch::Tensor exposure_photometric_loss(const torch::Tensor& image, const torch::Tensor& gt,
+                                        const torch::Tensor& exposure, float lambda_dssim = 0.2f,
+                                        const torch::Tensor& window1d = torch::Tensor(), bool log_gain = false);
+// g_c * image + b_c (one fused multiply-add per element, no graph) for evaluation and export; out: a contiguous tensor
+// of the image's shape to write (the image itself is allowed), undefined = a new one.
+torch::Tensor apply_exposure(const torch::Tensor& image, const torch::Tensor& exposure,
+                             const torch::Tensor& out = torch::Tensor());
+
 // ---- the LiDAR similarity loss (optimize_vis step 3) ---------------------------------------------------------------
 // lambda * compute_min_distance(points, Get_xyz()[sel], Get_scaling()[sel]) (src/gs/gaussian.cu:87-114, 230-237) as ONE
 // autograd node on the kernels of csrc/simi.hip: points [m,3] f32 and sel [n] int32 (ascending unique rows) on the

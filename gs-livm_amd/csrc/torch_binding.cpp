@@ -498,6 +498,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         },
         py::arg("image"), py::arg("gt"), py::arg("window1d") = py::none(), py::arg("totals") = py::none());
   n.def("psnr", &nx::psnr, py::arg("image"), py::arg("gt"));
+  n.def("exposure_photometric_loss",
+        [opt](torch::Tensor image, torch::Tensor gt, torch::Tensor exposure, float lambda_dssim, py::object window,
+              bool log_gain) {
+          return nx::exposure_photometric_loss(image, gt, exposure, lambda_dssim, opt(window), log_gain);
+        },
+        py::arg("image"), py::arg("gt"), py::arg("exposure"), py::arg("lambda_dssim") = 0.2f,
+        py::arg("window1d") = py::none(), py::arg("log_gain") = false);
+  n.def("apply_exposure",
+        [opt](torch::Tensor image, torch::Tensor exposure, py::object out) {
+          return nx::apply_exposure(image, exposure, opt(out));
+        },
+        py::arg("image"), py::arg("exposure"), py::arg("out") = py::none());
   n.def("to_u8", [opt](torch::Tensor image, bool bgr, py::object out) { return nx::to_u8(image, bgr, opt(out)); },
         py::arg("image"), py::arg("bgr") = true, py::arg("out") = py::none());
   n.def("depth_to_u8",

@@ -103,6 +103,46 @@ struct PhotometricLossFn : public torch::autograd::Function<PhotometricLossFn> {
   }
 };
 
+// [C,2] rows (g_c, b_c) from [C,2] or a shared [2] (expanded: autograd sums its gradient); log_gain: g = exp(column 0)
+torch::Tensor per_channel_exposure(const torch::Tensor& exposure, int64_t channels, bool log_gain) {
+  if (!exposure.defined() || !((exposure.dim() == 1 && exposure.size(0) == 2) ||
+                               (exposure.dim() == 2 && exposure.size(0) == channels && exposure.size(1) == 2)))
+    throw std::invalid_argument("exposure: [C,2] rows (gain, bias), or [2] shared by the channels");
+  torch::Tensor e = exposure.dim() == 1 ? exposure.expand({channels, 2}) : exposure;
+  if (log_gain) e = torch::stack({torch::exp(e.select(1, 0)), e.select(1, 1)}, 1);
+  return e;
+}
+
+struct ExposureLossFn : public torch::autograd::Function<ExposureLossFn> {
+  static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor image, torch::Tensor gt,
+                               torch::Tensor exposure, double lambda, torch::Tensor window1d) {
+    const torch::Tensor img = dev_f32(image, "image"), ref = dev_f32(gt, "gt"), e = dev_f32(exposure, "exposure");
+    if (img.dim() != 3 || img.sizes() != ref.sizes())
+      throw std::invalid_argument("exposure_photometric_loss: [C,H,W] images of one shape");
+    const int C = img.size(0), H = img.size(1), W = img.size(2);
+    float taps[11];
+    window_taps(window1d, taps);
+    const bool want = image.requires_grad() || exposure.requires_grad();
+    const size_t nbytes = gsr_exposure_loss_workspace(C, H, W);
+    torch::Tensor ws = workspace(nbytes, img);
+    torch::Tensor out3 = torch::empty({3}, img.options());
+    torch::Tensor grad = want ? torch::empty_like(img) : torch::Tensor();
+    torch::Tensor grad_e = want ? torch::empty_like(e) : torch::Tensor();
+    check(gsr_exposure_loss(C, H, W, fp(img), fp(ref), fp(e), taps, static_cast<float>(lambda), out3.data_ptr<float>(),
+                            fp(grad), fp(grad_e), reinterpret_cast<char*>(ws.data_ptr()), nbytes, current_stream()),
+          "gsr_exposure_loss");
+    ctx->save_for_backward({image.requires_grad() ? grad : torch::empty({0}, img.options()),
+                            exposure.requires_grad() ? grad_e : torch::empty({0}, img.options())});
+    return out3[0];
+  }
+  static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx,
+                                               torch::autograd::tensor_list grad_outputs) {
+    const auto saved = ctx->get_saved_variables();
+    return {scaled(saved[0], grad_outputs[0]), torch::Tensor(), scaled(saved[1], grad_outputs[0]), torch::Tensor(),
+            torch::Tensor()};
+  }
+};
+
 struct SimilarityLossFn : public torch::autograd::Function<SimilarityLossFn> {
   static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor points, torch::Tensor sel,
                                torch::Tensor xyz, torch::Tensor scaling, double lambda) {
@@ -256,6 +296,28 @@ torch::Tensor photometric_loss_parts(const torch::Tensor& image, const torch::Te
                                      const torch::Tensor& window1d) {
   torch::NoGradGuard no_grad;
   return run_loss(image, gt, lambda_dssim, window1d, false).first;
+}
+
+torch::Tensor exposure_photometric_loss(const torch::Tensor& image, const torch::Tensor& gt,
+                                        const torch::Tensor& exposure, float lambda_dssim,
+                                        const torch::Tensor& window1d, bool log_gain) {
+  if (!image.defined() || image.dim() != 3) throw std::invalid_argument("exposure_photometric_loss: image is [C,H,W]");
+  return ExposureLossFn::apply(image, gt, per_channel_exposure(exposure, image.size(0), log_gain),
+                               static_cast<double>(lambda_dssim), window1d.defined() ? window1d : reference_window_1d());
+}
+
+torch::Tensor apply_exposure(const torch::Tensor& image, const torch::Tensor& exposure, const torch::Tensor& out) {
+  torch::NoGradGuard no_grad;
+  const torch::Tensor img = dev_f32(image.detach(), "image");
+  if (img.dim() != 3) throw std::invalid_argument("apply_exposure: image is [C,H,W]");
+  const torch::Tensor e = dev_f32(per_channel_exposure(exposure.detach(), img.size(0), false), "exposure");
+  torch::Tensor dst = out.defined() ? out : torch::empty_like(img);
+  if (!dst.is_cuda() || dst.scalar_type() != torch::kFloat32 || !dst.is_contiguous() || dst.sizes() != img.sizes())
+    throw std::invalid_argument("apply_exposure: out is a contiguous float32 device tensor of the image's shape");
+  check(gsr_apply_exposure(static_cast<int>(img.size(0)), static_cast<int>(img.size(1)), static_cast<int>(img.size(2)),
+                           fp(img), fp(e), fp(dst), current_stream()),
+        "gsr_apply_exposure");
+  return dst;
 }
 
 torch::Tensor similarity_loss(const torch::Tensor& points, const torch::Tensor& sel, const torch::Tensor& xyz,

@@ -45,6 +45,63 @@ def photometric_loss(img, gt, lambda_dssim=0.2, window11=None):
     return PhotometricLoss.apply(img, gt, window11, float(lambda_dssim))
 
 
+class ExposureLoss(torch.autograd.Function):
+    """photometric_loss on the exposure-compensated image x' = fma(g_c, img, b_c) as one node (csrc/exposure.hip; an
+    extension: the reference has no such term); gradients w.r.t. img and the [C,2] exposure (gt is data), both scaled
+    by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, img, gt, exposure, window11, lambda_dssim):
+        want = ctx.needs_input_grad[0] or ctx.needs_input_grad[2]
+        out3, grad, grad_e = _capi.exposure_loss(img, gt, exposure, window11.tolist(), lambda_dssim, want_grad=want)
+        ctx.grads = (grad, grad_e)
+        ctx.parts = out3  # [loss, l1, ssim] of the compensated image, for logging
+        return out3[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, grad_e = ctx.grads
+        need_i, need_e = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        return (grad * g if need_i else None), None, (grad_e * g if need_e else None), None, None
+
+
+def identity_exposure(channels=3, device=None):
+    """The exposure that changes nothing: [C,2] f32 rows (g, b) = (1, 0).  A keyframe's leaf starts here."""
+    e = torch.zeros((int(channels), 2), dtype=torch.float32, device=device)
+    e[:, 0] = 1.0
+    return e
+
+
+def _per_channel(exposure, channels, log_gain=False):
+    """[C,2] rows (g_c, b_c) from [C,2] or a shared [2] (expanded: autograd sums its gradient over the channels);
+    log_gain: column 0 holds a with g = exp(a) (the MonoGS parametrisation), on C numbers in Torch."""
+    if exposure.dim() == 1:
+        exposure = exposure.expand(channels, 2)
+    if log_gain:
+        exposure = torch.stack((torch.exp(exposure[:, 0]), exposure[:, 1]), dim=1)
+    return exposure
+
+
+def exposure_photometric_loss(img, gt, exposure, lambda_dssim=0.2, window11=None, log_gain=False):
+    """photometric_loss(g * img + b, gt) without the compensated image ever reaching memory: the keyframe's exposure
+    ([C,2] rows (g_c, b_c), or [2] shared by the channels; f32 on the device, typically a leaf beside the pose leaf)
+    absorbs the camera's auto-exposure step instead of the map.  log_gain=True reads column 0 as log g.  Returns the
+    0-dim loss; gradients flow to img and exposure."""
+    if window11 is None:
+        window11 = reference_window_1d()
+    e = _per_channel(exposure, int(img.shape[0]), log_gain)
+    return ExposureLoss.apply(img, gt, e, window11, float(lambda_dssim))
+
+
+def apply_exposure(img, exposure, out=None):
+    """g_c * img + b_c (one fused multiply-add per element, no graph) for evaluation and export: what a keyframe's
+    learnt exposure makes of its render.  img: [C,H,W] f32 on the device; exposure: [C,2] or [2]; out: a contiguous
+    tensor to write (img itself is allowed) or None."""
+    with torch.no_grad():
+        return _capi.apply_exposure(img.detach().contiguous(), _per_channel(exposure.detach(), int(img.shape[0])).contiguous(),
+                                    out=out)
+
+
 class SimilarityLoss(torch.autograd.Function):
     """loss = lambda * compute_min_distance(points, xyz[sel], scaling[sel]) (src/gs/gaussian.cu:87-114, 230-237) as
     one node; gradients w.r.t. xyz and the ACTIVATED scaling (points and sel are data).  The gradients are dense [P,3]

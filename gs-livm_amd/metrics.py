@@ -6,7 +6,7 @@ with the host application."""
 import torch
 
 from . import _capi
-from .loss import reference_window_1d
+from .loss import apply_exposure, reference_window_1d
 from .render_utils import render
 
 
@@ -48,17 +48,23 @@ def depth_to_u8(depth, max_depth=50.0, out=None):
     return _capi.pack_depth_u8(depth, max_depth, out=out)
 
 
-def evaluate_keyframes(cameras, gts, model, bg, on_frame=None, window11=None):
+def evaluate_keyframes(cameras, gts, model, bg, on_frame=None, window11=None, exposures=None):
     """The loop of saveRender (:2198-2231): every keyframe is rendered forward-only and measured against its ground
     truth ([3,H,W] f32 on the device); the per-frame metrics and their running float64 sums stay on the device and are
     copied to the host ONCE, after the last frame (the reference makes two .item() round trips per frame).
     on_frame(i, image, depth): hook of a host that exports frames (to_u8 / side_by_side / depth_to_u8, PNG writing).
+    exposures: one learnt exposure per keyframe ([C,2] or [2], `exposure_photometric_loss`) or None for a keyframe
+    without one; the render is compensated in place (`apply_exposure`) before it is measured and handed to on_frame,
+    so that the metrics are not charged for the camera's gain.
     -> dict(rows = CPU f32 [n,4] of {psnr, ssim, l1, mse} per frame, totals = CPU f64 [4] = {sum psnr, sum ssim,
     sum l1, n}, mean_psnr, mean_ssim, frames = n)."""
     cameras, gts = list(cameras), list(gts)
     if len(cameras) != len(gts):
         raise ValueError("one ground-truth image per camera")
     n = len(cameras)
+    exposures = [None] * n if exposures is None else list(exposures)
+    if len(exposures) != n:
+        raise ValueError("one exposure (or None) per camera")
     dev = model.Get_xyz().device
     win = (reference_window_1d() if window11 is None else window11).tolist()
     # one buffer, one copy: the four float64 totals in front (8-byte aligned), the n float32 rows behind them
@@ -67,6 +73,8 @@ def evaluate_keyframes(cameras, gts, model, bg, on_frame=None, window11=None):
     with torch.no_grad():
         for i, (cam, gt) in enumerate(zip(cameras, gts)):
             image, depth, _ = render(cam, model, bg)
+            if exposures[i] is not None:
+                image = apply_exposure(image, exposures[i], out=image if image.is_contiguous() else None)
             _capi.image_metrics(image, gt, win, out=rows[i], totals=totals)
             if on_frame is not None:
                 on_frame(i, image, depth)

@@ -406,6 +406,34 @@ int gsr_photometric_loss(int channels, int height, int width, const float* img, 
                          const float* window11_host, float lambda_dssim, float* loss_out3, float* dL_dimg,
                          char* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- per-keyframe exposure compensation, fused into the photometric loss (an extension: the reference has no such
+ * term; csrc/exposure.hip) ----
+ *   x'(p) = fma(g_c, x(p), b_c),   L = (1 - lambda) * mean|x' - gt| + lambda * (1 - mean(SSIM(x', gt)))
+ * for keyframes of auto-exposure / auto-gain cameras: the brightness step between keyframes goes to 2 C numbers per
+ * keyframe instead of the SH coefficients, the opacities and the pose.  exposure: [channels][2] device f32,
+ * exposure[c] = (g_c, b_c); the identity is (1, 0).  The gain enters linearly -- a log-gain g = exp(a) is the host's,
+ * on C numbers.  Everything else is gsr_photometric_loss's, taken on x': img / gt / window11_host / loss_out3 as
+ * there, zero padding of the COMPENSATED image (outside the image x' is 0, not b_c).
+ * With G = dL/dx' for upstream gradient 1:
+ *   dL_dimg[c][p] = g_c G(p)        dL_dexposure[c] = (sum_p G(p) x(p), sum_p G(p))  -- x the ORIGINAL image --
+ * dL_dexposure: [channels][2] device f32.  dL_dimg and dL_dexposure are both given (three launches) or both null (two
+ * launches, no gradient); one without the other is refused.  Refusals, in this order: a non-positive dimension, a
+ * plane of 2^31 - 1 pixels or more, a null img / gt / exposure / window11_host / loss_out3 / workspace, one gradient
+ * pointer without the other, workspace_bytes below gsr_exposure_loss_workspace (which returns 0 for a refused shape);
+ * nothing is launched or written then.  The workspace may sit at any 4-byte aligned address.
+ * No host wait, no allocation, the caller's stream.  Deterministic: the two exposure sums are float64, added per work
+ * unit and then per channel in a fixed order, no atomics, narrowed once.  At exposure = identity and an img without
+ * negative zeros every output equals gsr_photometric_loss's bit for bit.
+ * gsr_apply_exposure: out[c][p] = fma(g_c, img[c][p], b_c), one launch (evaluation and export).  img / out:
+ * [channels][H][W] device f32 at any 4-byte aligned address; out == img is allowed, any other overlap is not. */
+size_t gsr_exposure_loss_workspace(int channels, int height, int width);
+int gsr_exposure_loss(int channels, int height, int width, const float* img, const float* gt,
+                      const float* exposure /* device [channels][2] */, const float* window11_host,
+                      float lambda_dssim, float* loss_out3, float* dL_dimg, float* dL_dexposure,
+                      char* workspace, size_t workspace_bytes, void* stream);
+int gsr_apply_exposure(int channels, int height, int width, const float* img, const float* exposure,
+                       float* out, void* stream);
+
 /* ---- the LiDAR similarity loss (step 3 of optimize_vis), fused ----
  *   r = mean(scaling[sel]) (one scalar over the 3n selected elements),  d_ij = |points_i - xyz[sel_j]|,
  *   L = lambda * mean_i min_j max(d_ij - r, 0) = lambda / m * sum_i max(min_j d_ij - r, 0)
