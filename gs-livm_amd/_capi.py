@@ -72,7 +72,8 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_prune_mark", "gsr_prune_compact", "gsr_lidar_depth_image", "gsr_lidar_depth_loss",
            "gsr_lidar_depth_loss_workspace", "gsr_density_accumulate", "gsr_densify_workspace", "gsr_densify_mark",
            "gsr_densify_apply", "gsr_pose_gradient", "gsr_pose_gradient_workspace", "gsr_exposure_loss",
-           "gsr_exposure_loss_workspace", "gsr_apply_exposure")
+           "gsr_exposure_loss_workspace", "gsr_apply_exposure", "gsr_visibility_words", "gsr_visibility_pack",
+           "gsr_covisibility", "gsr_observation_count", "gsr_visibility_remap")
 
 
 def lib():
@@ -215,6 +216,17 @@ def lib():
     L.gsr_densify_mark.argtypes = [ci, vp, vp, cf, cf, ci, vp, vp, vp, vp, sz, vp]
     L.gsr_densify_apply.restype = ci
     L.gsr_densify_apply.argtypes = [ci, ci, ci, vp, vp, C.c_ulonglong] + [vp] * 6 + [C.POINTER(vp), C.POINTER(vp), vp, vp]
+    ll = C.c_longlong
+    L.gsr_visibility_words.restype = sz
+    L.gsr_visibility_words.argtypes = [ci]
+    L.gsr_visibility_pack.restype = ci
+    L.gsr_visibility_pack.argtypes = [ci, vp, vp, vp, ci, vp]
+    L.gsr_covisibility.restype = ci
+    L.gsr_covisibility.argtypes = [ci, vp, ll, ci, vp, ll, ci, vp, vp, vp, vp]
+    L.gsr_observation_count.restype = ci
+    L.gsr_observation_count.argtypes = [ci, vp, ll, ci, ci, ci, vp, vp, vp]
+    L.gsr_visibility_remap.restype = ci
+    L.gsr_visibility_remap.argtypes = [ci, vp, ll, ci, vp, vp, vp, ll, ci, vp]
     L.gsr_init_gaussians.restype = ci
     L.gsr_init_gaussians.argtypes = [ci, ci, vp, vp, vp, cf] + [vp] * 6 + [vp]
     L.gsr_ply_row_floats.restype = sz

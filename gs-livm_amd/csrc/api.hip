@@ -150,6 +150,7 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_activate_backward", "k_adam", "k_loss_forward", "k_loss_finalize", "k_loss_backward", "k_init_gaussians", "k_pack_ply_rows", "k_model_step", "k_tile_order", "k_live_sat", "k_compact_near",
     "k_simi_nearest", "k_simi_points", "k_simi_grads",
     "k_delta_project", "k_delta_sample", "k_delta_scatter", "k_delta_convert",
+    "k_visibility",  // the four kernels of covis.hip under one id: the 64th, the last the one-word mask holds
     "k_lidar_clear", "k_lidar_splat", "k_lidar_convert", "k_lidar_loss_forward", "k_lidar_loss_finish",
     "k_lidar_loss_grads",
     "k_density_accumulate", "k_densify_mark", "k_densify_scan", "k_densify_rank", "k_densify_apply",
@@ -157,6 +158,7 @@ static const char* const kKernelNames[K_COUNT] = {
     "k_exposure_loss_forward", "k_exposure_loss_backward", "k_exposure_loss_finish", "k_apply_exposure",
     "k_metrics_forward", "k_metrics_finalize", "k_pack_image_u8", "k_pack_depth_u8",
     "k_prune_mark", "k_prune_scan", "k_prune_rank", "k_prune_compact"};
+static_assert(K_COUNT <= 64, "g_prof_mask is one 64-bit word");
 
 extern "C" {
 
@@ -1941,6 +1943,90 @@ int gsr_densify_apply(int P, int M, int n_new, const unsigned char* kinds, const
   if (int e = check_aligned4(bits)) return e;
   HIP_TRY(launch_densify_apply(P, M, kinds, offsets, seed, params6, exp_avg6, exp_avg_sq6, stats,
                                (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+// ---- keyframe covisibility (covis.hip).  The order of the checks is part of the contract (include/gsraster.h): shape,
+// then the choice of sources / outputs, then null pointers, then alignment, then (remap) overlapping slabs.
+static long long vis_need(int P) { return ((long long)P + 63) / 64; }
+static const long long kVisMaxWords = 0x7fffffffLL / 64;  // words * 64 stays an int32
+static const char* const kMisaligned8 = "misaligned pointer: visibility words need 8-byte alignment";
+
+size_t gsr_visibility_words(int P) { return P > 0 ? (size_t)vis_need(P) : 0; }
+
+int gsr_visibility_pack(int P, const int* radii, const unsigned char* mask, unsigned long long* bits, int words,
+                        void* stream_) {
+  g_err[0] = 0;
+  if (P <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (words < vis_need(P)) return fail(GSR_ERR_INVALID_ARGUMENT, "words too small: need %lld", vis_need(P));
+  if (words > kVisMaxWords) return fail(GSR_ERR_INVALID_ARGUMENT, "words * 64 beyond int32");
+  if ((radii != nullptr) == (mask != nullptr))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "exactly one of radii and mask is given");
+  if (!bits) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if ((uintptr_t)bits & 7u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned8);
+  if (int e = check_aligned4((uintptr_t)radii)) return e;
+  HIP_TRY(launch_visibility_pack(P, radii, mask, bits, words, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+int gsr_covisibility(int Q, const unsigned long long* q_bits, long long q_pitch, int K,
+                     const unsigned long long* k_bits, long long k_pitch, int words, int* inter, int* q_count,
+                     int* k_count, void* stream_) {
+  g_err[0] = 0;
+  if (Q <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad Q");
+  if (K <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad K");
+  if (words <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad words");
+  if (q_pitch < words || k_pitch < words) return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: need %d", words);
+  if (words > kVisMaxWords) return fail(GSR_ERR_INVALID_ARGUMENT, "words * 64 beyond int32");
+  if ((long long)Q * (long long)K > 0x7fffffffLL) return fail(GSR_ERR_INVALID_ARGUMENT, "Q * K beyond int32");
+  if (visibility_overlap_blocks(Q, words) > 0x7fffffffull)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "problem too large for one overlap launch");
+  if (!q_bits || !k_bits || !inter) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (((uintptr_t)q_bits | (uintptr_t)k_bits) & 7u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned8);
+  if (int e = check_aligned4((uintptr_t)inter | (uintptr_t)q_count | (uintptr_t)k_count)) return e;
+  HIP_TRY(launch_visibility_overlap(Q, q_bits, q_pitch, K, k_bits, k_pitch, words, inter, q_count, k_count,
+                                    (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+int gsr_observation_count(int K, const unsigned long long* bits, long long pitch, int P, int first_row, int min_count,
+                          int* count, unsigned char* drop, void* stream_) {
+  g_err[0] = 0;
+  if (K <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad K");
+  if (P <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (pitch < vis_need(P)) return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: need %lld", vis_need(P));
+  if (vis_need(P) > kVisMaxWords) return fail(GSR_ERR_INVALID_ARGUMENT, "words * 64 beyond int32");
+  if (first_row < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad first_row");
+  if (min_count < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad min_count");
+  if (!count && !drop) return fail(GSR_ERR_INVALID_ARGUMENT, "neither count nor drop is asked for");
+  if (!bits) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if ((uintptr_t)bits & 7u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned8);
+  if (int e = check_aligned4((uintptr_t)count)) return e;
+  HIP_TRY(launch_visibility_count(K, bits, pitch, P, first_row, min_count, count, drop, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+int gsr_visibility_remap(int K, const unsigned long long* src, long long src_pitch, int P, const unsigned char* reasons,
+                         const int* row_map, unsigned long long* dst, long long dst_pitch, int dst_words,
+                         void* stream_) {
+  g_err[0] = 0;
+  if (K <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad K");
+  if (P <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (dst_words <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad dst_words");
+  if (src_pitch < vis_need(P)) return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: need %lld", vis_need(P));
+  if (dst_pitch < dst_words) return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: need %d", dst_words);
+  if (vis_need(P) > kVisMaxWords || dst_words > kVisMaxWords)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "words * 64 beyond int32");
+  if (!src || !reasons || !row_map || !dst) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (((uintptr_t)src | (uintptr_t)dst) & 7u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned8);
+  if (int e = check_aligned4((uintptr_t)row_map)) return e;
+  {  // the slabs from their first word to the last word of their last row
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + 8u * (uintptr_t)((long long)(K - 1) * src_pitch + vis_need(P));
+    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + 8u * (uintptr_t)((long long)(K - 1) * dst_pitch + dst_words);
+    if (s0 < d1 && d0 < s1) return fail(GSR_ERR_INVALID_ARGUMENT, "src and dst overlap: the remap is out of place");
+  }
+  HIP_TRY(launch_visibility_remap(K, src, src_pitch, P, reasons, row_map, dst, dst_pitch, dst_words,
+                                  (hipStream_t)stream_));
   return GSR_OK;
 }
 

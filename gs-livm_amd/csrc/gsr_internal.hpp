@@ -511,6 +511,18 @@ hipError_t launch_densify_mark(int P, const float* stats, const float* scaling_r
 hipError_t launch_densify_apply(int P, int M, const unsigned char* kinds, const int* offsets, unsigned long long seed,
                                 float* const* params6, float* const* exp_avg6, float* const* exp_avg_sq6, float* stats,
                                 hipStream_t s);
+// covis.hip (keyframe covisibility: visibility bitsets, their overlap counts, observation counts, the remap after a prune)
+hipError_t launch_visibility_pack(int P, const int* radii, const unsigned char* mask, unsigned long long* bits, int words,
+                                  hipStream_t s);
+unsigned long long visibility_overlap_blocks(int Q, int words);
+hipError_t launch_visibility_overlap(int Q, const unsigned long long* q_bits, long long q_pitch, int K,
+                                     const unsigned long long* k_bits, long long k_pitch, int words, int* inter,
+                                     int* q_count, int* k_count, hipStream_t s);
+hipError_t launch_visibility_count(int K, const unsigned long long* bits, long long pitch, int P, int first_row,
+                                   int min_count, int* count, unsigned char* drop, hipStream_t s);
+hipError_t launch_visibility_remap(int K, const unsigned long long* src, long long src_pitch, int P,
+                                   const unsigned char* reasons, const int* row_map, unsigned long long* dst,
+                                   long long dst_pitch, int dst_words, hipStream_t s);
 
 inline int sort_passes(int end_bit) { return (end_bit + 7) / 8; }
 // digit width: the key bits are split evenly over the passes (13 tile bits -> 7 + 6, 32 depth bits -> 4 x 8)
@@ -524,6 +536,9 @@ enum KernelId {
   K_DSORT_SCATTER, K_ACTIVATE, K_ACTIVATE_BWD, K_ADAM, K_LOSS_FWD, K_LOSS_FINALIZE, K_LOSS_BWD, K_INIT_GAUSSIANS, K_PACK_PLY, K_MODEL_STEP, K_TILE_ORDER, K_LIVE_SAT, K_COMPACT_NEAR,
   K_SIMI_NEAREST, K_SIMI_POINTS, K_SIMI_GRADS,
   K_DELTA_PROJECT, K_DELTA_SAMPLE, K_DELTA_SCATTER, K_DELTA_CONVERT,
+  // ONE id for the four covisibility kernels (covis.hip): it is the 64th, and the profiler mask is one 64-bit word.  THE
+  // MASK IS NOW FULL: a further kernel shares an id or the mask is widened first.
+  K_VISIBILITY,
   // (beside the other depth term; ids are looked up by name, and the prune kernels stay the last four)
   K_LIDAR_CLEAR, K_LIDAR_SPLAT, K_LIDAR_CONVERT, K_LIDAR_LOSS_FWD, K_LIDAR_LOSS_FINISH, K_LIDAR_LOSS_GRADS,
   K_DENSITY_ACCUMULATE, K_DENSIFY_MARK, K_DENSIFY_SCAN, K_DENSIFY_RANK, K_DENSIFY_APPLY,

@@ -212,6 +212,29 @@ void densify_apply(int64_t P, int64_t n_new, const torch::Tensor& kinds, const t
                    const std::vector<torch::Tensor>& params6, const std::vector<torch::Tensor>& exp_avg6,
                    const std::vector<torch::Tensor>& exp_avg_sq6, const torch::Tensor& stats = torch::Tensor());
 
+// ---- keyframe covisibility (an extension: the reference draws its training views blindly) -----------------------------
+// Thin tensor-level hosts of csrc/covis.hip; include/gsraster.h has the contract.  A visibility row is int64 words, bit
+// i % 64 of word i / 64 = model row i; a slab is a 2-D int64 device tensor with contiguous rows, its stride(0) the pitch
+// (a 1-D tensor is one row).  All device tensors, nothing waits.  (Not part of the oracle/ref_link link check either.)
+// source: a forward's radii ([P] int32, seen = radii > 0) or a bool / uint8 mask (markVisible's).  words: 0 = ceil(P / 64);
+// all `words` words are written, bits at and beyond P are zero.
+torch::Tensor visibility_pack(const torch::Tensor& source, int64_t words = 0);
+struct Covisibility {
+  torch::Tensor inter, q_count, k_count;  // [Q,K], [Q], [K] int32; the counts undefined when not asked for
+};
+// inter[q][k] = popcount(q row & k row) over `words` words (0 = all that both hold); k_bits undefined = q_bits.
+Covisibility covisibility(const torch::Tensor& q_bits, const torch::Tensor& k_bits = torch::Tensor(), int64_t words = 0,
+                          bool counts = true);
+struct ObservationCount {
+  torch::Tensor count, drop;  // [P] int32, [P] uint8 (i >= first_row && count < min_count); undefined when not asked for
+};
+ObservationCount observation_count(const torch::Tensor& bits, int64_t P, int64_t first_row = 0, int64_t min_count = 0,
+                                   bool want_count = true, bool want_drop = false);
+// The rows of `src` after the stable compaction of prune_mark's (reasons, row_map): a new [K, dst_words] slab
+// (dst_words: 0 = ceil(P / 64), which always suffices).
+torch::Tensor visibility_remap(const torch::Tensor& src, const torch::Tensor& reasons, const torch::Tensor& row_map,
+                               int64_t dst_words = 0);
+
 // ---- row 4: map growth and PLY export ---------------------------------------------------------------------------
 // The tensor construction of GaussianModel::addNewPointcloud (src/gs/gaussian.cu:241-313) for n new points -- xyz
 // [n,3], covs [n,3,3], rgbs [n,3] in 0..255 -- written IN PLACE into n-row views (normally the tail rows of capacity

@@ -598,6 +598,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("P"), py::arg("n_new"), py::arg("kinds"), py::arg("offsets"), py::arg("seed"), py::arg("params6"),
         py::arg("exp_avg6") = std::vector<torch::Tensor>(), py::arg("exp_avg_sq6") = std::vector<torch::Tensor>(),
         py::arg("stats") = py::none());
+  n.def("visibility_pack", &nx::visibility_pack, py::arg("source"), py::arg("words") = 0);
+  n.def("covisibility",
+        [opt](torch::Tensor q_bits, py::object k_bits, int64_t words, bool counts) {
+          const nx::Covisibility c = nx::covisibility(q_bits, opt(k_bits), words, counts);
+          return std::make_tuple(c.inter, c.q_count, c.k_count);
+        },
+        py::arg("q_bits"), py::arg("k_bits") = py::none(), py::arg("words") = 0, py::arg("counts") = true);
+  n.def("observation_count",
+        [](torch::Tensor bits, int64_t P, int64_t first_row, int64_t min_count, bool want_count, bool want_drop) {
+          const nx::ObservationCount c = nx::observation_count(bits, P, first_row, min_count, want_count, want_drop);
+          return std::make_tuple(c.count, c.drop);
+        },
+        py::arg("bits"), py::arg("P"), py::arg("first_row") = 0, py::arg("min_count") = 0, py::arg("want_count") = true,
+        py::arg("want_drop") = false);
+  n.def("visibility_remap", &nx::visibility_remap, py::arg("src"), py::arg("reasons"), py::arg("row_map"),
+        py::arg("dst_words") = 0);
   n.def("init_gaussians", &nx::init_gaussians);
   n.def("pack_ply_rows", &nx::pack_ply_rows);
   n.def("write_ply", &nx::write_ply);

@@ -668,6 +668,104 @@ void densify_apply(int64_t P, int64_t n_new, const torch::Tensor& kinds, const t
 }
 
 namespace {
+// A slab of visibility rows: a 2-D int64 device tensor with contiguous rows (a 1-D tensor is one row); the pitch is its
+// row stride in words.
+struct Slab {
+  torch::Tensor t;
+  int64_t rows, pitch;
+  unsigned long long* ptr() const { return reinterpret_cast<unsigned long long*>(t.data_ptr<int64_t>()); }
+};
+Slab slab(const torch::Tensor& bits, const char* what) {
+  torch::Tensor t = bits.defined() && bits.dim() == 1 ? bits.unsqueeze(0) : bits;
+  if (!t.defined() || !t.is_cuda() || t.scalar_type() != torch::kInt64 || t.dim() != 2 || t.size(0) < 1 || t.size(1) < 1 ||
+      (t.size(1) > 1 && t.stride(1) != 1))
+    throw std::invalid_argument(std::string(what) + ": expected an int64 device tensor [rows, words] with contiguous rows");
+  const int64_t pitch = t.size(0) > 1 ? t.stride(0) : std::max<int64_t>(t.stride(0), t.size(1));
+  return Slab{t, t.size(0), pitch};
+}
+int64_t words_of(int64_t P) { return (P + 63) / 64; }
+}  // namespace
+
+torch::Tensor visibility_pack(const torch::Tensor& source, int64_t words) {
+  torch::NoGradGuard no_grad;
+  if (!source.defined() || !source.is_cuda())
+    throw std::invalid_argument("visibility_pack: int32 radii or a bool / uint8 mask on the device");
+  const torch::Tensor src = source.reshape({-1}).contiguous();
+  const int64_t P = src.numel();
+  const int* radii = nullptr;
+  const unsigned char* mask = nullptr;
+  if (src.scalar_type() == torch::kInt32) radii = P ? src.data_ptr<int>() : nullptr;
+  else if (src.scalar_type() == torch::kBool || src.scalar_type() == torch::kByte)
+    mask = P ? static_cast<const unsigned char*>(src.data_ptr()) : nullptr;
+  else throw std::invalid_argument("visibility_pack: int32 radii or a bool / uint8 mask on the device");
+  if (words <= 0) words = words_of(P);
+  torch::Tensor out = torch::empty({words}, src.options().dtype(torch::kInt64));
+  check(gsr_visibility_pack(static_cast<int>(P), radii, mask, reinterpret_cast<unsigned long long*>(out.data_ptr<int64_t>()),
+                            static_cast<int>(std::min<int64_t>(words, 0x7fffffff)), current_stream()),
+        "gsr_visibility_pack");
+  return out;
+}
+
+Covisibility covisibility(const torch::Tensor& q_bits, const torch::Tensor& k_bits, int64_t words, bool counts) {
+  torch::NoGradGuard no_grad;
+  const Slab q = slab(q_bits, "covisibility");
+  const Slab k = k_bits.defined() ? slab(k_bits, "covisibility") : q;
+  if (words <= 0) words = std::min(q.t.size(1), k.t.size(1));
+  if (words > q.t.size(1) || words > k.t.size(1)) throw std::invalid_argument("covisibility: a row holds fewer words");
+  const auto ints = q.t.options().dtype(torch::kInt32);
+  Covisibility out;
+  out.inter = torch::empty({q.rows, k.rows}, ints);
+  if (counts) {
+    out.q_count = torch::empty({q.rows}, ints);
+    out.k_count = torch::empty({k.rows}, ints);
+  }
+  check(gsr_covisibility(static_cast<int>(q.rows), q.ptr(), q.pitch, static_cast<int>(k.rows), k.ptr(), k.pitch,
+                         static_cast<int>(std::min<int64_t>(words, 0x7fffffff)), out.inter.data_ptr<int>(),
+                         counts ? out.q_count.data_ptr<int>() : nullptr, counts ? out.k_count.data_ptr<int>() : nullptr,
+                         current_stream()),
+        "gsr_covisibility");
+  return out;
+}
+
+ObservationCount observation_count(const torch::Tensor& bits, int64_t P, int64_t first_row, int64_t min_count,
+                                   bool want_count, bool want_drop) {
+  torch::NoGradGuard no_grad;
+  const Slab b = slab(bits, "observation_count");
+  const auto int32 = [](int64_t v) { return v >= -0x7fffffffLL && v <= 0x7fffffffLL; };
+  if (P < 0 || !int32(P) || !int32(first_row) || !int32(min_count))
+    throw std::invalid_argument("observation_count: P, first_row and min_count are int32, P is not negative");
+  if (b.t.size(1) < words_of(P)) throw std::invalid_argument("observation_count: the rows hold fewer than ceil(P / 64) words");
+  ObservationCount out;
+  if (want_count) out.count = torch::empty({P}, b.t.options().dtype(torch::kInt32));
+  if (want_drop) out.drop = torch::empty({P}, b.t.options().dtype(torch::kByte));
+  check(gsr_observation_count(static_cast<int>(b.rows), b.ptr(), b.pitch, static_cast<int>(P), static_cast<int>(first_row),
+                              static_cast<int>(min_count), want_count && P ? out.count.data_ptr<int>() : nullptr,
+                              want_drop && P ? out.drop.data_ptr<unsigned char>() : nullptr, current_stream()),
+        "gsr_observation_count");
+  return out;
+}
+
+torch::Tensor visibility_remap(const torch::Tensor& src, const torch::Tensor& reasons, const torch::Tensor& row_map,
+                               int64_t dst_words) {
+  torch::NoGradGuard no_grad;
+  const Slab s = slab(src, "visibility_remap");
+  const int64_t P = reasons.defined() ? reasons.numel() : 0;
+  if (!reasons.defined() || !reasons.is_cuda() || reasons.scalar_type() != torch::kByte || !reasons.is_contiguous() ||
+      !row_map.defined() || !row_map.is_cuda() || row_map.scalar_type() != torch::kInt32 || !row_map.is_contiguous() ||
+      row_map.numel() != P + 1)
+    throw std::invalid_argument("visibility_remap: reasons [P] uint8 and row_map [P+1] int32 on the device, from prune_mark");
+  if (s.t.size(1) < words_of(P)) throw std::invalid_argument("visibility_remap: the source rows hold fewer than ceil(P / 64) words");
+  if (dst_words <= 0) dst_words = words_of(P);
+  torch::Tensor dst = torch::empty({s.rows, dst_words}, s.t.options());
+  check(gsr_visibility_remap(static_cast<int>(s.rows), s.ptr(), s.pitch, static_cast<int>(P),
+                             P ? reasons.data_ptr<unsigned char>() : nullptr, row_map.data_ptr<int>(),
+                             reinterpret_cast<unsigned long long*>(dst.numel() ? dst.data_ptr<int64_t>() : nullptr),
+                             dst_words, static_cast<int>(std::min<int64_t>(dst_words, 0x7fffffff)), current_stream()),
+        "gsr_visibility_remap");
+  return dst;
+}
+
+namespace {
 // dst[k][row_map[i]] = src[k][i] where reasons[i] == 0, at most eighteen tensors: one launch
 void compact18(const std::vector<torch::Tensor>& src, const std::vector<torch::Tensor>& dst, const torch::Tensor& reasons,
                const torch::Tensor& row_map) {

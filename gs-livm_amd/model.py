@@ -320,6 +320,7 @@ class GrowableGaussians(GaussianParameters):
         self._buf, self._m, self._v = {}, {}, {}
         self._optimizer = None
         self._stats = None  # [capacity, 3] {grad_sum, views, max_radius}: enable_density_stats()
+        self._visibility = []  # covis.KeyframeVisibility records that follow a prune: attach_visibility()
         self.voxel_index = VoxelIndex(self.device)  # gs_hash_indexes_
         self._reserve(max(1, int(capacity)))
         self._bind()
@@ -355,6 +356,14 @@ class GrowableGaussians(GaussianParameters):
 
     def attach(self, optimizer):
         self._optimizer = optimizer
+
+    def attach_visibility(self, vis):
+        """Makes `prune` renumber the keyframe visibility records `vis` (covis.KeyframeVisibility) with the rows: one
+        launch on the device row map, only when rows were dropped, before prune returns.  Growth needs nothing: new rows
+        keep the old numbers and older keyframes read 0 for them.  Without an attachment prune launches what it always
+        launched."""
+        if not any(v is vis for v in self._visibility):
+            self._visibility.append(vis)
 
     @torch.no_grad()
     def add_new_pointcloud(self, xyz, covs, rgbs, scale_factor=1.0, voxel_keys=None, voxel_counts=None):
@@ -437,6 +446,8 @@ class GrowableGaussians(GaussianParameters):
         self.P = P_new
         self._bind()
         self.voxel_index.remap(row_map_host)
+        for vis in self._visibility:
+            vis.remap(reasons, row_map, rows_after=P_new)
         return out
 
     @torch.no_grad()

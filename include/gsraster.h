@@ -698,6 +698,64 @@ int gsr_densify_apply(int P, int M, int n_new, const unsigned char* kinds, const
                       float* opacity_raw, float* const* exp_avg6, float* const* exp_avg_sq6, float* stats,
                       void* stream);
 
+/* ---- keyframe covisibility: one bit per (keyframe, Gaussian), kept on the device (an extension) ----
+ * The reference draws its training views blindly (lioOptimization.cpp:1573-1641).  A host that refines poses and prunes
+ * floaters wants what MonoGS and SplaTAM keep: which keyframes see the same Gaussians, and how many keyframes see each
+ * Gaussian.  Which keyframes to choose, with which thresholds, and when to prune stays with the caller.
+ *
+ * A VISIBILITY ROW is `words` >= gsr_visibility_words(P) little-endian 64-bit words: bit i % 64 of word i / 64 belongs
+ * to model row i.  The rows of several keyframes lie in one SLAB with a row pitch counted in words (pitch >= words; the
+ * words between a row's end and the next row are never read or written).  Everything here is integer arithmetic: every
+ * result is exact and the same on every run.
+ *
+ * gsr_visibility_pack (ONE launch per keyframe): bit i = radii[i] > 0 (radii [P] int32, gsr_forward's output) or
+ * mask[i] != 0 (mask [P] bytes, what gsr_mark_visible writes); exactly one of the two is given.  ALL `words` words of the
+ * row are written and the bits at and beyond P are zero: a row recorded again after the model shrank or grew carries no
+ * stale bit.
+ *
+ * gsr_covisibility (ONE launch behind the zero fill of the outputs on the stream): for Q query rows and K keyframe rows
+ * over `words` words, inter [Q][K] int32 (row-major) = sum over the words of popcount(q_w & k_w); q_count [Q] and
+ * k_count [K] (each nullable) are the rows' own popcounts.  The two slabs may be the same memory: the full matrix, whose
+ * diagonal is the counts.  Eight query rows stay in registers while the keyframe rows stream past them, so a keyframe
+ * word is loaded once per eight query rows.  Per-workgroup partial counts are added with 32-bit integer atomics: exact
+ * and independent of the order.  All `words` words count: a caller that passes more than gsr_visibility_words(P) words
+ * keeps the tail zero, as gsr_visibility_pack does.
+ *
+ * gsr_observation_count (ONE launch, each word of the slab read once): count [P] int32 (nullable) = how many of the K
+ * rows have bit i set; drop [P] bytes (nullable) = (i >= first_row && count[i] < min_count) ? 1 : 0 -- the mask
+ * gsr_prune_mark takes as `drop`: the rows from first_row on that fewer than min_count keyframes observe.  At least one
+ * of the two is asked for.
+ *
+ * gsr_visibility_remap (ONE launch) follows a stable compaction: reasons [P] and row_map [P + 1] exactly as
+ * gsr_prune_mark wrote them, on the device.  In each of the K destination rows bit row_map[i] = source bit i for every
+ * row with reasons[i] == 0, and every other bit of the row's dst_words words is zero.  Out of place; a gather (each
+ * destination word is stored once: no atomics, no separate zero fill).  The new row count P' = row_map[P] is known to
+ * the device only: the caller passes dst_words >= gsr_visibility_words(P') -- gsr_visibility_words(P) always suffices
+ * -- and a bit that would lie beyond dst_words words is not written anywhere.
+ *
+ * Alignment: visibility words 8 bytes, int32 arrays 4 bytes, byte arrays 1; any other offset is refused.
+ * Refused (GSR_ERR_INVALID_ARGUMENT with a gsr_last_error text, nothing enqueued or written), IN THIS ORDER:
+ *   1. shape: a count (P, Q, K, words, dst_words) that is not positive; `words` or a pitch below what the rows need
+ *      (gsr_visibility_words(P); `words`; dst_words); words * 64 beyond int32; Q * K beyond int32; a negative first_row or
+ *      min_count;
+ *   2. the choice: both or neither of radii and mask; neither of count and drop;
+ *   3. a null required pointer (q_count and k_count are optional);
+ *   4. a misaligned pointer, bit pointers before int32 pointers;
+ *   5. gsr_visibility_remap: src and dst slabs that overlap.
+ * gsr_visibility_words(P) = (P + 63) / 64, 0 for P <= 0.
+ * No host synchronisation, no allocation, the caller's stream only. */
+size_t gsr_visibility_words(int P);
+int gsr_visibility_pack(int P, const int* radii, const unsigned char* mask, unsigned long long* bits, int words,
+                        void* stream);
+int gsr_covisibility(int Q, const unsigned long long* q_bits, long long q_pitch, int K,
+                     const unsigned long long* k_bits, long long k_pitch, int words, int* inter, int* q_count,
+                     int* k_count, void* stream);
+int gsr_observation_count(int K, const unsigned long long* bits, long long pitch, int P, int first_row, int min_count,
+                          int* count, unsigned char* drop, void* stream);
+int gsr_visibility_remap(int K, const unsigned long long* src, long long src_pitch, int P,
+                         const unsigned char* reasons, const int* row_map, unsigned long long* dst, long long dst_pitch,
+                         int dst_words, void* stream);
+
 /* Optional per-kernel device timing (hipEvent pairs recorded on the launch stream around every
  * kernel launch while enabled).  Measurement aid for bench.py's roofline line; the reference has only
  * host wall-clock timers (include/common/timer/timer.h:36-52).  Not thread-safe; off by default.
@@ -710,7 +768,9 @@ int gsr_kernel_count(void);
 const char* gsr_kernel_name(int kernel_id);
 int gsr_profile_enable(int on);
 /* like gsr_profile_enable(1), but records only the listed kernel ids: an event pair costs a few microseconds
- * of GPU idle time per launch, so a timed run should carry events for the kernel under study only. */
+ * of GPU idle time per launch, so a timed run should carry events for the kernel under study only.
+ * The set of recorded ids is one 64-bit word and gsr_kernel_count() is 64: THE WORD IS FULL.  The four covisibility
+ * kernels are timed under the one id "k_visibility"; the next kernel shares an id or widens the word first. */
 int gsr_profile_enable_only(const int* kernel_ids, int n);
 int gsr_profile_read(int max_ids, double* total_ms, int* launches);
 /* diagnostics: number of gsr_forward calls of this process whose instance count reached the host through the
