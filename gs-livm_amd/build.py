@@ -43,7 +43,7 @@ UNITS = {
     "metrics.hip": ["-fno-slp-vectorize"],  # (k_metrics_forward is k_loss_forward's arithmetic: built like loss.hip)
     "api.hip": [],
 }
-HEADERS = [os.path.join(CSRC, "gsr_internal.hpp"), os.path.join(CSRC, "sort_core.hpp"),
+HEADERS = [os.path.join(CSRC, "gsr_internal.hpp"), os.path.join(CSRC, "gsr_api.hpp"), os.path.join(CSRC, "sort_core.hpp"),
            os.path.join(CSRC, "gsr_workgroup.hpp"), os.path.join(CSRC, "gsr_window.hpp"),
            os.path.join(ROOT, "include", "gsraster.h")]
 

@@ -1,6 +1,10 @@
-// api.hip -- the C ABI of libgsraster_hip.so (include/gsraster.h): argument checks, blob carving and
-// stage sequencing.  Restates the ORCHESTRATION of CudaRasterizer::Rasterizer::forward / backward
-// (reference rasterizer_impl.cu:181-342, :346-457); all device work is in the sibling .hip files.
+// api.hip -- the rasterizer's part of the C ABI of libgsraster_hip.so (include/gsraster.h): argument checks, blob
+// carving and stage sequencing of gsr_forward / gsr_backward / gsr_backward_depth / gsr_pose_gradient /
+// gsr_mark_visible, the state views and sizes, the profiler with its kernel-name table, the binning switches, env()
+// and the thread's last error (gsr_api.hpp).  Restates the ORCHESTRATION of CudaRasterizer::Rasterizer::forward /
+// backward (reference rasterizer_impl.cu:181-342, :346-457); its device work is in preprocess.hip, radix_sort.hip and
+// render.hip.  Every other family (optimizer, losses, metrics, growth, prune, densify, covis) keeps its entry points
+// in its own unit, beside its kernels.
 //
 // How a forward is sequenced (gsr_forward; plan_frame picks the kind of frame, enqueue_chain enqueues one chain):
 //   synchronous  (sync_frame: a thread's first, debug, GSR_SYNC_FORWARD)  k_preprocess + depth sort, host waits for
@@ -29,43 +33,24 @@
 #include <unordered_map>
 #include <vector>
 
+#include "gsr_api.hpp"
 #include "gsr_internal.hpp"
 
 using namespace gsr;
 
+// The last error of the calling thread, whichever translation unit's entry point refused (gsr_api.hpp).
 static thread_local char g_err[512] = "";
 
-static int fail(int code, const char* fmt, ...) {
+namespace gsr {
+int fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
 }
-
-// Input checks that several entry points share: GSR_OK, or the error as fail() left it.
-// H W >= limit: the pixel offsets (0x7fffffff) or pixel indices (0x80000000) of a plane are 32-bit.
-static int check_plane(int height, int width, unsigned long long limit) {
-  if ((unsigned long long)height * (unsigned long long)width >= limit)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "image plane too large");
-  return GSR_OK;
-}
-static int check_workspace(size_t workspace_bytes, size_t need) {
-  if (workspace_bytes < need) return fail(GSR_ERR_INVALID_ARGUMENT, "workspace too small: need %zu bytes", need);
-  return GSR_OK;
-}
-static const char* const kMisaligned = "misaligned pointer: float and int32 arrays need 4-byte alignment";
-// bits: the OR of the pointers
-static int check_aligned4(uintptr_t bits) {
-  if (bits & 3u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned);
-  return GSR_OK;
-}
-
-#define HIP_TRY(expr)                                                                            \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess) return fail(GSR_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));       \
-  } while (0)
+void clear_error() { g_err[0] = 0; }
+}  // namespace gsr
 
 // debug != 0: synchronise after the stage so a faulting kernel is reported where it ran
 // (the reference's CHECK_CUDA, auxiliary.h:146-154).
@@ -1565,468 +1550,6 @@ int gsr_mark_visible(int P, const float* means3D, const float* viewmatrix, const
   if (P == 0) return GSR_OK;
   if (!means3D || !viewmatrix || !present) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
   HIP_TRY(launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_activate(int P, int M, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
-                 const float* features_dc, const float* features_rest, float* scales, float* rotations,
-                 float* opacities, float* shs, void* stream_) {
-  g_err[0] = 0;
-  if (P < 0 || M < 1 || M > 16) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/M");
-  if (P == 0) return GSR_OK;
-  if (!scaling_raw || !rotation_raw || !opacity_raw || !features_dc || (M > 1 && !features_rest) || !scales ||
-      !rotations || !opacities || !shs)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  HIP_TRY(launch_activate(P, M, scaling_raw, rotation_raw, opacity_raw, features_dc, features_rest, scales, rotations,
-                          opacities, shs, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_activate_backward(int P, int M, const float* rotation_raw, const float* scales, const float* opacities,
-                          const float* dL_dscales, const float* dL_drotations, const float* dL_dopacities,
-                          const float* dL_dshs, float* dL_dscaling_raw, float* dL_drotation_raw,
-                          float* dL_dopacity_raw, float* dL_dfeatures_dc, float* dL_dfeatures_rest, void* stream_) {
-  g_err[0] = 0;
-  if (P < 0 || M < 1 || M > 16) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/M");
-  if (P == 0) return GSR_OK;
-  if (!rotation_raw || !scales || !opacities || !dL_dscales || !dL_drotations || !dL_dopacities || !dL_dshs ||
-      !dL_dscaling_raw || !dL_drotation_raw || !dL_dopacity_raw || !dL_dfeatures_dc || (M > 1 && !dL_dfeatures_rest))
-    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  HIP_TRY(launch_activate_backward(P, M, rotation_raw, scales, opacities, dL_dscales, dL_drotations, dL_dopacities,
-                                   dL_dshs, dL_dscaling_raw, dL_drotation_raw, dL_dopacity_raw, dL_dfeatures_dc,
-                                   dL_dfeatures_rest, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_adam_step(int n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
-                  float* const* exp_avg_sq, const size_t* numel, const float* lr, double beta1, double beta2, double eps,
-                  int step, int zero_grads, void* stream_) {
-  g_err[0] = 0;
-  if (n_tensors < 0 || n_tensors > 8) return fail(GSR_ERR_INVALID_ARGUMENT, "1..8 tensors per call");
-  if (step < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "step counts from 1");
-  if (n_tensors == 0) return GSR_OK;
-  if (!params || !grads || !exp_avg || !exp_avg_sq || !numel || !lr) return fail(GSR_ERR_INVALID_ARGUMENT, "null array");
-  for (int k = 0; k < n_tensors; k++)
-    if (numel[k] && (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k]))
-      return fail(GSR_ERR_INVALID_ARGUMENT, "null tensor pointer");
-  HIP_TRY(launch_adam(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, step, zero_grads,
-                      (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-size_t gsr_photometric_loss_workspace(int channels, int height, int width) {
-  if (channels <= 0 || height <= 0 || width <= 0) return 0;
-  return loss_workspace_bytes(channels, height, width);
-}
-
-int gsr_photometric_loss(int channels, int height, int width, const float* img, const float* gt,
-                         const float* window11_host, float lambda_dssim, float* loss_out3, float* dL_dimg,
-                         char* workspace, size_t workspace_bytes, void* stream_) {
-  g_err[0] = 0;
-  if (channels <= 0 || height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if (int e = check_plane(height, width, 0x7fffffffull)) return e;  // (32-bit offsets inside a plane)
-  if (!img || !gt || !window11_host || !loss_out3 || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (int e = check_workspace(workspace_bytes, loss_workspace_bytes(channels, height, width))) return e;
-  HIP_TRY(launch_photometric_loss(channels, height, width, img, gt, window11_host, lambda_dssim, loss_out3, dL_dimg,
-                                  workspace, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-size_t gsr_exposure_loss_workspace(int channels, int height, int width) {
-  if (channels <= 0 || height <= 0 || width <= 0 ||
-      (unsigned long long)height * (unsigned long long)width >= 0x7fffffffull)
-    return 0;
-  return exposure_loss_workspace_bytes(channels, height, width);
-}
-
-int gsr_exposure_loss(int channels, int height, int width, const float* img, const float* gt, const float* exposure,
-                      const float* window11_host, float lambda_dssim, float* loss_out3, float* dL_dimg,
-                      float* dL_dexposure, char* workspace, size_t workspace_bytes, void* stream_) {
-  g_err[0] = 0;
-  if (channels <= 0 || height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if (int e = check_plane(height, width, 0x7fffffffull)) return e;  // (32-bit offsets inside a plane)
-  if (!img || !gt || !exposure || !window11_host || !loss_out3 || !workspace)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (!dL_dimg != !dL_dexposure)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "dL_dimg and dL_dexposure: both or neither");
-  if (int e = check_workspace(workspace_bytes, exposure_loss_workspace_bytes(channels, height, width))) return e;
-  HIP_TRY(launch_exposure_loss(channels, height, width, img, gt, exposure, window11_host, lambda_dssim, loss_out3,
-                               dL_dimg, dL_dexposure, workspace, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_apply_exposure(int channels, int height, int width, const float* img, const float* exposure, float* out,
-                       void* stream_) {
-  g_err[0] = 0;
-  if (channels <= 0 || height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if (int e = check_plane(height, width, 0x7fffffffull)) return e;
-  if (!img || !exposure || !out) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (int e = check_aligned4(reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(exposure) |
-                             reinterpret_cast<uintptr_t>(out)))
-    return e;
-  HIP_TRY(launch_apply_exposure(channels, height, width, img, exposure, out, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-size_t gsr_similarity_loss_workspace(int m, int n) {
-  if (m <= 0 || n <= 0 || n > 0x7fffffff - 1024) return 0;
-  return simi_workspace_bytes(m, n);
-}
-
-int gsr_similarity_loss(int P, int m, int n, const float* points, const int* sel, const float* xyz,
-                        const float* scaling, float lambda, float* out3, float* grad_xyz, float* grad_scaling,
-                        int accumulate, char* workspace, size_t workspace_bytes, void* stream_) {
-  g_err[0] = 0;
-  if (P < 0 || m < 0 || n < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/m/n");
-  if (n > P) return fail(GSR_ERR_INVALID_ARGUMENT, "n = %d selected rows of P = %d (the selection is unique)", n, P);
-  if (n > 0x7fffffff - 1024) return fail(GSR_ERR_INVALID_ARGUMENT, "n too large");
-  if (!out3) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (m > 0 && n > 0) {
-    if (!points || !sel || !xyz || !scaling || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-    if (int e = check_workspace(workspace_bytes, simi_workspace_bytes(m, n))) return e;
-  }
-  HIP_TRY(launch_similarity_loss(P, m, n, points, sel, xyz, scaling, lambda, out3, grad_xyz, grad_scaling,
-                                 accumulate ? 1 : 0, workspace, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-size_t gsr_delta_depth_loss_workspace(int height, int width) {
-  if (height < 2 || width < 2 || (unsigned long long)height * (unsigned long long)width >= 0x80000000ull) return 0;
-  return delta_workspace_bytes(height, width);
-}
-
-int gsr_delta_depth_loss(int height, int width, const float* depth_src, const float* acc_src, const float* depth_ref,
-                         const float* acc_ref, const float* inv_K_src9, const float* K_ref9, const float* T_rel12,
-                         float lambda, float* out3, float* warped, float* dL_ddepth_src, float* dL_ddepth_ref,
-                         char* workspace, size_t workspace_bytes, void* stream_) {
-  g_err[0] = 0;
-  if (height < 2 || width < 2)  // (the reference divides by W - 1 and H - 1)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape: at least 2 x 2");
-  if (int e = check_plane(height, width, 0x80000000ull)) return e;  // (32-bit pixel indices)
-  if (!depth_src || !acc_src || !depth_ref || !acc_ref || !inv_K_src9 || !K_ref9 || !T_rel12 || !out3 || !workspace)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (int e = check_workspace(workspace_bytes, delta_workspace_bytes(height, width))) return e;
-  HIP_TRY(launch_delta_depth_loss(height, width, depth_src, acc_src, depth_ref, acc_ref, inv_K_src9, K_ref9, T_rel12,
-                                  lambda, out3, warped, dL_ddepth_src, dL_ddepth_ref, workspace,
-                                  (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_lidar_depth_image(int n, const float* points_world, const float* T_cw12, const float* K9, int height, int width,
-                          float min_depth, float max_depth, float* lidar_depth, int* counts2, void* stream_) {
-  g_err[0] = 0;
-  if (n < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad n");
-  if (height < 1 || width < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if (int e = check_plane(height, width, 0x80000000ull)) return e;  // (32-bit pixel indices)
-  if ((n > 0 && !points_world) || !T_cw12 || !K9 || !lidar_depth) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (!(min_depth >= 0.f && min_depth <= 3.402823466e38f))  // (false for NaN and +inf)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "bad min_depth: finite and >= 0");
-  if (!(max_depth > min_depth)) return fail(GSR_ERR_INVALID_ARGUMENT, "bad max_depth: greater than min_depth");
-  HIP_TRY(launch_lidar_depth_image(n, points_world, T_cw12, K9, height, width, min_depth, max_depth, lidar_depth,
-                                   counts2, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-size_t gsr_lidar_depth_loss_workspace(int height, int width) {
-  if (height < 1 || width < 1 || (unsigned long long)height * (unsigned long long)width >= 0x80000000ull) return 0;
-  return lidar_loss_workspace_bytes(height, width);
-}
-
-int gsr_lidar_depth_loss(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
-                         float acc_min, float lambda, float* out3, float* dL_ddepth, float* dL_dacc, char* workspace,
-                         size_t workspace_bytes, void* stream_) {
-  g_err[0] = 0;
-  if (height < 1 || width < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if (int e = check_plane(height, width, 0x80000000ull)) return e;  // (32-bit pixel indices)
-  if (!depth || !acc || !lidar_depth || !out3 || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (!(acc_min > 0.f && acc_min <= 3.402823466e38f))  // (false for NaN and +inf)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "bad acc_min: finite and > 0");
-  if (int e = check_workspace(workspace_bytes, lidar_loss_workspace_bytes(height, width))) return e;
-  HIP_TRY(launch_lidar_depth_loss(height, width, depth, acc, lidar_depth, acc_min, lambda, out3, dL_ddepth, dL_dacc,
-                                  workspace, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-size_t gsr_image_metrics_workspace(int channels, int height, int width) {
-  if (channels <= 0 || height <= 0 || width <= 0 ||
-      (unsigned long long)height * (unsigned long long)width >= 0x7fffffffull)
-    return 0;
-  return metrics_workspace_bytes(channels, height, width);
-}
-
-int gsr_image_metrics(int channels, int height, int width, const float* img, const float* gt,
-                      const float* window11_host, float* out4, double* totals, char* workspace, size_t workspace_bytes,
-                      void* stream_) {
-  g_err[0] = 0;
-  if (channels <= 0 || height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if (int e = check_plane(height, width, 0x7fffffffull)) return e;  // (32-bit offsets inside a plane)
-  if (!img || !gt || !window11_host || !out4 || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (int e = check_workspace(workspace_bytes, metrics_workspace_bytes(channels, height, width))) return e;
-  HIP_TRY(launch_image_metrics(channels, height, width, img, gt, window11_host, out4, totals, workspace,
-                               (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_pack_image_u8(int height, int width, const float* img3, int bgr, unsigned char* out, size_t pitch_bytes,
-                      void* stream_) {
-  g_err[0] = 0;
-  if (height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if (int e = check_plane(height, width, 0x7fffffffull)) return e;
-  if (!img3 || !out) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (pitch_bytes < 3 * (size_t)width)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: a row has %zu bytes", 3 * (size_t)width);
-  HIP_TRY(launch_pack_image_u8(height, width, img3, bgr, out, pitch_bytes, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_pack_depth_u8(int height, int width, const float* depth, float max_depth, unsigned char* out,
-                      size_t pitch_bytes, void* stream_) {
-  g_err[0] = 0;
-  if (height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
-  if (int e = check_plane(height, width, 0x7fffffffull)) return e;
-  if (!depth || !out) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (pitch_bytes < (size_t)width)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: a row has %zu bytes", (size_t)width);
-  if (!(max_depth > 0.f) || !(max_depth <= 3.402823466e38f))
-    return fail(GSR_ERR_INVALID_ARGUMENT, "max_depth must be positive and finite");
-  HIP_TRY(launch_pack_depth_u8(height, width, depth, max_depth, out, pitch_bytes, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_model_step(int P, int M, float* const* params6, float* const* exp_avg6, float* const* exp_avg_sq6,
-                   const float* dL_dxyz, const float* dL_dscales, const float* dL_drotations, const float* dL_dopacities,
-                   const float* dL_dshs, float* scales_out, float* rotations_out, float* opacities_out, float* shs_out,
-                   const float* lr6, double beta1, double beta2, double eps, int step, void* stream_) {
-  g_err[0] = 0;
-  if (P < 0 || M < 1 || M > 16) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/M");
-  if (step < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "step counts from 1");
-  if (P == 0) return GSR_OK;
-  if (!params6 || !exp_avg6 || !exp_avg_sq6 || !lr6 || !dL_dxyz || !dL_dscales || !dL_drotations || !dL_dopacities ||
-      !dL_dshs)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  for (int k = 0; k < 6; k++)
-    if ((k != 2 || M > 1) && (!params6[k] || !exp_avg6[k] || !exp_avg_sq6[k]))
-      return fail(GSR_ERR_INVALID_ARGUMENT, "null tensor pointer (group %d)", k);
-  HIP_TRY(launch_model_step(P, M, params6, exp_avg6, exp_avg_sq6, dL_dxyz, dL_dscales, dL_drotations, dL_dopacities,
-                            dL_dshs, scales_out, rotations_out, opacities_out, shs_out, lr6, beta1, beta2, eps, step,
-                            (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_init_gaussians(int n, int M, const float* xyz, const float* covs, const float* rgbs, float scale_factor,
-                       float* xyz_out, float* features_dc_out, float* features_rest_out, float* scaling_out,
-                       float* rotation_out, float* opacity_out, void* stream_) {
-  g_err[0] = 0;
-  if (n < 0 || M < 1 || M > 16) return fail(GSR_ERR_INVALID_ARGUMENT, "bad n/M");
-  if (n == 0) return GSR_OK;
-  if (!xyz || !covs || !rgbs || !xyz_out || !features_dc_out || (M > 1 && !features_rest_out) || !scaling_out ||
-      !rotation_out || !opacity_out)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  HIP_TRY(launch_init_gaussians(n, M, xyz, covs, rgbs, scale_factor, xyz_out, features_dc_out, features_rest_out,
-                                scaling_out, rotation_out, opacity_out, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-size_t gsr_ply_row_floats(int M) { return M >= 1 ? (size_t)(14 + 3 * M) : 0; }
-
-int gsr_pack_ply_rows(int P, int M, const float* xyz, const float* features_dc, const float* features_rest,
-                      const float* opacity, const float* scaling, const float* rotation, float* rows, void* stream_) {
-  g_err[0] = 0;
-  if (P < 0 || M < 1 || M > 16) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/M");
-  if (P == 0) return GSR_OK;
-  if (!xyz || !features_dc || (M > 1 && !features_rest) || !opacity || !scaling || !rotation || !rows)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  HIP_TRY(launch_pack_ply_rows(P, M, xyz, features_dc, features_rest, opacity, scaling, rotation, rows,
-                               (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-size_t gsr_prune_workspace(int P) {
-  if (P <= 0 || P > GSR_PRUNE_MAX_ROWS) return 0;
-  return prune_workspace_bytes(P);
-}
-
-int gsr_prune_mark(int P, const float* xyz, const float* scaling_raw, const float* rotation_raw,
-                   const float* opacity_raw, const unsigned char* drop, float min_opacity, float max_scale,
-                   int drop_nonfinite, unsigned char* reasons, int* row_map, int* counts5, char* workspace,
-                   size_t workspace_bytes, void* stream_) {
-  g_err[0] = 0;
-  if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
-  if (!row_map || !counts5) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (P > 0 && (!xyz || !scaling_raw || !rotation_raw || !opacity_raw || !reasons || !workspace))
-    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (int e = check_aligned4((uintptr_t)xyz | (uintptr_t)scaling_raw | (uintptr_t)rotation_raw | (uintptr_t)opacity_raw |
-                             (uintptr_t)row_map | (uintptr_t)counts5 | (uintptr_t)workspace))
-    return e;
-  if (int e = check_workspace(workspace_bytes, prune_workspace_bytes(P))) return e;
-  HIP_TRY(launch_prune_mark(P, xyz, scaling_raw, rotation_raw, opacity_raw, drop, min_opacity, max_scale,
-                            drop_nonfinite ? 1 : 0, reasons, row_map, counts5, workspace, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_prune_compact(int P, int n_tensors, const float* const* src, float* const* dst, const int* widths,
-                      const unsigned char* reasons, const int* row_map, void* stream_) {
-  g_err[0] = 0;
-  if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
-  if (n_tensors < 0 || n_tensors > PRUNE_MAX_TENSORS)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "bad tensor count: at most %d", PRUNE_MAX_TENSORS);
-  if (n_tensors > 0 && !widths) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  for (int k = 0; k < n_tensors; k++)
-    if (widths[k] < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad row width (tensor %d)", k);
-  if (n_tensors > 0 && prune_compact_blocks(P, n_tensors, widths) > 0x7fffffffull)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "model too large for one compaction launch");
-  if (P == 0 || n_tensors == 0) return GSR_OK;
-  if (!src || !dst || !reasons || !row_map) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  for (int k = 0; k < n_tensors; k++)
-    if (widths[k] > 0 && (!src[k] || !dst[k])) return fail(GSR_ERR_INVALID_ARGUMENT, "null tensor pointer (tensor %d)", k);
-  if (int e = check_aligned4((uintptr_t)row_map)) return e;
-  for (int k = 0; k < n_tensors; k++)
-    if (widths[k] > 0 && (((uintptr_t)src[k] | (uintptr_t)dst[k]) & 3u))
-      return fail(GSR_ERR_INVALID_ARGUMENT, "%s (tensor %d)", kMisaligned, k);
-  HIP_TRY(launch_prune_compact(P, n_tensors, src, dst, widths, reasons, row_map, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_density_accumulate(int P, const int* radii, const float* dL_dmean2D, float* stats, void* stream_) {
-  g_err[0] = 0;
-  if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
-  if (P == 0) return GSR_OK;
-  if (!radii || !dL_dmean2D || !stats) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (int e = check_aligned4((uintptr_t)radii | (uintptr_t)dL_dmean2D | (uintptr_t)stats)) return e;
-  HIP_TRY(launch_density_accumulate(P, radii, dL_dmean2D, stats, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-size_t gsr_densify_workspace(int P) {
-  if (P <= 0 || P > GSR_PRUNE_MAX_ROWS) return 0;
-  return densify_workspace_bytes(P);
-}
-
-int gsr_densify_mark(int P, const float* stats, const float* scaling_raw, float grad_threshold, float size_threshold,
-                     int max_new, unsigned char* kinds, int* offsets, int* counts3, char* workspace,
-                     size_t workspace_bytes, void* stream_) {
-  g_err[0] = 0;
-  if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
-  if (!offsets || !counts3) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (P > 0 && (!stats || !scaling_raw || !kinds || !workspace)) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (int e = check_aligned4((uintptr_t)stats | (uintptr_t)scaling_raw | (uintptr_t)offsets | (uintptr_t)counts3 |
-                             (uintptr_t)workspace))
-    return e;
-  if (int e = check_workspace(workspace_bytes, densify_workspace_bytes(P))) return e;
-  HIP_TRY(launch_densify_mark(P, stats, scaling_raw, grad_threshold, size_threshold, max_new, kinds, offsets, counts3,
-                              workspace, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_densify_apply(int P, int M, int n_new, const unsigned char* kinds, const int* offsets, unsigned long long seed,
-                      float* xyz, float* features_dc, float* features_rest, float* scaling_raw, float* rotation_raw,
-                      float* opacity_raw, float* const* exp_avg6, float* const* exp_avg_sq6, float* stats,
-                      void* stream_) {
-  g_err[0] = 0;
-  if (P < 0 || n_new < 0 || (long long)P + (long long)n_new > (long long)GSR_PRUNE_MAX_ROWS)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/n_new");
-  if (M < 1 || M > 16) return fail(GSR_ERR_INVALID_ARGUMENT, "bad M");
-  if (P == 0 || n_new == 0) return GSR_OK;
-  float* const params6[6] = {xyz, features_dc, M > 1 ? features_rest : nullptr, scaling_raw, rotation_raw, opacity_raw};
-  if (!kinds || !offsets) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  for (int k = 0; k < 6; k++) {
-    if (k == 2 && M == 1) continue;  // _features_rest at M = 1: its pointers are not looked at
-    if (!params6[k] || (exp_avg6 && !exp_avg6[k]) || (exp_avg_sq6 && !exp_avg_sq6[k]))
-      return fail(GSR_ERR_INVALID_ARGUMENT, "null tensor pointer (group %d)", k);
-  }
-  uintptr_t bits = (uintptr_t)offsets | (uintptr_t)stats;
-  for (int k = 0; k < 6; k++) {
-    if (k == 2 && M == 1) continue;
-    bits |= (uintptr_t)params6[k] | (uintptr_t)(exp_avg6 ? exp_avg6[k] : nullptr) |
-            (uintptr_t)(exp_avg_sq6 ? exp_avg_sq6[k] : nullptr);
-  }
-  if (int e = check_aligned4(bits)) return e;
-  HIP_TRY(launch_densify_apply(P, M, kinds, offsets, seed, params6, exp_avg6, exp_avg_sq6, stats,
-                               (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-// ---- keyframe covisibility (covis.hip).  The order of the checks is part of the contract (include/gsraster.h): shape,
-// then the choice of sources / outputs, then null pointers, then alignment, then (remap) overlapping slabs.
-static long long vis_need(int P) { return ((long long)P + 63) / 64; }
-static const long long kVisMaxWords = 0x7fffffffLL / 64;  // words * 64 stays an int32
-static const char* const kMisaligned8 = "misaligned pointer: visibility words need 8-byte alignment";
-
-size_t gsr_visibility_words(int P) { return P > 0 ? (size_t)vis_need(P) : 0; }
-
-int gsr_visibility_pack(int P, const int* radii, const unsigned char* mask, unsigned long long* bits, int words,
-                        void* stream_) {
-  g_err[0] = 0;
-  if (P <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
-  if (words < vis_need(P)) return fail(GSR_ERR_INVALID_ARGUMENT, "words too small: need %lld", vis_need(P));
-  if (words > kVisMaxWords) return fail(GSR_ERR_INVALID_ARGUMENT, "words * 64 beyond int32");
-  if ((radii != nullptr) == (mask != nullptr))
-    return fail(GSR_ERR_INVALID_ARGUMENT, "exactly one of radii and mask is given");
-  if (!bits) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if ((uintptr_t)bits & 7u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned8);
-  if (int e = check_aligned4((uintptr_t)radii)) return e;
-  HIP_TRY(launch_visibility_pack(P, radii, mask, bits, words, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_covisibility(int Q, const unsigned long long* q_bits, long long q_pitch, int K,
-                     const unsigned long long* k_bits, long long k_pitch, int words, int* inter, int* q_count,
-                     int* k_count, void* stream_) {
-  g_err[0] = 0;
-  if (Q <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad Q");
-  if (K <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad K");
-  if (words <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad words");
-  if (q_pitch < words || k_pitch < words) return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: need %d", words);
-  if (words > kVisMaxWords) return fail(GSR_ERR_INVALID_ARGUMENT, "words * 64 beyond int32");
-  if ((long long)Q * (long long)K > 0x7fffffffLL) return fail(GSR_ERR_INVALID_ARGUMENT, "Q * K beyond int32");
-  if (visibility_overlap_blocks(Q, words) > 0x7fffffffull)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "problem too large for one overlap launch");
-  if (!q_bits || !k_bits || !inter) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (((uintptr_t)q_bits | (uintptr_t)k_bits) & 7u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned8);
-  if (int e = check_aligned4((uintptr_t)inter | (uintptr_t)q_count | (uintptr_t)k_count)) return e;
-  HIP_TRY(launch_visibility_overlap(Q, q_bits, q_pitch, K, k_bits, k_pitch, words, inter, q_count, k_count,
-                                    (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_observation_count(int K, const unsigned long long* bits, long long pitch, int P, int first_row, int min_count,
-                          int* count, unsigned char* drop, void* stream_) {
-  g_err[0] = 0;
-  if (K <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad K");
-  if (P <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
-  if (pitch < vis_need(P)) return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: need %lld", vis_need(P));
-  if (vis_need(P) > kVisMaxWords) return fail(GSR_ERR_INVALID_ARGUMENT, "words * 64 beyond int32");
-  if (first_row < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad first_row");
-  if (min_count < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad min_count");
-  if (!count && !drop) return fail(GSR_ERR_INVALID_ARGUMENT, "neither count nor drop is asked for");
-  if (!bits) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if ((uintptr_t)bits & 7u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned8);
-  if (int e = check_aligned4((uintptr_t)count)) return e;
-  HIP_TRY(launch_visibility_count(K, bits, pitch, P, first_row, min_count, count, drop, (hipStream_t)stream_));
-  return GSR_OK;
-}
-
-int gsr_visibility_remap(int K, const unsigned long long* src, long long src_pitch, int P, const unsigned char* reasons,
-                         const int* row_map, unsigned long long* dst, long long dst_pitch, int dst_words,
-                         void* stream_) {
-  g_err[0] = 0;
-  if (K <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad K");
-  if (P <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
-  if (dst_words <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad dst_words");
-  if (src_pitch < vis_need(P)) return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: need %lld", vis_need(P));
-  if (dst_pitch < dst_words) return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: need %d", dst_words);
-  if (vis_need(P) > kVisMaxWords || dst_words > kVisMaxWords)
-    return fail(GSR_ERR_INVALID_ARGUMENT, "words * 64 beyond int32");
-  if (!src || !reasons || !row_map || !dst) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
-  if (((uintptr_t)src | (uintptr_t)dst) & 7u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned8);
-  if (int e = check_aligned4((uintptr_t)row_map)) return e;
-  {  // the slabs from their first word to the last word of their last row
-    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + 8u * (uintptr_t)((long long)(K - 1) * src_pitch + vis_need(P));
-    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + 8u * (uintptr_t)((long long)(K - 1) * dst_pitch + dst_words);
-    if (s0 < d1 && d0 < s1) return fail(GSR_ERR_INVALID_ARGUMENT, "src and dst overlap: the remap is out of place");
-  }
-  HIP_TRY(launch_visibility_remap(K, src, src_pitch, P, reasons, row_map, dst, dst_pitch, dst_words,
-                                  (hipStream_t)stream_));
   return GSR_OK;
 }
 

@@ -22,6 +22,7 @@
 //                         __ballot per keyframe makes the word.  Every destination word is stored exactly once, zeros
 //                         beyond P' included: no atomics, no zero fill, nothing out of a row's dst_words words.
 // Plain vector loads and stores only.
+#include "gsr_api.hpp"
 #include "gsr_internal.hpp"
 #include "gsr_workgroup.hpp"
 
@@ -196,52 +197,121 @@ __global__ __launch_bounds__(VIS_BLOCK) void k_visibility_remap(const int K, con
   }
 }
 
-hipError_t launch_visibility_pack(int P, const int* radii, const unsigned char* mask, unsigned long long* bits, int words,
-                                  hipStream_t s) {
-  ProfScope ps(K_VISIBILITY, s);
-  constexpr int per_block = WG_WAVES * PACK_WORDS;
-  hipLaunchKernelGGL(k_visibility_pack, dim3((unsigned)((words + per_block - 1) / per_block)), dim3(VIS_BLOCK), 0, s, P,
-                     radii, mask, bits, words);
-  return hipGetLastError();
-}
-
 // workgroups of the one overlap launch (the entry point refuses a problem that needs more than a grid holds)
-unsigned long long visibility_overlap_blocks(int Q, int words) {
+static unsigned long long visibility_overlap_blocks(int Q, int words) {
   const unsigned long long tiles = ((unsigned long long)Q + OVERLAP_QTILE - 1) / OVERLAP_QTILE;
   const unsigned long long chunks = ((unsigned long long)words + VIS_BLOCK - 1) / VIS_BLOCK;
   return tiles * chunks;
 }
 
-hipError_t launch_visibility_overlap(int Q, const unsigned long long* q_bits, long long q_pitch, int K,
-                                     const unsigned long long* k_bits, long long k_pitch, int words, int* inter,
-                                     int* q_count, int* k_count, hipStream_t s) {
+static long long vis_need(int P) { return ((long long)P + 63) / 64; }
+static const long long kVisMaxWords = 0x7fffffffLL / 64;  // words * 64 stays an int32
+static const char* const kMisaligned8 = "misaligned pointer: visibility words need 8-byte alignment";
+
+}  // namespace gsr
+
+using namespace gsr;
+
+// ---- the entry points.  The order of the checks is part of the contract (include/gsraster.h): shape, then the choice of
+// sources / outputs, then null pointers, then alignment, then (remap) overlapping slabs.
+extern "C" {
+
+size_t gsr_visibility_words(int P) { return P > 0 ? (size_t)vis_need(P) : 0; }
+
+int gsr_visibility_pack(int P, const int* radii, const unsigned char* mask, unsigned long long* bits, int words,
+                        void* stream_) {
+  clear_error();
+  if (P <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (words < vis_need(P)) return fail(GSR_ERR_INVALID_ARGUMENT, "words too small: need %lld", vis_need(P));
+  if (words > kVisMaxWords) return fail(GSR_ERR_INVALID_ARGUMENT, "words * 64 beyond int32");
+  if ((radii != nullptr) == (mask != nullptr))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "exactly one of radii and mask is given");
+  if (!bits) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if ((uintptr_t)bits & 7u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned8);
+  if (int e = check_aligned4((uintptr_t)radii)) return e;
+  hipStream_t s = (hipStream_t)stream_;
   ProfScope ps(K_VISIBILITY, s);
-  hipError_t e = hipMemsetAsync(inter, 0, (size_t)Q * (size_t)K * sizeof(int), s);
-  if (e == hipSuccess && q_count) e = hipMemsetAsync(q_count, 0, (size_t)Q * sizeof(int), s);
-  if (e == hipSuccess && k_count) e = hipMemsetAsync(k_count, 0, (size_t)K * sizeof(int), s);
-  if (e != hipSuccess) return e;
+  constexpr int per_block = WG_WAVES * PACK_WORDS;
+  hipLaunchKernelGGL(k_visibility_pack, dim3((unsigned)((words + per_block - 1) / per_block)), dim3(VIS_BLOCK), 0, s, P,
+                     radii, mask, bits, words);
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
+}
+
+int gsr_covisibility(int Q, const unsigned long long* q_bits, long long q_pitch, int K,
+                     const unsigned long long* k_bits, long long k_pitch, int words, int* inter, int* q_count,
+                     int* k_count, void* stream_) {
+  clear_error();
+  if (Q <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad Q");
+  if (K <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad K");
+  if (words <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad words");
+  if (q_pitch < words || k_pitch < words) return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: need %d", words);
+  if (words > kVisMaxWords) return fail(GSR_ERR_INVALID_ARGUMENT, "words * 64 beyond int32");
+  if ((long long)Q * (long long)K > 0x7fffffffLL) return fail(GSR_ERR_INVALID_ARGUMENT, "Q * K beyond int32");
+  if (visibility_overlap_blocks(Q, words) > 0x7fffffffull)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "problem too large for one overlap launch");
+  if (!q_bits || !k_bits || !inter) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (((uintptr_t)q_bits | (uintptr_t)k_bits) & 7u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned8);
+  if (int e = check_aligned4((uintptr_t)inter | (uintptr_t)q_count | (uintptr_t)k_count)) return e;
+  hipStream_t s = (hipStream_t)stream_;
+  ProfScope ps(K_VISIBILITY, s);
+  HIP_TRY(hipMemsetAsync(inter, 0, (size_t)Q * (size_t)K * sizeof(int), s));
+  if (q_count) HIP_TRY(hipMemsetAsync(q_count, 0, (size_t)Q * sizeof(int), s));
+  if (k_count) HIP_TRY(hipMemsetAsync(k_count, 0, (size_t)K * sizeof(int), s));
   const unsigned chunks = (unsigned)(((unsigned long long)words + VIS_BLOCK - 1) / VIS_BLOCK);
   hipLaunchKernelGGL(k_visibility_overlap, dim3((unsigned)visibility_overlap_blocks(Q, words)), dim3(VIS_BLOCK), 0, s, Q,
                      q_bits, q_pitch, K, k_bits, k_pitch, words, chunks, inter, q_count, k_count);
-  return hipGetLastError();
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
 }
 
-hipError_t launch_visibility_count(int K, const unsigned long long* bits, long long pitch, int P, int first_row,
-                                   int min_count, int* count, unsigned char* drop, hipStream_t s) {
+int gsr_observation_count(int K, const unsigned long long* bits, long long pitch, int P, int first_row, int min_count,
+                          int* count, unsigned char* drop, void* stream_) {
+  clear_error();
+  if (K <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad K");
+  if (P <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (pitch < vis_need(P)) return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: need %lld", vis_need(P));
+  if (vis_need(P) > kVisMaxWords) return fail(GSR_ERR_INVALID_ARGUMENT, "words * 64 beyond int32");
+  if (first_row < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad first_row");
+  if (min_count < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad min_count");
+  if (!count && !drop) return fail(GSR_ERR_INVALID_ARGUMENT, "neither count nor drop is asked for");
+  if (!bits) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if ((uintptr_t)bits & 7u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned8);
+  if (int e = check_aligned4((uintptr_t)count)) return e;
+  hipStream_t s = (hipStream_t)stream_;
   ProfScope ps(K_VISIBILITY, s);
-  const int words = (int)(((long long)P + 63) / 64);
+  const int words = (int)vis_need(P);
   hipLaunchKernelGGL(k_visibility_count, dim3((unsigned)((words + WG_WAVES - 1) / WG_WAVES)), dim3(VIS_BLOCK), 0, s, K,
                      bits, pitch, P, words, first_row, min_count, count, drop);
-  return hipGetLastError();
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
 }
 
-hipError_t launch_visibility_remap(int K, const unsigned long long* src, long long src_pitch, int P,
-                                   const unsigned char* reasons, const int* row_map, unsigned long long* dst,
-                                   long long dst_pitch, int dst_words, hipStream_t s) {
+int gsr_visibility_remap(int K, const unsigned long long* src, long long src_pitch, int P, const unsigned char* reasons,
+                         const int* row_map, unsigned long long* dst, long long dst_pitch, int dst_words,
+                         void* stream_) {
+  clear_error();
+  if (K <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad K");
+  if (P <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (dst_words <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad dst_words");
+  if (src_pitch < vis_need(P)) return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: need %lld", vis_need(P));
+  if (dst_pitch < dst_words) return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: need %d", dst_words);
+  if (vis_need(P) > kVisMaxWords || dst_words > kVisMaxWords)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "words * 64 beyond int32");
+  if (!src || !reasons || !row_map || !dst) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (((uintptr_t)src | (uintptr_t)dst) & 7u) return fail(GSR_ERR_INVALID_ARGUMENT, "%s", kMisaligned8);
+  if (int e = check_aligned4((uintptr_t)row_map)) return e;
+  {  // the slabs from their first word to the last word of their last row
+    const uintptr_t s0 = (uintptr_t)src, s1 = s0 + 8u * (uintptr_t)((long long)(K - 1) * src_pitch + vis_need(P));
+    const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + 8u * (uintptr_t)((long long)(K - 1) * dst_pitch + dst_words);
+    if (s0 < d1 && d0 < s1) return fail(GSR_ERR_INVALID_ARGUMENT, "src and dst overlap: the remap is out of place");
+  }
+  hipStream_t s = (hipStream_t)stream_;
   ProfScope ps(K_VISIBILITY, s);
   hipLaunchKernelGGL(k_visibility_remap, dim3((unsigned)((dst_words + WG_WAVES - 1) / WG_WAVES)), dim3(VIS_BLOCK), 0, s,
                      K, src, src_pitch, P, reasons, row_map, dst, dst_pitch, dst_words);
-  return hipGetLastError();
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
 }
 
-}  // namespace gsr
+}  // extern "C"

@@ -50,6 +50,7 @@
 //                    the workspace; per-workgroup f64 gap sums and mask counts; the maximum of |u|
 //   k_delta_scatter  thread = pixel: the four fixed-point contributions; workgroup 0 sums the partials and writes out3
 //   k_delta_convert  thread = destination pixel: accumulator back to float, times r_z, plus the coordinate term, times c
+#include "gsr_api.hpp"
 #include "gsr_internal.hpp"
 #include "gsr_workgroup.hpp"
 
@@ -256,12 +257,13 @@ __global__ __launch_bounds__(256) void k_delta_convert(const int N, const int W,
   dL_ddepth_src[j] = c * __builtin_fmaf(rz, taps, coord[j]);
 }
 
-size_t delta_workspace_bytes(int H, int W) { return DeltaWorkspace::carve(nullptr, H, W).bytes; }
+static size_t delta_workspace_bytes(int H, int W) { return DeltaWorkspace::carve(nullptr, H, W).bytes; }
 
-hipError_t launch_delta_depth_loss(int H, int W, const float* depth_src, const float* acc_src, const float* depth_ref,
-                                   const float* acc_ref, const float* inv_K_src9, const float* K_ref9,
-                                   const float* T_rel12, float lambda, float* out3, float* warped,
-                                   float* dL_ddepth_src, float* dL_ddepth_ref, char* workspace, hipStream_t s) {
+static hipError_t launch_delta_depth_loss(int H, int W, const float* depth_src, const float* acc_src,
+                                          const float* depth_ref, const float* acc_ref, const float* inv_K_src9,
+                                          const float* K_ref9, const float* T_rel12, float lambda, float* out3,
+                                          float* warped, float* dL_ddepth_src, float* dL_ddepth_ref, char* workspace,
+                                          hipStream_t s) {
   const int N = H * W, nblocks = (N + 255) / 256;
   DeltaCam cam;
   {
@@ -316,3 +318,31 @@ hipError_t launch_delta_depth_loss(int H, int W, const float* depth_src, const f
 }
 
 }  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_delta_depth_loss_workspace(int height, int width) {
+  if (height < 2 || width < 2 || !plane_fits(height, width, 0x80000000ull)) return 0;
+  return delta_workspace_bytes(height, width);
+}
+
+int gsr_delta_depth_loss(int height, int width, const float* depth_src, const float* acc_src, const float* depth_ref,
+                         const float* acc_ref, const float* inv_K_src9, const float* K_ref9, const float* T_rel12,
+                         float lambda, float* out3, float* warped, float* dL_ddepth_src, float* dL_ddepth_ref,
+                         char* workspace, size_t workspace_bytes, void* stream_) {
+  clear_error();
+  if (height < 2 || width < 2)  // (the reference divides by W - 1 and H - 1)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape: at least 2 x 2");
+  if (int e = check_plane(height, width, 0x80000000ull)) return e;  // (32-bit pixel indices)
+  if (!depth_src || !acc_src || !depth_ref || !acc_ref || !inv_K_src9 || !K_ref9 || !T_rel12 || !out3 || !workspace)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (int e = check_workspace(workspace_bytes, delta_workspace_bytes(height, width))) return e;
+  HIP_TRY(launch_delta_depth_loss(height, width, depth_src, acc_src, depth_ref, acc_ref, inv_K_src9, K_ref9, T_rel12,
+                                  lambda, out3, warped, dL_ddepth_src, dL_ddepth_ref, workspace,
+                                  (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+}  // extern "C"

@@ -22,6 +22,7 @@
 // The surgery is in place and race free: a thread reads only its own row i < P, and writes only row i and row
 // P + offsets[i] >= P, which no other thread reads or writes.  The parent of a split becomes its first child in place,
 // so every existing row keeps its number (VoxelIndex needs no remap) and nothing is compacted.
+#include "gsr_api.hpp"
 #include "gsr_internal.hpp"
 #include "gsr_workgroup.hpp"
 
@@ -32,7 +33,7 @@ constexpr float LN_1_6 = 0.47000363f;  // log(0.8 * 2): a child's scale is the p
 
 inline size_t densify_blocks(int P) { return ((size_t)P + DENSIFY_BLOCK - 1) / DENSIFY_BLOCK; }
 // [2][nblocks] int32: [0] candidates per workgroup -> their exclusive scan; [1] splits per workgroup
-size_t densify_workspace_bytes(int P) { return P > 0 ? 2 * densify_blocks(P) * sizeof(int) : 0; }
+static size_t densify_workspace_bytes(int P) { return P > 0 ? 2 * densify_blocks(P) * sizeof(int) : 0; }
 
 __global__ __launch_bounds__(DENSIFY_BLOCK) void k_density_accumulate(const int P, const int* __restrict__ radii,
                                                                       const float* __restrict__ dL_dmean2D,
@@ -211,16 +212,43 @@ __global__ __launch_bounds__(DENSIFY_BLOCK) void k_densify_apply(const DensifyAr
   zero_row(a.stats, dst, 3);
 }
 
-hipError_t launch_density_accumulate(int P, const int* radii, const float* dL_dmean2D, float* stats, hipStream_t s) {
+}  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+int gsr_density_accumulate(int P, const int* radii, const float* dL_dmean2D, float* stats, void* stream_) {
+  clear_error();
+  if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (P == 0) return GSR_OK;
+  if (!radii || !dL_dmean2D || !stats) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (int e = check_aligned4((uintptr_t)radii | (uintptr_t)dL_dmean2D | (uintptr_t)stats)) return e;
+  hipStream_t s = (hipStream_t)stream_;
   ProfScope ps(K_DENSITY_ACCUMULATE, s);
   hipLaunchKernelGGL(k_density_accumulate, dim3((unsigned)densify_blocks(P)), dim3(DENSIFY_BLOCK), 0, s, P, radii,
                      dL_dmean2D, stats);
-  return hipGetLastError();
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
 }
 
-hipError_t launch_densify_mark(int P, const float* stats, const float* scaling_raw, float grad_threshold,
-                               float size_threshold, int max_new, unsigned char* kinds, int* offsets, int* counts3,
-                               char* workspace, hipStream_t s) {
+size_t gsr_densify_workspace(int P) {
+  if (P <= 0 || P > GSR_PRUNE_MAX_ROWS) return 0;
+  return densify_workspace_bytes(P);
+}
+
+int gsr_densify_mark(int P, const float* stats, const float* scaling_raw, float grad_threshold, float size_threshold,
+                     int max_new, unsigned char* kinds, int* offsets, int* counts3, char* workspace,
+                     size_t workspace_bytes, void* stream_) {
+  clear_error();
+  if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (!offsets || !counts3) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (P > 0 && (!stats || !scaling_raw || !kinds || !workspace)) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (int e = check_aligned4((uintptr_t)stats | (uintptr_t)scaling_raw | (uintptr_t)offsets | (uintptr_t)counts3 |
+                             (uintptr_t)workspace))
+    return e;
+  if (int e = check_workspace(workspace_bytes, densify_workspace_bytes(P))) return e;
+  hipStream_t s = (hipStream_t)stream_;
   const int nblocks = (int)densify_blocks(P);
   const int cap = max_new < 0 ? 0x7fffffff : max_new;
   int* totals = reinterpret_cast<int*>(workspace);
@@ -238,12 +266,34 @@ hipError_t launch_densify_mark(int P, const float* stats, const float* scaling_r
     ProfScope ps(K_DENSIFY_RANK, s);
     hipLaunchKernelGGL(k_densify_rank, dim3(nblocks), dim3(DENSIFY_BLOCK), 0, s, P, kinds, totals, cap, offsets);
   }
-  return hipGetLastError();
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
 }
 
-hipError_t launch_densify_apply(int P, int M, const unsigned char* kinds, const int* offsets, unsigned long long seed,
-                                float* const* params6, float* const* exp_avg6, float* const* exp_avg_sq6, float* stats,
-                                hipStream_t s) {
+int gsr_densify_apply(int P, int M, int n_new, const unsigned char* kinds, const int* offsets, unsigned long long seed,
+                      float* xyz, float* features_dc, float* features_rest, float* scaling_raw, float* rotation_raw,
+                      float* opacity_raw, float* const* exp_avg6, float* const* exp_avg_sq6, float* stats,
+                      void* stream_) {
+  clear_error();
+  if (P < 0 || n_new < 0 || (long long)P + (long long)n_new > (long long)GSR_PRUNE_MAX_ROWS)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/n_new");
+  if (M < 1 || M > 16) return fail(GSR_ERR_INVALID_ARGUMENT, "bad M");
+  if (P == 0 || n_new == 0) return GSR_OK;
+  float* const params6[6] = {xyz, features_dc, M > 1 ? features_rest : nullptr, scaling_raw, rotation_raw, opacity_raw};
+  if (!kinds || !offsets) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  for (int k = 0; k < 6; k++) {
+    if (k == 2 && M == 1) continue;  // _features_rest at M = 1: its pointers are not looked at
+    if (!params6[k] || (exp_avg6 && !exp_avg6[k]) || (exp_avg_sq6 && !exp_avg_sq6[k]))
+      return fail(GSR_ERR_INVALID_ARGUMENT, "null tensor pointer (group %d)", k);
+  }
+  uintptr_t bits = (uintptr_t)offsets | (uintptr_t)stats;
+  for (int k = 0; k < 6; k++) {
+    if (k == 2 && M == 1) continue;
+    bits |= (uintptr_t)params6[k] | (uintptr_t)(exp_avg6 ? exp_avg6[k] : nullptr) |
+            (uintptr_t)(exp_avg_sq6 ? exp_avg_sq6[k] : nullptr);
+  }
+  if (int e = check_aligned4(bits)) return e;
+  hipStream_t s = (hipStream_t)stream_;
   DensifyArgs a;
   for (int t = 0; t < 6; t++) {
     const bool has = t != 2 || M > 1;
@@ -255,7 +305,8 @@ hipError_t launch_densify_apply(int P, int M, const unsigned char* kinds, const 
   a.k0 = (uint32_t)seed; a.k1 = (uint32_t)(seed >> 32);
   ProfScope ps(K_DENSIFY_APPLY, s);
   hipLaunchKernelGGL(k_densify_apply, dim3((unsigned)densify_blocks(P)), dim3(DENSIFY_BLOCK), 0, s, a);
-  return hipGetLastError();
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
 }
 
-}  // namespace gsr
+}  // extern "C"

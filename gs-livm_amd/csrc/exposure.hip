@@ -17,6 +17,7 @@
 //                             addresses allow
 // Deterministic: no atomics, fixed-order reductions.  The window passes are gsr_window.hpp's, the float64 sums
 // gsr_workgroup.hpp's; built with loss.hip's flags (build.py).
+#include "gsr_api.hpp"
 #include "gsr_internal.hpp"
 #include "gsr_window.hpp"
 
@@ -239,15 +240,15 @@ static inline size_t exposure_carve(Carver& cv, int C, int H, int W, float** map
   return align_up(cv.off);
 }
 
-size_t exposure_loss_workspace_bytes(int C, int H, int W) {
+static size_t exposure_loss_workspace_bytes(int C, int H, int W) {
   Carver cv(nullptr);
   float *maps[3], *partials;
   return exposure_carve(cv, C, H, W, maps, &partials) + WindowGrid(C, H, W).units * 2 * sizeof(double) + 16;
 }
 
-hipError_t launch_exposure_loss(int C, int H, int W, const float* img, const float* gt, const float* exposure,
-                                const float* window11, float lambda, float* loss_out3, float* dL_dimg,
-                                float* dL_dexposure, char* workspace, hipStream_t s) {
+static hipError_t launch_exposure_loss(int C, int H, int W, const float* img, const float* gt, const float* exposure,
+                                       const float* window11, float lambda, float* loss_out3, float* dL_dimg,
+                                       float* dL_dexposure, char* workspace, hipStream_t s) {
   Carver cv(workspace);
   float *maps[3], *partials;
   const size_t pairs_off = exposure_carve(cv, C, H, W, maps, &partials);
@@ -274,15 +275,52 @@ hipError_t launch_exposure_loss(int C, int H, int W, const float* img, const flo
   return hipGetLastError();
 }
 
-hipError_t launch_apply_exposure(int C, int H, int W, const float* img, const float* exposure, float* out,
-                                 hipStream_t s) {
-  const int n = H * W;  // (H W < 2^31)
+}  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_exposure_loss_workspace(int channels, int height, int width) {
+  if (channels <= 0 || height <= 0 || width <= 0 || !plane_fits(height, width, 0x7fffffffull)) return 0;
+  return exposure_loss_workspace_bytes(channels, height, width);
+}
+
+int gsr_exposure_loss(int channels, int height, int width, const float* img, const float* gt, const float* exposure,
+                      const float* window11_host, float lambda_dssim, float* loss_out3, float* dL_dimg,
+                      float* dL_dexposure, char* workspace, size_t workspace_bytes, void* stream_) {
+  clear_error();
+  if (channels <= 0 || height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if (int e = check_plane(height, width, 0x7fffffffull)) return e;  // (32-bit offsets inside a plane)
+  if (!img || !gt || !exposure || !window11_host || !loss_out3 || !workspace)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (!dL_dimg != !dL_dexposure)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "dL_dimg and dL_dexposure: both or neither");
+  if (int e = check_workspace(workspace_bytes, exposure_loss_workspace_bytes(channels, height, width))) return e;
+  HIP_TRY(launch_exposure_loss(channels, height, width, img, gt, exposure, window11_host, lambda_dssim, loss_out3,
+                               dL_dimg, dL_dexposure, workspace, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+int gsr_apply_exposure(int channels, int height, int width, const float* img, const float* exposure, float* out,
+                       void* stream_) {
+  clear_error();
+  if (channels <= 0 || height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if (int e = check_plane(height, width, 0x7fffffffull)) return e;
+  if (!img || !exposure || !out) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (int e = check_aligned4(reinterpret_cast<uintptr_t>(img) | reinterpret_cast<uintptr_t>(exposure) |
+                             reinterpret_cast<uintptr_t>(out)))
+    return e;
+  hipStream_t s = (hipStream_t)stream_;
+  const int n = height * width;  // (H W < 2^31)
   // 16-byte accesses need img and out at the same phase; then every plane has at most 3 + 3 scalars
   const int vec = ((reinterpret_cast<uintptr_t>(img) ^ reinterpret_cast<uintptr_t>(out)) & 15u) == 0 && n >= 8;
   const unsigned threads = vec ? (unsigned)(n / 4 + 6) : (unsigned)n;
   ProfScope ps(K_APPLY_EXPOSURE, s);
-  hipLaunchKernelGGL(k_apply_exposure, dim3((threads + 255u) / 256u, C), dim3(256), 0, s, n, img, exposure, out, vec);
-  return hipGetLastError();
+  hipLaunchKernelGGL(k_apply_exposure, dim3((threads + 255u) / 256u, channels), dim3(256), 0, s, n, img, exposure, out,
+                     vec);
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
 }
 
-}  // namespace gsr
+}  // extern "C"

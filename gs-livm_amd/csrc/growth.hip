@@ -7,6 +7,7 @@
 //                      export (construct_list_of_attributes :474-492, Save_ply :494-522): one coalesced pass on
 //                      the device and ONE device-to-host copy instead of seven .cpu() copies + a host interleave.
 // gfx950 only; both kernels are pure streaming (HBM-bound).
+#include "gsr_api.hpp"
 #include "gsr_internal.hpp"
 
 namespace gsr {
@@ -65,23 +66,45 @@ __global__ __launch_bounds__(256) void k_pack_ply_rows(const size_t total, const
   rows[e] = v;
 }
 
-hipError_t launch_init_gaussians(int n, int M, const float* xyz, const float* covs, const float* rgbs, float scale_factor,
-                                 float* xyz_out, float* fdc_out, float* frest_out, float* scaling_out,
-                                 float* rotation_out, float* opacity_out, hipStream_t s) {
+}  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+int gsr_init_gaussians(int n, int M, const float* xyz, const float* covs, const float* rgbs, float scale_factor,
+                       float* xyz_out, float* features_dc_out, float* features_rest_out, float* scaling_out,
+                       float* rotation_out, float* opacity_out, void* stream_) {
+  clear_error();
+  if (n < 0 || M < 1 || M > 16) return fail(GSR_ERR_INVALID_ARGUMENT, "bad n/M");
+  if (n == 0) return GSR_OK;
+  if (!xyz || !covs || !rgbs || !xyz_out || !features_dc_out || (M > 1 && !features_rest_out) || !scaling_out ||
+      !rotation_out || !opacity_out)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  hipStream_t s = (hipStream_t)stream_;
   ProfScope ps(K_INIT_GAUSSIANS, s);
   hipLaunchKernelGGL(k_init_gaussians, dim3((n + 255) / 256), dim3(256), 0, s, n, M, xyz, covs, rgbs, scale_factor,
-                     xyz_out, fdc_out, frest_out, scaling_out, rotation_out, opacity_out);
-  return hipGetLastError();
+                     xyz_out, features_dc_out, features_rest_out, scaling_out, rotation_out, opacity_out);
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
 }
 
-hipError_t launch_pack_ply_rows(int P, int M, const float* xyz, const float* fdc, const float* frest,
-                                const float* opacity, const float* scaling, const float* rotation, float* rows,
-                                hipStream_t s) {
+size_t gsr_ply_row_floats(int M) { return M >= 1 ? (size_t)(14 + 3 * M) : 0; }
+
+int gsr_pack_ply_rows(int P, int M, const float* xyz, const float* features_dc, const float* features_rest,
+                      const float* opacity, const float* scaling, const float* rotation, float* rows, void* stream_) {
+  clear_error();
+  if (P < 0 || M < 1 || M > 16) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/M");
+  if (P == 0) return GSR_OK;
+  if (!xyz || !features_dc || (M > 1 && !features_rest) || !opacity || !scaling || !rotation || !rows)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  hipStream_t s = (hipStream_t)stream_;
   const size_t total = (size_t)P * (14 + 3 * M);
   ProfScope ps(K_PACK_PLY, s);
-  hipLaunchKernelGGL(k_pack_ply_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, M, xyz, fdc, frest,
-                     opacity, scaling, rotation, rows);
-  return hipGetLastError();
+  hipLaunchKernelGGL(k_pack_ply_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, total, M, xyz,
+                     features_dc, features_rest, opacity, scaling, rotation, rows);
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
 }
 
-}  // namespace gsr
+}  // extern "C"

@@ -1,5 +1,8 @@
-// gsr_internal.hpp -- state layouts and stage launchers shared by the HIP translation units
-// of libgsraster_hip.so (gfx950 only).  Not part of the public ABI (include/gsraster.h).
+// gsr_internal.hpp -- what the HIP translation units of libgsraster_hip.so (gfx950 only) share: the rasterizer's state
+// layouts, the stage launchers api.hip sequences (preprocess.hip, radix_sort.hip, render.hip), the environment switches,
+// the profiler's kernel ids and ProfScope, and a few device helpers.  The other units (optimizer, losses, metrics, growth,
+// prune, densify, covis) declare nothing here: each holds its own extern "C" entry points beside its kernels (gsr_api.hpp).
+// Not part of the public ABI (include/gsraster.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -429,100 +432,6 @@ hipError_t launch_pose_gradient(const FrameParams& fp, const int* radii, const f
                                 const float* proj, const float* dL_dmean2D, const float* dL_dconic,
                                 const float* dL_ddepths, const float* dL_dmean3D, float* dL_dpose, char* workspace,
                                 hipStream_t s);
-// optimizer.hip ("next" row: fused activations + Adam)
-hipError_t launch_activate(int P, int M, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
-                           const float* f_dc, const float* f_rest, float* scales, float* rotations, float* opacities,
-                           float* shs, hipStream_t s);
-hipError_t launch_activate_backward(int P, int M, const float* rotation_raw, const float* scales,
-                                    const float* opacities, const float* g_scales, const float* g_rot,
-                                    const float* g_opac, const float* g_shs, float* g_scaling_raw,
-                                    float* g_rotation_raw, float* g_opacity_raw, float* g_f_dc, float* g_f_rest,
-                                    hipStream_t s);
-// loss.hip ("next" row: fused L1 + SSIM photometric loss)
-size_t loss_workspace_bytes(int C, int H, int W);
-hipError_t launch_photometric_loss(int C, int H, int W, const float* img, const float* gt, const float* window11,
-                                   float lambda, float* loss_out3, float* dL_dimg, char* workspace, hipStream_t s);
-// exposure.hip (per-keyframe exposure compensation x' = fma(g_c, x, b_c) fused into the photometric loss, with the
-// gradients towards the image and the [C][2] exposure; the workspace may sit at any float-aligned address)
-size_t exposure_loss_workspace_bytes(int C, int H, int W);
-hipError_t launch_exposure_loss(int C, int H, int W, const float* img, const float* gt, const float* exposure,
-                                const float* window11, float lambda, float* loss_out3, float* dL_dimg,
-                                float* dL_dexposure, char* workspace, hipStream_t s);
-hipError_t launch_apply_exposure(int C, int H, int W, const float* img, const float* exposure, float* out,
-                                 hipStream_t s);
-// simi.hip (the LiDAR similarity loss: nearest selected Gaussian per point, one clamp, deterministic gradients)
-size_t simi_workspace_bytes(int m, int n);
-hipError_t launch_similarity_loss(int P, int m, int n, const float* points, const int* sel, const float* xyz,
-                                  const float* scaling, float lambda, float* out3, float* grad_xyz,
-                                  float* grad_scaling, int accumulate, char* workspace, hipStream_t s);
-// delta.hip (the delta-depth loss between a keyframe pair and its gradients towards both depth images; the three small
-// matrices are HOST pointers, composed on the host in double)
-size_t delta_workspace_bytes(int H, int W);
-hipError_t launch_delta_depth_loss(int H, int W, const float* depth_src, const float* acc_src, const float* depth_ref,
-                                   const float* acc_ref, const float* inv_K_src9, const float* K_ref9,
-                                   const float* T_rel12, float lambda, float* out3, float* warped,
-                                   float* dL_ddepth_src, float* dL_ddepth_ref, char* workspace, hipStream_t s);
-// lidar.hip (LiDAR depth supervision: a sweep's z-buffer in a keyframe's view, and the masked depth L1 of a render
-// against it with the gradients towards depth and silhouette; T_cw12 and K9 are HOST pointers, composed in double)
-hipError_t launch_lidar_depth_image(int n, const float* points_world, const float* T_cw12, const float* K9, int H,
-                                    int W, float min_depth, float max_depth, float* lidar_depth, int* counts2,
-                                    hipStream_t s);
-size_t lidar_loss_workspace_bytes(int H, int W);
-hipError_t launch_lidar_depth_loss(int H, int W, const float* depth, const float* acc, const float* lidar_depth,
-                                   float acc_min, float lambda, float* out3, float* dL_ddepth, float* dL_dacc,
-                                   char* workspace, hipStream_t s);
-// metrics.hip (the evaluation pass: PSNR / SSIM / L1 / mse of a render against its ground truth, 8-bit frame export)
-size_t metrics_workspace_bytes(int C, int H, int W);
-hipError_t launch_image_metrics(int C, int H, int W, const float* img, const float* gt, const float* window11,
-                                float* out4, double* totals, char* workspace, hipStream_t s);
-hipError_t launch_pack_image_u8(int H, int W, const float* img3, int bgr, unsigned char* out, size_t pitch,
-                                hipStream_t s);
-hipError_t launch_pack_depth_u8(int H, int W, const float* depth, float max_depth, unsigned char* out, size_t pitch,
-                                hipStream_t s);
-hipError_t launch_init_gaussians(int n, int M, const float* xyz, const float* covs, const float* rgbs, float scale_factor,
-                                 float* xyz_out, float* fdc_out, float* frest_out, float* scaling_out,
-                                 float* rotation_out, float* opacity_out, hipStream_t s);
-hipError_t launch_pack_ply_rows(int P, int M, const float* xyz, const float* fdc, const float* frest,
-                                const float* opacity, const float* scaling, const float* rotation, float* rows,
-                                hipStream_t s);
-hipError_t launch_model_step(int P, int M, float* const* params, float* const* exp_avg, float* const* exp_avg_sq,
-                             const float* g_xyz, const float* g_scales, const float* g_rot, const float* g_opac,
-                             const float* g_shs, float* a_scales, float* a_rot, float* a_opac, float* a_shs,
-                             const float* lr, double beta1, double beta2, double eps, int step, hipStream_t s);
-hipError_t launch_adam(int n, float* const* params, float* const* grads, float* const* exp_avg,
-                       float* const* exp_avg_sq, const size_t* numel, const float* lr, double beta1, double beta2,
-                       double eps, int step, int zero_grads, hipStream_t s);
-// prune.hip (in-place pruning: the drop rule, the stable row map, the out-of-place compaction of up to 18 tensors)
-constexpr int PRUNE_MAX_TENSORS = 18;
-size_t prune_workspace_bytes(int P);
-hipError_t launch_prune_mark(int P, const float* xyz, const float* scaling_raw, const float* rotation_raw,
-                             const float* opacity_raw, const unsigned char* drop, float min_opacity, float max_scale,
-                             int drop_nonfinite, unsigned char* reasons, int* row_map, int* counts5, char* workspace,
-                             hipStream_t s);
-unsigned long long prune_compact_blocks(int P, int n, const int* widths);
-hipError_t launch_prune_compact(int P, int n, const float* const* src, float* const* dst, const int* widths,
-                                const unsigned char* reasons, const int* row_map, hipStream_t s);
-// densify.hip (adaptive density control: the gradient statistics, the clone / split marks, the in-place surgery)
-size_t densify_workspace_bytes(int P);
-hipError_t launch_density_accumulate(int P, const int* radii, const float* dL_dmean2D, float* stats, hipStream_t s);
-hipError_t launch_densify_mark(int P, const float* stats, const float* scaling_raw, float grad_threshold,
-                               float size_threshold, int max_new, unsigned char* kinds, int* offsets, int* counts3,
-                               char* workspace, hipStream_t s);
-hipError_t launch_densify_apply(int P, int M, const unsigned char* kinds, const int* offsets, unsigned long long seed,
-                                float* const* params6, float* const* exp_avg6, float* const* exp_avg_sq6, float* stats,
-                                hipStream_t s);
-// covis.hip (keyframe covisibility: visibility bitsets, their overlap counts, observation counts, the remap after a prune)
-hipError_t launch_visibility_pack(int P, const int* radii, const unsigned char* mask, unsigned long long* bits, int words,
-                                  hipStream_t s);
-unsigned long long visibility_overlap_blocks(int Q, int words);
-hipError_t launch_visibility_overlap(int Q, const unsigned long long* q_bits, long long q_pitch, int K,
-                                     const unsigned long long* k_bits, long long k_pitch, int words, int* inter,
-                                     int* q_count, int* k_count, hipStream_t s);
-hipError_t launch_visibility_count(int K, const unsigned long long* bits, long long pitch, int P, int first_row,
-                                   int min_count, int* count, unsigned char* drop, hipStream_t s);
-hipError_t launch_visibility_remap(int K, const unsigned long long* src, long long src_pitch, int P,
-                                   const unsigned char* reasons, const int* row_map, unsigned long long* dst,
-                                   long long dst_pitch, int dst_words, hipStream_t s);
 
 inline int sort_passes(int end_bit) { return (end_bit + 7) / 8; }
 // digit width: the key bits are split evenly over the passes (13 tile bits -> 7 + 6, 32 depth bits -> 4 x 8)

@@ -32,6 +32,7 @@
 //   k_lidar_loss_grads    thread = pixel: both gradients, every element written
 // Bounds: every thread tests its index against the count; a pixel index comes from coordinates that were tested
 // against +-2^30 and then against the image before the atomic.
+#include "gsr_api.hpp"
 #include "gsr_internal.hpp"
 #include "gsr_workgroup.hpp"
 
@@ -179,9 +180,9 @@ __global__ __launch_bounds__(256) void k_lidar_loss_grads(const int N, const flo
   if (dL_dacc) dL_dacc[i] = ga;
 }
 
-hipError_t launch_lidar_depth_image(int n, const float* points_world, const float* T_cw12, const float* K9, int H,
-                                    int W, float min_depth, float max_depth, float* lidar_depth, int* counts2,
-                                    hipStream_t s) {
+static hipError_t launch_lidar_depth_image(int n, const float* points_world, const float* T_cw12, const float* K9,
+                                           int H, int W, float min_depth, float max_depth, float* lidar_depth,
+                                           int* counts2, hipStream_t s) {
   const int N = H * W, nblocks = (int)(((long long)N + 255) / 256);
   unsigned int* image = reinterpret_cast<unsigned int*>(lidar_depth);
   {
@@ -210,11 +211,11 @@ hipError_t launch_lidar_depth_image(int n, const float* points_world, const floa
   return hipGetLastError();
 }
 
-size_t lidar_loss_workspace_bytes(int H, int W) { return LidarWorkspace::carve(nullptr, H, W).bytes; }
+static size_t lidar_loss_workspace_bytes(int H, int W) { return LidarWorkspace::carve(nullptr, H, W).bytes; }
 
-hipError_t launch_lidar_depth_loss(int H, int W, const float* depth, const float* acc, const float* lidar_depth,
-                                   float acc_min, float lambda, float* out3, float* dL_ddepth, float* dL_dacc,
-                                   char* workspace, hipStream_t s) {
+static hipError_t launch_lidar_depth_loss(int H, int W, const float* depth, const float* acc,
+                                          const float* lidar_depth, float acc_min, float lambda, float* out3,
+                                          float* dL_ddepth, float* dL_dacc, char* workspace, hipStream_t s) {
   const int N = H * W, nblocks = (int)(((long long)N + 255) / 256);
   const LidarWorkspace w = LidarWorkspace::carve(workspace, H, W);
   {
@@ -236,3 +237,44 @@ hipError_t launch_lidar_depth_loss(int H, int W, const float* depth, const float
 }
 
 }  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+int gsr_lidar_depth_image(int n, const float* points_world, const float* T_cw12, const float* K9, int height, int width,
+                          float min_depth, float max_depth, float* lidar_depth, int* counts2, void* stream_) {
+  clear_error();
+  if (n < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad n");
+  if (height < 1 || width < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if (int e = check_plane(height, width, 0x80000000ull)) return e;  // (32-bit pixel indices)
+  if ((n > 0 && !points_world) || !T_cw12 || !K9 || !lidar_depth) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (!(min_depth >= 0.f && min_depth <= 3.402823466e38f))  // (false for NaN and +inf)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "bad min_depth: finite and >= 0");
+  if (!(max_depth > min_depth)) return fail(GSR_ERR_INVALID_ARGUMENT, "bad max_depth: greater than min_depth");
+  HIP_TRY(launch_lidar_depth_image(n, points_world, T_cw12, K9, height, width, min_depth, max_depth, lidar_depth,
+                                   counts2, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+size_t gsr_lidar_depth_loss_workspace(int height, int width) {
+  if (height < 1 || width < 1 || !plane_fits(height, width, 0x80000000ull)) return 0;
+  return lidar_loss_workspace_bytes(height, width);
+}
+
+int gsr_lidar_depth_loss(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
+                         float acc_min, float lambda, float* out3, float* dL_ddepth, float* dL_dacc, char* workspace,
+                         size_t workspace_bytes, void* stream_) {
+  clear_error();
+  if (height < 1 || width < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if (int e = check_plane(height, width, 0x80000000ull)) return e;  // (32-bit pixel indices)
+  if (!depth || !acc || !lidar_depth || !out3 || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (!(acc_min > 0.f && acc_min <= 3.402823466e38f))  // (false for NaN and +inf)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "bad acc_min: finite and > 0");
+  if (int e = check_workspace(workspace_bytes, lidar_loss_workspace_bytes(height, width))) return e;
+  HIP_TRY(launch_lidar_depth_loss(height, width, depth, acc, lidar_depth, acc_min, lambda, out3, dL_ddepth, dL_dacc,
+                                  workspace, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+}  // extern "C"

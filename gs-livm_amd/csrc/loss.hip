@@ -16,6 +16,7 @@
 // loss_utils.cuh:33-37) -- including the reference's own, which is NOT symmetric (gaussian() floors
 // (x - window_size)/2, loss_utils.cuh:24-31), so correlation (forward) and its transpose (backward) are kept
 // apart.  Zero padding of window/2, as conv2d(padding = window_size / 2).
+#include "gsr_api.hpp"
 #include "gsr_internal.hpp"
 #include "gsr_window.hpp"
 
@@ -177,13 +178,14 @@ __global__ __launch_bounds__(256) void k_loss_backward(const int C, const int H,
   }
 }
 
-size_t loss_workspace_bytes(int C, int H, int W) {
+static size_t loss_workspace_bytes(int C, int H, int W) {
   const size_t maps = 3 * align_up((size_t)C * H * W * sizeof(float));
   return maps + align_up(WindowGrid(C, H, W).units * 2 * sizeof(float)) + ALIGN;
 }
 
-hipError_t launch_photometric_loss(int C, int H, int W, const float* img, const float* gt, const float* window11,
-                                   float lambda, float* loss_out3, float* dL_dimg, char* workspace, hipStream_t s) {
+static hipError_t launch_photometric_loss(int C, int H, int W, const float* img, const float* gt,
+                                          const float* window11, float lambda, float* loss_out3, float* dL_dimg,
+                                          char* workspace, hipStream_t s) {
   Carver cv(workspace);
   const size_t n = (size_t)C * H * W;
   float* mapA = cv.take<float>(n);
@@ -212,3 +214,27 @@ hipError_t launch_photometric_loss(int C, int H, int W, const float* img, const 
 }
 
 }  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_photometric_loss_workspace(int channels, int height, int width) {
+  if (channels <= 0 || height <= 0 || width <= 0) return 0;
+  return loss_workspace_bytes(channels, height, width);
+}
+
+int gsr_photometric_loss(int channels, int height, int width, const float* img, const float* gt,
+                         const float* window11_host, float lambda_dssim, float* loss_out3, float* dL_dimg,
+                         char* workspace, size_t workspace_bytes, void* stream_) {
+  clear_error();
+  if (channels <= 0 || height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if (int e = check_plane(height, width, 0x7fffffffull)) return e;  // (32-bit offsets inside a plane)
+  if (!img || !gt || !window11_host || !loss_out3 || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (int e = check_workspace(workspace_bytes, loss_workspace_bytes(channels, height, width))) return e;
+  HIP_TRY(launch_photometric_loss(channels, height, width, img, gt, window11_host, lambda_dssim, loss_out3, dL_dimg,
+                                  workspace, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+}  // extern "C"

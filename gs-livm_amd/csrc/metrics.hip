@@ -17,6 +17,7 @@
 // Deterministic: no atomics, fixed-order reductions.
 #include <math.h>
 
+#include "gsr_api.hpp"
 #include "gsr_internal.hpp"
 #include "gsr_window.hpp"
 
@@ -194,10 +195,12 @@ __global__ __launch_bounds__(256) void k_pack_depth_u8(const int H, const int W,
 }
 
 // the partials only: three floats per work unit, element alignment
-size_t metrics_workspace_bytes(int C, int H, int W) { return WindowGrid(C, H, W).units * MPART_ * sizeof(float); }
+static size_t metrics_workspace_bytes(int C, int H, int W) {
+  return WindowGrid(C, H, W).units * MPART_ * sizeof(float);
+}
 
-hipError_t launch_image_metrics(int C, int H, int W, const float* img, const float* gt, const float* window11,
-                                float* out4, double* totals, char* workspace, hipStream_t s) {
+static hipError_t launch_image_metrics(int C, int H, int W, const float* img, const float* gt, const float* window11,
+                                       float* out4, double* totals, char* workspace, hipStream_t s) {
   float* partials = reinterpret_cast<float*>(workspace);
   const dim3 grid = WindowGrid(C, H, W).grid;
   const Window win(window11);
@@ -214,27 +217,69 @@ hipError_t launch_image_metrics(int C, int H, int W, const float* img, const flo
   return hipGetLastError();
 }
 
-hipError_t launch_pack_image_u8(int H, int W, const float* img3, int bgr, unsigned char* out, size_t pitch,
-                                hipStream_t s) {
-  const int gpr = (W + 3) / 4;
-  const uint32_t ngroups = (uint32_t)((size_t)gpr * H);  // (H W < 2^31)
-  const int vec_in = (reinterpret_cast<uintptr_t>(img3) & 15) == 0 && (W & 3) == 0;
-  ProfScope ps(K_PACK_IMAGE_U8, s);
-  hipLaunchKernelGGL(k_pack_image_u8, dim3((ngroups + 255) / 256), dim3(256), 0, s, H, W, img3, bgr ? 1 : 0, out, pitch,
-                     gpr, ngroups, vec_in);
-  return hipGetLastError();
+}  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_image_metrics_workspace(int channels, int height, int width) {
+  if (channels <= 0 || height <= 0 || width <= 0 || !plane_fits(height, width, 0x7fffffffull)) return 0;
+  return metrics_workspace_bytes(channels, height, width);
 }
 
-hipError_t launch_pack_depth_u8(int H, int W, const float* depth, float max_depth, unsigned char* out, size_t pitch,
-                                hipStream_t s) {
-  const int gpr = (W + 3) / 4;
-  const uint32_t ngroups = (uint32_t)((size_t)gpr * H);
-  const int vec_in = (reinterpret_cast<uintptr_t>(depth) & 15) == 0 && (W & 3) == 0;
+int gsr_image_metrics(int channels, int height, int width, const float* img, const float* gt,
+                      const float* window11_host, float* out4, double* totals, char* workspace, size_t workspace_bytes,
+                      void* stream_) {
+  clear_error();
+  if (channels <= 0 || height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if (int e = check_plane(height, width, 0x7fffffffull)) return e;  // (32-bit offsets inside a plane)
+  if (!img || !gt || !window11_host || !out4 || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (int e = check_workspace(workspace_bytes, metrics_workspace_bytes(channels, height, width))) return e;
+  HIP_TRY(launch_image_metrics(channels, height, width, img, gt, window11_host, out4, totals, workspace,
+                               (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+int gsr_pack_image_u8(int height, int width, const float* img3, int bgr, unsigned char* out, size_t pitch_bytes,
+                      void* stream_) {
+  clear_error();
+  if (height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if (int e = check_plane(height, width, 0x7fffffffull)) return e;
+  if (!img3 || !out) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (pitch_bytes < 3 * (size_t)width)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: a row has %zu bytes", 3 * (size_t)width);
+  hipStream_t s = (hipStream_t)stream_;
+  const int gpr = (width + 3) / 4;
+  const uint32_t ngroups = (uint32_t)((size_t)gpr * height);  // (H W < 2^31)
+  const int vec_in = (reinterpret_cast<uintptr_t>(img3) & 15) == 0 && (width & 3) == 0;
+  ProfScope ps(K_PACK_IMAGE_U8, s);
+  hipLaunchKernelGGL(k_pack_image_u8, dim3((ngroups + 255) / 256), dim3(256), 0, s, height, width, img3, bgr ? 1 : 0,
+                     out, pitch_bytes, gpr, ngroups, vec_in);
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
+}
+
+int gsr_pack_depth_u8(int height, int width, const float* depth, float max_depth, unsigned char* out,
+                      size_t pitch_bytes, void* stream_) {
+  clear_error();
+  if (height <= 0 || width <= 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad image shape");
+  if (int e = check_plane(height, width, 0x7fffffffull)) return e;
+  if (!depth || !out) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (pitch_bytes < (size_t)width)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "pitch too small: a row has %zu bytes", (size_t)width);
+  if (!(max_depth > 0.f) || !(max_depth <= 3.402823466e38f))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "max_depth must be positive and finite");
+  hipStream_t s = (hipStream_t)stream_;
+  const int gpr = (width + 3) / 4;
+  const uint32_t ngroups = (uint32_t)((size_t)gpr * height);
+  const int vec_in = (reinterpret_cast<uintptr_t>(depth) & 15) == 0 && (width & 3) == 0;
   const float scale = 255.0f / max_depth;  // formed in float32, as `depthMap * (255.0f / maxDepth)` (:2155)
   ProfScope ps(K_PACK_DEPTH_U8, s);
-  hipLaunchKernelGGL(k_pack_depth_u8, dim3((ngroups + 255) / 256), dim3(256), 0, s, H, W, depth, scale, out, pitch, gpr,
-                     ngroups, vec_in);
-  return hipGetLastError();
+  hipLaunchKernelGGL(k_pack_depth_u8, dim3((ngroups + 255) / 256), dim3(256), 0, s, height, width, depth, scale, out,
+                     pitch_bytes, gpr, ngroups, vec_in);
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
 }
 
-}  // namespace gsr
+}  // extern "C"

@@ -12,6 +12,8 @@
 //                        (the reference's zero_grad, src/liw/lioOptimization.cpp:1831-1832).
 //
 // All three are pure streaming kernels (HBM-bound): 16-byte accesses where the layout allows.
+// The file ends with their entry points (include/gsraster.h): the argument checks, then the launches.
+#include "gsr_api.hpp"
 #include "gsr_internal.hpp"
 
 namespace gsr {
@@ -391,10 +393,11 @@ __global__ __launch_bounds__(256) void k_sh_step(const StepArgs a) {
   if (4 * n4 + (int)threadIdx.x < n) dst[4 * n4 + threadIdx.x] = sh_buf[4 * n4 + threadIdx.x];
 }
 
-hipError_t launch_model_step(int P, int M, float* const* params, float* const* exp_avg, float* const* exp_avg_sq,
-                             const float* g_xyz, const float* g_scales, const float* g_rot, const float* g_opac,
-                             const float* g_shs, float* a_scales, float* a_rot, float* a_opac, float* a_shs,
-                             const float* lr, double beta1, double beta2, double eps, int step, hipStream_t s) {
+static hipError_t launch_model_step(int P, int M, float* const* params, float* const* exp_avg,
+                                    float* const* exp_avg_sq, const float* g_xyz, const float* g_scales,
+                                    const float* g_rot, const float* g_opac, const float* g_shs, float* a_scales,
+                                    float* a_rot, float* a_opac, float* a_shs, const float* lr, double beta1,
+                                    double beta2, double eps, int step, hipStream_t s) {
   StepArgs a;
   a.P = P; a.M = M;
   a.xyz = params[0]; a.fdc = params[1]; a.frest = params[2]; a.scaling = params[3]; a.rot = params[4]; a.opac = params[5];
@@ -435,32 +438,9 @@ hipError_t launch_model_step(int P, int M, float* const* params, float* const* e
   return hipGetLastError();
 }
 
-hipError_t launch_activate(int P, int M, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
-                           const float* f_dc, const float* f_rest, float* scales, float* rotations, float* opacities,
-                           float* shs, hipStream_t s) {
-  ProfScope ps(K_ACTIVATE, s);
-  hipLaunchKernelGGL(k_activate, dim3((P + 255) / 256), dim3(256), 0, s, P, M, scaling_raw, rotation_raw, opacity_raw,
-                     f_dc, f_rest, scales, rotations, opacities, shs);
-  if (M > 1 && P > 0) launch_sh_move<false>(P, M, shs, const_cast<float*>(f_dc), const_cast<float*>(f_rest), s);
-  return hipGetLastError();
-}
-
-hipError_t launch_activate_backward(int P, int M, const float* rotation_raw, const float* scales,
-                                    const float* opacities, const float* g_scales, const float* g_rot,
-                                    const float* g_opac, const float* g_shs, float* g_scaling_raw,
-                                    float* g_rotation_raw, float* g_opacity_raw, float* g_f_dc, float* g_f_rest,
-                                    hipStream_t s) {
-  ProfScope ps(K_ACTIVATE_BWD, s);
-  hipLaunchKernelGGL(k_activate_backward, dim3((P + 255) / 256), dim3(256), 0, s, P, M, rotation_raw, scales,
-                     opacities, g_scales, g_rot, g_opac, g_shs, g_scaling_raw, g_rotation_raw, g_opacity_raw, g_f_dc,
-                     g_f_rest);
-  if (M > 1 && P > 0) launch_sh_move<true>(P, M, const_cast<float*>(g_shs), g_f_dc, g_f_rest, s);
-  return hipGetLastError();
-}
-
-hipError_t launch_adam(int n, float* const* params, float* const* grads, float* const* exp_avg,
-                       float* const* exp_avg_sq, const size_t* numel, const float* lr, double beta1, double beta2,
-                       double eps, int step, int zero_grads, hipStream_t s) {
+static hipError_t launch_adam(int n, float* const* params, float* const* grads, float* const* exp_avg,
+                              float* const* exp_avg_sq, const size_t* numel, const float* lr, double beta1,
+                              double beta2, double eps, int step, int zero_grads, hipStream_t s) {
   AdamArgs a;
   a.n = n;
   a.beta1 = (float)beta1;
@@ -494,3 +474,83 @@ hipError_t launch_adam(int n, float* const* params, float* const* grads, float* 
 }
 
 }  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+int gsr_activate(int P, int M, const float* scaling_raw, const float* rotation_raw, const float* opacity_raw,
+                 const float* features_dc, const float* features_rest, float* scales, float* rotations,
+                 float* opacities, float* shs, void* stream_) {
+  clear_error();
+  if (P < 0 || M < 1 || M > 16) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/M");
+  if (P == 0) return GSR_OK;
+  if (!scaling_raw || !rotation_raw || !opacity_raw || !features_dc || (M > 1 && !features_rest) || !scales ||
+      !rotations || !opacities || !shs)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  hipStream_t s = (hipStream_t)stream_;
+  ProfScope ps(K_ACTIVATE, s);
+  hipLaunchKernelGGL(k_activate, dim3((P + 255) / 256), dim3(256), 0, s, P, M, scaling_raw, rotation_raw, opacity_raw,
+                     features_dc, features_rest, scales, rotations, opacities, shs);
+  if (M > 1) launch_sh_move<false>(P, M, shs, const_cast<float*>(features_dc), const_cast<float*>(features_rest), s);
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
+}
+
+int gsr_activate_backward(int P, int M, const float* rotation_raw, const float* scales, const float* opacities,
+                          const float* dL_dscales, const float* dL_drotations, const float* dL_dopacities,
+                          const float* dL_dshs, float* dL_dscaling_raw, float* dL_drotation_raw,
+                          float* dL_dopacity_raw, float* dL_dfeatures_dc, float* dL_dfeatures_rest, void* stream_) {
+  clear_error();
+  if (P < 0 || M < 1 || M > 16) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/M");
+  if (P == 0) return GSR_OK;
+  if (!rotation_raw || !scales || !opacities || !dL_dscales || !dL_drotations || !dL_dopacities || !dL_dshs ||
+      !dL_dscaling_raw || !dL_drotation_raw || !dL_dopacity_raw || !dL_dfeatures_dc || (M > 1 && !dL_dfeatures_rest))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  hipStream_t s = (hipStream_t)stream_;
+  ProfScope ps(K_ACTIVATE_BWD, s);
+  hipLaunchKernelGGL(k_activate_backward, dim3((P + 255) / 256), dim3(256), 0, s, P, M, rotation_raw, scales,
+                     opacities, dL_dscales, dL_drotations, dL_dopacities, dL_dshs, dL_dscaling_raw, dL_drotation_raw,
+                     dL_dopacity_raw, dL_dfeatures_dc, dL_dfeatures_rest);
+  if (M > 1) launch_sh_move<true>(P, M, const_cast<float*>(dL_dshs), dL_dfeatures_dc, dL_dfeatures_rest, s);
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
+}
+
+int gsr_adam_step(int n_tensors, float* const* params, float* const* grads, float* const* exp_avg,
+                  float* const* exp_avg_sq, const size_t* numel, const float* lr, double beta1, double beta2, double eps,
+                  int step, int zero_grads, void* stream_) {
+  clear_error();
+  if (n_tensors < 0 || n_tensors > 8) return fail(GSR_ERR_INVALID_ARGUMENT, "1..8 tensors per call");
+  if (step < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "step counts from 1");
+  if (n_tensors == 0) return GSR_OK;
+  if (!params || !grads || !exp_avg || !exp_avg_sq || !numel || !lr) return fail(GSR_ERR_INVALID_ARGUMENT, "null array");
+  for (int k = 0; k < n_tensors; k++)
+    if (numel[k] && (!params[k] || !grads[k] || !exp_avg[k] || !exp_avg_sq[k]))
+      return fail(GSR_ERR_INVALID_ARGUMENT, "null tensor pointer");
+  HIP_TRY(launch_adam(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2, eps, step, zero_grads,
+                      (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+int gsr_model_step(int P, int M, float* const* params6, float* const* exp_avg6, float* const* exp_avg_sq6,
+                   const float* dL_dxyz, const float* dL_dscales, const float* dL_drotations, const float* dL_dopacities,
+                   const float* dL_dshs, float* scales_out, float* rotations_out, float* opacities_out, float* shs_out,
+                   const float* lr6, double beta1, double beta2, double eps, int step, void* stream_) {
+  clear_error();
+  if (P < 0 || M < 1 || M > 16) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/M");
+  if (step < 1) return fail(GSR_ERR_INVALID_ARGUMENT, "step counts from 1");
+  if (P == 0) return GSR_OK;
+  if (!params6 || !exp_avg6 || !exp_avg_sq6 || !lr6 || !dL_dxyz || !dL_dscales || !dL_drotations || !dL_dopacities ||
+      !dL_dshs)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  for (int k = 0; k < 6; k++)
+    if ((k != 2 || M > 1) && (!params6[k] || !exp_avg6[k] || !exp_avg_sq6[k]))
+      return fail(GSR_ERR_INVALID_ARGUMENT, "null tensor pointer (group %d)", k);
+  HIP_TRY(launch_model_step(P, M, params6, exp_avg6, exp_avg_sq6, dL_dxyz, dL_dscales, dL_drotations, dL_dopacities,
+                            dL_dshs, scales_out, rotations_out, opacities_out, shs_out, lr6, beta1, beta2, eps, step,
+                            (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+}  // extern "C"

@@ -18,6 +18,7 @@
 //
 // The compaction is out of place on purpose: an in-place stable compaction races between workgroups (one writes the
 // rows another has yet to read).  Rows [P', ...) of a destination are not written.
+#include "gsr_api.hpp"
 #include "gsr_internal.hpp"
 #include "gsr_workgroup.hpp"
 
@@ -26,13 +27,14 @@ namespace gsr {
 constexpr int PRUNE_BLOCK = WG_THREADS;  // rows per workgroup of k_prune_mark / k_prune_rank (4 waves)
 constexpr int COMPACT_ITEMS = 4;      // floats per thread of k_prune_compact, 256 apart: 1024 consecutive floats per workgroup
 constexpr int COMPACT_TILE = 256 * COMPACT_ITEMS;
+constexpr int PRUNE_MAX_TENSORS = 18;  // tensors one compaction launch moves (CompactArgs)
 
 // reasons[i]: 0 = keep
 constexpr unsigned R_OPACITY = 1u, R_SCALE = 2u, R_NONFINITE = 4u, R_MASK = 8u;
 
 inline size_t prune_blocks(int P) { return ((size_t)P + PRUNE_BLOCK - 1) / PRUNE_BLOCK; }
 // [5][nblocks] int32: [0] kept rows per workgroup -> their exclusive scan; [1..4] rows per workgroup with reason bit 0..3
-size_t prune_workspace_bytes(int P) { return P > 0 ? 5 * prune_blocks(P) * sizeof(int) : 0; }
+static size_t prune_workspace_bytes(int P) { return P > 0 ? 5 * prune_blocks(P) * sizeof(int) : 0; }
 
 // The activated values are those of k_activate / k_model_step bit for bit (same expf, same sigmoidf_), so "dropped for
 // scale" is exactly "k_preprocess' scale cull fires at scale_modifier 1", and the comparisons are the rasterizer's:
@@ -159,38 +161,16 @@ __global__ __launch_bounds__(256) void k_prune_compact(const CompactArgs a) {
     if (keep[k]) dst[out[k]] = v[k];
 }
 
-hipError_t launch_prune_mark(int P, const float* xyz, const float* scaling_raw, const float* rotation_raw,
-                             const float* opacity_raw, const unsigned char* drop, float min_opacity, float max_scale,
-                             int drop_nonfinite, unsigned char* reasons, int* row_map, int* counts5, char* workspace,
-                             hipStream_t s) {
-  const int nblocks = (int)prune_blocks(P);
-  int* totals = reinterpret_cast<int*>(workspace);
-  if (nblocks) {
-    ProfScope ps(K_PRUNE_MARK, s);
-    hipLaunchKernelGGL(k_prune_mark, dim3(nblocks), dim3(PRUNE_BLOCK), 0, s, P, xyz, scaling_raw, rotation_raw,
-                       opacity_raw, drop, min_opacity, max_scale, drop_nonfinite, reasons, totals, nblocks);
-  }
-  {
-    ProfScope ps(K_PRUNE_SCAN, s);
-    hipLaunchKernelGGL(k_prune_scan, dim3(1), dim3(PRUNE_BLOCK), 0, s, totals, nblocks, counts5, row_map + P);
-  }
-  if (nblocks) {
-    ProfScope ps(K_PRUNE_RANK, s);
-    hipLaunchKernelGGL(k_prune_rank, dim3(nblocks), dim3(PRUNE_BLOCK), 0, s, P, reasons, totals, row_map);
-  }
-  return hipGetLastError();
-}
-
 // workgroups of the one compaction launch (the entry point refuses a model that needs more than a grid holds)
-unsigned long long prune_compact_blocks(int P, int n, const int* widths) {
+static unsigned long long prune_compact_blocks(int P, int n, const int* widths) {
   unsigned long long blocks = 0;
   for (int k = 0; k < n; k++)
     if (widths[k] > 0) blocks += ((unsigned long long)P * (unsigned long long)widths[k] + COMPACT_TILE - 1) / COMPACT_TILE;
   return blocks;
 }
 
-hipError_t launch_prune_compact(int P, int n, const float* const* src, float* const* dst, const int* widths,
-                                const unsigned char* reasons, const int* row_map, hipStream_t s) {
+static hipError_t launch_prune_compact(int P, int n, const float* const* src, float* const* dst, const int* widths,
+                                       const unsigned char* reasons, const int* row_map, hipStream_t s) {
   CompactArgs a;
   a.n = 0;
   a.reasons = reasons;
@@ -216,3 +196,70 @@ hipError_t launch_prune_compact(int P, int n, const float* const* src, float* co
 }
 
 }  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_prune_workspace(int P) {
+  if (P <= 0 || P > GSR_PRUNE_MAX_ROWS) return 0;
+  return prune_workspace_bytes(P);
+}
+
+int gsr_prune_mark(int P, const float* xyz, const float* scaling_raw, const float* rotation_raw,
+                   const float* opacity_raw, const unsigned char* drop, float min_opacity, float max_scale,
+                   int drop_nonfinite, unsigned char* reasons, int* row_map, int* counts5, char* workspace,
+                   size_t workspace_bytes, void* stream_) {
+  clear_error();
+  if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (!row_map || !counts5) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (P > 0 && (!xyz || !scaling_raw || !rotation_raw || !opacity_raw || !reasons || !workspace))
+    return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (int e = check_aligned4((uintptr_t)xyz | (uintptr_t)scaling_raw | (uintptr_t)rotation_raw | (uintptr_t)opacity_raw |
+                             (uintptr_t)row_map | (uintptr_t)counts5 | (uintptr_t)workspace))
+    return e;
+  if (int e = check_workspace(workspace_bytes, prune_workspace_bytes(P))) return e;
+  hipStream_t s = (hipStream_t)stream_;
+  const int nblocks = (int)prune_blocks(P);
+  int* totals = reinterpret_cast<int*>(workspace);
+  if (nblocks) {
+    ProfScope ps(K_PRUNE_MARK, s);
+    hipLaunchKernelGGL(k_prune_mark, dim3(nblocks), dim3(PRUNE_BLOCK), 0, s, P, xyz, scaling_raw, rotation_raw,
+                       opacity_raw, drop, min_opacity, max_scale, drop_nonfinite ? 1 : 0, reasons, totals, nblocks);
+  }
+  {
+    ProfScope ps(K_PRUNE_SCAN, s);
+    hipLaunchKernelGGL(k_prune_scan, dim3(1), dim3(PRUNE_BLOCK), 0, s, totals, nblocks, counts5, row_map + P);
+  }
+  if (nblocks) {
+    ProfScope ps(K_PRUNE_RANK, s);
+    hipLaunchKernelGGL(k_prune_rank, dim3(nblocks), dim3(PRUNE_BLOCK), 0, s, P, reasons, totals, row_map);
+  }
+  HIP_TRY(hipGetLastError());
+  return GSR_OK;
+}
+
+int gsr_prune_compact(int P, int n_tensors, const float* const* src, float* const* dst, const int* widths,
+                      const unsigned char* reasons, const int* row_map, void* stream_) {
+  clear_error();
+  if (P < 0 || P > GSR_PRUNE_MAX_ROWS) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P");
+  if (n_tensors < 0 || n_tensors > PRUNE_MAX_TENSORS)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "bad tensor count: at most %d", PRUNE_MAX_TENSORS);
+  if (n_tensors > 0 && !widths) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  for (int k = 0; k < n_tensors; k++)
+    if (widths[k] < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad row width (tensor %d)", k);
+  if (n_tensors > 0 && prune_compact_blocks(P, n_tensors, widths) > 0x7fffffffull)
+    return fail(GSR_ERR_INVALID_ARGUMENT, "model too large for one compaction launch");
+  if (P == 0 || n_tensors == 0) return GSR_OK;
+  if (!src || !dst || !reasons || !row_map) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  for (int k = 0; k < n_tensors; k++)
+    if (widths[k] > 0 && (!src[k] || !dst[k])) return fail(GSR_ERR_INVALID_ARGUMENT, "null tensor pointer (tensor %d)", k);
+  if (int e = check_aligned4((uintptr_t)row_map)) return e;
+  for (int k = 0; k < n_tensors; k++)
+    if (widths[k] > 0 && (((uintptr_t)src[k] | (uintptr_t)dst[k]) & 3u))
+      return fail(GSR_ERR_INVALID_ARGUMENT, "%s (tensor %d)", kMisaligned, k);
+  HIP_TRY(launch_prune_compact(P, n_tensors, src, dst, widths, reasons, row_map, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+}  // extern "C"

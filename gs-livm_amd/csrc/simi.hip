@@ -22,6 +22,7 @@
 // on the caller's stream.  Ties (two centres at bit-equal squared distance) go to the lower position in `sel`; a point
 // at exactly d == r contributes nothing (the reference leaves both undefined).  m and n are bounded by int only: the
 // 500-point cap of the reference (MAX_SIMI, include/gs/gp3d/gp_types.h:15) is the host's policy.
+#include "gsr_api.hpp"
 #include "gsr_internal.hpp"
 #include "gsr_workgroup.hpp"
 
@@ -273,11 +274,11 @@ __global__ void k_simi_zero3(float* __restrict__ out3) {
   if (threadIdx.x < 3) out3[threadIdx.x] = 0.f;
 }
 
-size_t simi_workspace_bytes(int m, int n) { return SimiWorkspace::carve(nullptr, m, n).bytes; }
+static size_t simi_workspace_bytes(int m, int n) { return SimiWorkspace::carve(nullptr, m, n).bytes; }
 
-hipError_t launch_similarity_loss(int P, int m, int n, const float* points, const int* sel, const float* xyz,
-                                  const float* scaling, float lambda, float* out3, float* grad_xyz,
-                                  float* grad_scaling, int accumulate, char* workspace, hipStream_t s) {
+static hipError_t launch_similarity_loss(int P, int m, int n, const float* points, const int* sel, const float* xyz,
+                                         const float* scaling, float lambda, float* out3, float* grad_xyz,
+                                         float* grad_scaling, int accumulate, char* workspace, hipStream_t s) {
   if (m == 0 || n == 0) {  // no term: {0, 0, 0}, no gradient
     ProfScope ps(K_SIMI_GRADS, s);
     hipLaunchKernelGGL(k_simi_zero3, dim3(1), dim3(64), 0, s, out3);
@@ -306,3 +307,31 @@ hipError_t launch_similarity_loss(int P, int m, int n, const float* points, cons
 }
 
 }  // namespace gsr
+
+using namespace gsr;
+
+extern "C" {
+
+size_t gsr_similarity_loss_workspace(int m, int n) {
+  if (m <= 0 || n <= 0 || n > 0x7fffffff - 1024) return 0;
+  return simi_workspace_bytes(m, n);
+}
+
+int gsr_similarity_loss(int P, int m, int n, const float* points, const int* sel, const float* xyz,
+                        const float* scaling, float lambda, float* out3, float* grad_xyz, float* grad_scaling,
+                        int accumulate, char* workspace, size_t workspace_bytes, void* stream_) {
+  clear_error();
+  if (P < 0 || m < 0 || n < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/m/n");
+  if (n > P) return fail(GSR_ERR_INVALID_ARGUMENT, "n = %d selected rows of P = %d (the selection is unique)", n, P);
+  if (n > 0x7fffffff - 1024) return fail(GSR_ERR_INVALID_ARGUMENT, "n too large");
+  if (!out3) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+  if (m > 0 && n > 0) {
+    if (!points || !sel || !xyz || !scaling || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
+    if (int e = check_workspace(workspace_bytes, simi_workspace_bytes(m, n))) return e;
+  }
+  HIP_TRY(launch_similarity_loss(P, m, n, points, sel, xyz, scaling, lambda, out3, grad_xyz, grad_scaling,
+                                 accumulate ? 1 : 0, workspace, (hipStream_t)stream_));
+  return GSR_OK;
+}
+
+}  // extern "C"

@@ -129,3 +129,65 @@ def test_adaptive_near_budget_rule():
     for k in range(64 * 40):                     # (leave the thread's rule as it was found)
         fb(0, 1000, 0)
     assert L.gsr_near_budget_scale() == 256
+
+
+# Refusals and successful calls that return before the device is touched, by the translation unit that holds the entry
+# point.  The pointers are never dereferenced: validation fails, or the empty problem returns, first.
+def _abi_calls():
+    L = G.lib()
+    null = C.c_void_p(None)
+    refuse = {
+        "lidar.hip": (lambda: L.gsr_lidar_depth_loss(0, 4, null, null, null, 0.5, 1.0, null, null, null, null, 0, null),
+                      b"bad image shape"),
+        "covis.hip": (lambda: L.gsr_visibility_pack(1, null, null, null, 0, null), b"words too small: need 1"),
+        "optimizer.hip": (lambda: L.gsr_activate(-1, 1, *([null] * 10)), b"bad P/M"),
+        "densify.hip": (lambda: L.gsr_density_accumulate(-1, null, null, null, null), b"bad P"),
+        "api.hip": (lambda: L.gsr_mark_visible(-3, null, null, null, null, null), b"bad P"),
+    }
+    succeed = {
+        "optimizer.hip": lambda: L.gsr_activate(0, 1, *([null] * 10)),
+        "growth.hip": lambda: L.gsr_init_gaussians(0, 1, null, null, null, 1.0, *([null] * 7)),
+        "densify.hip": lambda: L.gsr_density_accumulate(0, null, null, null, null),
+        "api.hip": lambda: L.gsr_mark_visible(0, null, null, null, null, null),
+    }
+    return L, refuse, succeed
+
+
+def test_last_error_is_one_buffer_per_thread_across_units():
+    """The entry points live in twelve translation units and share ONE thread-local last error (csrc/gsr_api.hpp): a
+    successful call in any unit clears what a refusal in any other unit left, a later refusal replaces an earlier one,
+    and a refusal on another thread neither shows on this thread nor loses its own message."""
+    import threading
+
+    L, refuse, succeed = _abi_calls()
+    assert {"lidar.hip", "covis.hip", "optimizer.hip"} <= set(refuse)
+    for ru, (bad, msg) in refuse.items():
+        for su, good in succeed.items():
+            if su == ru:
+                continue
+            assert bad() == -1 and L.gsr_last_error() == msg, (ru, L.gsr_last_error())
+            assert good() == 0 and L.gsr_last_error() == b"", (ru, su, L.gsr_last_error())
+        for ru2, (bad2, msg2) in refuse.items():  # (the other direction for the units without a no-device success)
+            if ru2 == ru:
+                continue
+            assert bad() == -1 and bad2() == -1 and L.gsr_last_error() == msg2, (ru, ru2, L.gsr_last_error())
+    # the size queries neither set nor clear it
+    bad, msg = refuse["lidar.hip"]
+    assert bad() == -1
+    assert L.gsr_lidar_depth_loss_workspace(0, 4) == 0 and L.gsr_prune_workspace(5) > 0
+    assert L.gsr_last_error() == msg
+
+    seen = {}
+
+    def other():
+        seen["fresh"] = L.gsr_last_error()
+        bad2, _ = refuse["covis.hip"]
+        seen["rc"] = bad2()
+        seen["own"] = L.gsr_last_error()
+
+    t = threading.Thread(target=other)
+    t.start()
+    t.join()
+    assert seen == {"fresh": b"", "rc": -1, "own": refuse["covis.hip"][1]}, seen
+    assert L.gsr_last_error() == msg  # this thread's message is as it was
+    assert succeed["api.hip"]() == 0 and L.gsr_last_error() == b""
