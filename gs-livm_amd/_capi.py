@@ -73,7 +73,8 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_lidar_depth_loss_workspace", "gsr_density_accumulate", "gsr_densify_workspace", "gsr_densify_mark",
            "gsr_densify_apply", "gsr_pose_gradient", "gsr_pose_gradient_workspace", "gsr_exposure_loss",
            "gsr_exposure_loss_workspace", "gsr_apply_exposure", "gsr_visibility_words", "gsr_visibility_pack",
-           "gsr_covisibility", "gsr_observation_count", "gsr_visibility_remap")
+           "gsr_covisibility", "gsr_observation_count", "gsr_visibility_remap", "gsr_contribution_workspace",
+           "gsr_contribution", "gsr_contribution_finish")
 
 
 def lib():
@@ -227,6 +228,12 @@ def lib():
     L.gsr_observation_count.argtypes = [ci, vp, ll, ci, ci, ci, vp, vp, vp]
     L.gsr_visibility_remap.restype = ci
     L.gsr_visibility_remap.argtypes = [ci, vp, ll, ci, vp, vp, vp, ll, ci, vp]
+    L.gsr_contribution_workspace.restype = sz
+    L.gsr_contribution_workspace.argtypes = [ci]
+    L.gsr_contribution.restype = ci
+    L.gsr_contribution.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp]
+    L.gsr_contribution_finish.restype = ci
+    L.gsr_contribution_finish.argtypes = [ci, vp, ci, cf, vp, vp, vp, vp, vp, vp]
     L.gsr_init_gaussians.restype = ci
     L.gsr_init_gaussians.argtypes = [ci, ci, vp, vp, vp, cf] + [vp] * 6 + [vp]
     L.gsr_ply_row_floats.restype = sz
@@ -918,6 +925,34 @@ def prune_compact(src, dst, reasons, row_map):
     arr = lambda ts: VP(*[t.data_ptr() if t.numel() else None for t in ts])  # noqa: E731
     _check(lib().gsr_prune_compact(P, n, arr(src), arr(dst), (C.c_int * max(n, 1))(*widths), _ptr(reasons),
                                    C.c_void_p(row_map.data_ptr()), _stream()))
+
+
+# ---- per-Gaussian blend contribution (include/gsraster.h; csrc/contrib.hip, the walk in csrc/render.hip) ----
+def contribution_rows(P, R, W, H, geomBuffer, binningBuffer, imageBuffer, out=None):
+    """The integer frame rows of a completed forward, the zero fill plus one launch (gsr_contribution): [P, 2] int64 on
+    the device, row i = {wsum_fx, pixels | wmax_bits << 32}.  R: what rasterize_forward returned (its key is used).
+    out: a contiguous int64 device tensor [P, 2] to write instead of a new one."""
+    P = int(P)
+    if out is None:
+        out = torch.empty((P, 2), dtype=torch.int64, device=geomBuffer.device)
+    assert out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() == 2 * P
+    _check(lib().gsr_contribution(P, _key(R), int(W), int(H), _ptr(geomBuffer), _ptr(binningBuffer), _ptr(imageBuffer),
+                                  _ptr(out), _stream()))
+    return out
+
+
+def contribution_finish(rows, min_pixels=1, min_weight=0.0, n_touched=None, weight_sum=None, weight_max=None,
+                        mask=None, stats=None):
+    """One launch over the frame rows (gsr_contribution_finish): writes the given outputs -- n_touched [P] int32,
+    weight_sum / weight_max [P] f32, mask [P] uint8, contiguous device tensors -- and folds the view into
+    stats [P, 3] f32 = {weight_sum_total, views, weight_max} in place; None = not wanted."""
+    P = int(rows.numel()) // 2
+    assert rows.is_cuda and rows.dtype == torch.int64 and rows.is_contiguous()
+    for t, dt, n in ((n_touched, torch.int32, P), (weight_sum, torch.float32, P), (weight_max, torch.float32, P),
+                     (mask, torch.uint8, P), (stats, torch.float32, 3 * P)):
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == n)
+    _check(lib().gsr_contribution_finish(P, _ptr(rows), int(min_pixels), float(min_weight), _ptr(n_touched),
+                                         _ptr(weight_sum), _ptr(weight_max), _ptr(mask), _ptr(stats), _stream()))
 
 
 # ---- adaptive density control (include/gsraster.h; csrc/densify.hip) ----

@@ -38,6 +38,7 @@ UNITS = {
     "lidar.hip": [],
     "prune.hip": [],
     "covis.hip": [],  # (integer arithmetic throughout: no floating-point flag bears on it)
+    "contrib.hip": [],  # (entry points + the finish kernel; the walk is built with render.hip, whose alpha it recomputes)
     # the accumulated gradient norm and the clone / split marks are restated bit for bit in float32 on the host
     "densify.hip": ["-ffp-contract=off"],
     "metrics.hip": ["-fno-slp-vectorize"],  # (k_metrics_forward is k_loss_forward's arithmetic: built like loss.hip)

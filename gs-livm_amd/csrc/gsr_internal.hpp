@@ -416,6 +416,10 @@ hipError_t launch_tile_order(const FrameParams& fp, ImageState im, hipStream_t s
 hipError_t launch_blend_backward(const FrameParams& fp, GeomState g, BinningState b, ImageState im, const float* bg,
                                  const float* dL_dpix, const float* dL_dacc, const float* dL_ddepth, bool have_tile_order,
                                  hipStream_t s);
+// the per-Gaussian blend contribution of a completed forward (render.hip, beside the blend kernels whose alpha it
+// recomputes; entry points in contrib.hip): frame_rows [P] 16-byte rows, zero on entry; reads fp.W, H, gx, gy only
+hipError_t launch_contribution(const FrameParams& fp, GeomState g, BinningState b, ImageState im, char* frame_rows,
+                               hipStream_t s);
 hipError_t launch_gaussian_backward(const FrameParams& fp, GeomState g, BinningState b, const int* radii,
                                     const float* means3D, const float* scales, const float* rotations,
                                     const float* shs, const float* cov3D_precomp, const float* view, const float* proj,

@@ -235,6 +235,20 @@ ObservationCount observation_count(const torch::Tensor& bits, int64_t P, int64_t
 torch::Tensor visibility_remap(const torch::Tensor& src, const torch::Tensor& reasons, const torch::Tensor& row_map,
                                int64_t dst_words = 0);
 
+// ---- per-Gaussian blend contribution (an extension: the reference's rasterizer has no such output) ---------------------
+// Thin tensor-level hosts of gsr_contribution / gsr_contribution_finish; include/gsraster.h has the contract.  geom,
+// binning, img: the three blobs of a completed forward (RasterizeGaussiansCUDA's last three results), R: its first.
+// Returns the integer frame rows, [P, 2] int64 = {wsum_fx, pixels | wmax_bits << 32}.  Nothing waits.
+torch::Tensor contribution(const torch::Tensor& geom, const torch::Tensor& binning, const torch::Tensor& img, int64_t P,
+                           int64_t R, int64_t W, int64_t H);
+struct Contribution {
+  torch::Tensor n_touched, weight_sum, weight_max, mask;  // [P] int32, f32, f32, uint8; undefined when not asked for
+};
+// stats (optional): [P, 3] f32 {weight_sum_total, views, weight_max}, updated in place.
+Contribution contribution_finish(const torch::Tensor& rows, int64_t min_pixels = 1, double min_weight = 0.0,
+                                 bool want_n_touched = true, bool want_weight_sum = true, bool want_weight_max = true,
+                                 bool want_mask = true, const torch::Tensor& stats = torch::Tensor());
+
 // ---- row 4: map growth and PLY export ---------------------------------------------------------------------------
 // The tensor construction of GaussianModel::addNewPointcloud (src/gs/gaussian.cu:241-313) for n new points -- xyz
 // [n,3], covs [n,3,3], rgbs [n,3] in 0..255 -- written IN PLACE into n-row views (normally the tail rows of capacity

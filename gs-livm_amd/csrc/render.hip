@@ -20,7 +20,9 @@
 //   k_gather_records (preprocess.hip) sums a Gaussian's records.  The reference issues 9 global atomicAdds per
 //   (pixel, splat) instead (backward.cu:565, 591-600) and is run-to-run non-deterministic; this path is bitwise
 //   reproducible.
-// Also here: k_live_sat (which tiles the near chain left unfinished), k_release_go (end of an asynchronous far chain).
+// Also here: k_live_sat (which tiles the near chain left unfinished), k_release_go (end of an asynchronous far chain),
+// and k_contribution_tile (gsr_contribution, an extension: per Gaussian, the pixels that blended it and the sum and
+// maximum of alpha T over them -- a forward-order walk that shares the blend kernels' alpha arithmetic and flags).
 #include "gsr_internal.hpp"
 
 namespace gsr {
@@ -900,6 +902,162 @@ __global__ __launch_bounds__(64 * TW, 1) void k_blend_backward_tile(
       }
     }
   }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Per-Gaussian blend contribution (gsr_contribution; an extension: the reference's rasterizer has no such output, MonoGS'
+// has n_touched).  ONE WAVE PER 16x16 TILE, four pixels per lane, no barriers -- the shape and the staging of
+// k_blend_backward_tile, walked FRONT TO BACK: T starts at 1 and is carried as the forward carries it
+// (T <- T (1 - alpha), a subtraction and a multiplication), alpha is recomputed with the forward's own sequence of roundings
+// (splat_power_shared, exp2 on the pre-scaled conic, min(0.99, .)), and a pixel takes the splat at list position pos iff
+// pos < n_contrib[pixel] && !(power > 0) && !(alpha < 1/255): exactly the pairs the forward blended (its termination
+// is the n_contrib cut; a pixel outside the image has n_contrib = 0 here and never counts).
+// Per (tile, entry): the pixel count is the popcount of the four ballots (exact), the weight sum alpha T is added over a
+// lane's four pixels and then over the wave in a fixed order, the largest weight is a wave max; lane 63 parks the three
+// in LDS.  After the sub-chunk lane j adds entry j's results to the Gaussian's frame row with INTEGER atomics -- the count,
+// the sum rounded to units of 2^-32 in 64 bits, the bits of the (non-negative) maximum -- so the rows do not depend on the
+// order the tiles run in, bit for bit; entries no pixel took issue nothing.  (One lane per entry inside the walk would
+// cost a wave-wide atomic instruction per visit.)
+// Reads ranges / rangesB, point_list, splats, n_contrib, quad_last: nothing of the model, no image, no background.
+// ------------------------------------------------------------------------------------------------
+// max over the 64 lanes of a wave of NON-NEGATIVE floats; valid in lane 63 (masked-off DPP sources read 0)
+__device__ __forceinline__ float wave_max_to_hi(float v) {
+  v = fmaxf(v, dpp_full<0xB1>(v));
+  v = fmaxf(v, dpp_full<0x4E>(v));
+  v = fmaxf(v, dpp_full<0x124>(v));
+  v = fmaxf(v, dpp_full<0x128>(v));
+  v = fmaxf(v, dpp_get<0x142, 0xA, 0xF>(v));  // row_bcast:15 into rows 1 and 3
+  v = fmaxf(v, dpp_get<0x143, 0xC, 0xF>(v));  // row_bcast:31 into rows 2 and 3
+  return v;
+}
+
+struct ContribRow {  // one Gaussian's frame row, 16 bytes (include/gsraster.h, gsr_contribution)
+  unsigned long long wsum_fx;  // sum of alpha T, each tile's share rounded to units of 2^-32
+  uint32_t pixels;
+  uint32_t wmax_bits;  // bits of the largest alpha T (>= 0: the order of the bits is the order of the values)
+};
+
+template <int TW>  // TW tiles (= waves) per workgroup; the waves never synchronise
+__global__ __launch_bounds__(64 * TW) void k_contribution_tile(
+    const FrameParams fp, const uint2* __restrict__ ranges, const uint2* __restrict__ rangesB,
+    const uint32_t* __restrict__ quad_last_in, const uint32_t* __restrict__ point_list,
+    const float4* __restrict__ splats, const uint32_t* __restrict__ n_contrib, ContribRow* __restrict__ rows) {
+  __shared__ float4 sE[TW][64][2];  // (x, y, A', B' | C', opacity, -, -) per staged entry
+  __shared__ float sSum[TW][64], sMax[TW][64];
+  __shared__ uint32_t sCnt[TW][64];
+  const int lane = threadIdx.x & 63, wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int tile = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * TW + wq));
+  if (tile >= fp.gx * fp.gy) return;
+  const uint32_t ql0 = quad_last_in[4 * tile], ql1 = quad_last_in[4 * tile + 1], ql2 = quad_last_in[4 * tile + 2],
+                 ql3 = quad_last_in[4 * tile + 3];
+  // entries [0, n) of the tile's list were blended into at least one pixel's prefix
+  const int n = __builtin_amdgcn_readfirstlane((int)max(max(ql0, ql1), max(ql2, ql3)));
+  if (n == 0) return;
+  const int tile_x = tile % fp.gx, tile_y = tile / fp.gx;
+  // the tile's list = its near segment followed by its far segment (near/far frames; (0, 0) otherwise)
+  const uint2 rng = ranges[tile];
+  const uint32_t rbase = rng.x, rbaseB = rangesB[tile].x;
+  const int lenA = (int)(rng.y - rng.x);
+  const int px = tile_x * TILE + (lane & 15);
+  const float pfx = (float)px;
+  const float tx0 = (float)(tile_x * TILE), ty0 = (float)(tile_y * TILE);
+
+  float pfy[4], T[4];
+  int lastc[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int py = tile_y * TILE + 4 * k + (lane >> 4);
+    const bool inside = px < fp.W && py < fp.H;
+    pfy[k] = (float)py;
+    T[k] = 1.0f;
+    lastc[k] = inside ? (int)n_contrib[(size_t)fp.W * py + px] : 0;  // a pixel outside the image never takes a splat
+  }
+
+  float4 a = make_float4(0, 0, 0, 0), b = a;
+  uint32_t eid = 0;
+  bool hit = false;
+  auto gather = [&](const int pos) {
+    hit = false;
+    if (pos < n) {
+      const uint32_t id = pos < lenA ? point_list[rbase + (uint32_t)pos] : point_list[rbaseB + (uint32_t)(pos - lenA)];
+      a = splats[(size_t)id * SPLAT_F4 + 0];
+      b = splats[(size_t)id * SPLAT_F4 + 1];
+      const float4 c = splats[(size_t)id * SPLAT_F4 + 2];
+      eid = id;
+      // footprint box against the tile, then the ellipse itself (hx < 0: never; hx >= 1e6: indefinite conic, no culling)
+      hit = (a.x + c.z >= tx0) && (a.x - c.z <= tx0 + 15.0f) && (a.y + c.w >= ty0) && (a.y - c.w <= ty0 + 15.0f);
+      if (hit && c.z < 1.0e6f)
+        hit = ellipse_reaches_quad<15>(a.x, a.y, a.z, a.w, b.x, footprint_tau(b.y), tx0, ty0);
+    }
+  };
+  gather(lane);
+  for (int base = 0; base < n; base += 64) {
+    constexpr float L2E = 1.4426950408889634f;
+    sE[wq][lane][0] = make_float4(a.x, a.y, a.z * (-0.5f * L2E), a.w * (-L2E));
+    sE[wq][lane][1] = make_float4(b.x * (-0.5f * L2E), b.y, 0.f, 0.f);
+    sCnt[wq][lane] = 0u;  // (an entry the walk does not visit, or that no pixel takes, issues no atomics)
+    const uint32_t my_id = eid;
+    uint64_t m = __ballot(hit);
+    gather(base + 64 + lane);  // the next sub-chunk's gather completes while this one is walked
+    __builtin_amdgcn_wave_barrier();
+    while (m) {
+      const int jj = __builtin_ctzll(m);
+      m &= m - 1;
+      const int pos = base + jj;  // 0-based position in the tile's list: the forward's `last` of this entry is pos + 1
+      const float4 ea = sE[wq][jj][0];
+      const float4 eb = sE[wq][jj][1];
+      const float dx = ea.x - pfx;
+      const float dx2 = dx * dx;
+      const float Adx2 = ea.z * dx2;
+      float wsum = 0.f, wmax = 0.f;
+      uint32_t cnt = 0u;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const float dy = ea.y - pfy[k];
+        const float power = splat_power_shared(Adx2, ea.w, eb.x, dx, dy);  // = log2(e) x the reference's power
+        const float araw = fminf(0.99f, eb.y * __builtin_amdgcn_exp2f(power));
+        const bool ok = (pos < lastc[k]) && !(power > 0.0f) && !(araw < 1.0f / 255.0f);
+        cnt += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(ok));
+        if (ok) {
+          const float w = araw * T[k];
+          wsum += w;
+          wmax = fmaxf(wmax, w);
+          float oma = 1.0f - araw;
+          asm volatile("" : "+v"(oma));  // (no fma(-alpha, T, T): the forward subtracts, then multiplies)
+          T[k] = T[k] * oma;  // the forward's test_T = T (1 - alpha)
+        }
+      }
+      if (cnt != 0u) {  // (uniform over the wave)
+        const float s = wave_sum_to_hi(wsum);
+        const float mx = wave_max_to_hi(wmax);
+        if (lane == 63) {
+          sSum[wq][jj] = s;
+          sMax[wq][jj] = mx;
+          sCnt[wq][jj] = cnt;
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t c = sCnt[wq][lane];
+    if (c != 0u) {  // lane j: the atomics of entry j (my_id < P: the forward's own list)
+      ContribRow* const r = rows + my_id;
+      // <= 256 pixels x 0.99: the product is exact in a double and far below 2^63
+      const unsigned long long fx = (unsigned long long)__double2ll_rn((double)sSum[wq][lane] * 4294967296.0);
+      atomicAdd(&r->wsum_fx, fx);
+      atomicAdd(&r->pixels, c);
+      atomicMax(&r->wmax_bits, __float_as_uint(sMax[wq][lane]));
+    }
+    __builtin_amdgcn_wave_barrier();  // (the next sub-chunk's stores to the LDS image come after these loads)
+  }
+}
+
+hipError_t launch_contribution(const FrameParams& fp, GeomState g, BinningState b, ImageState im, char* frame_rows,
+                               hipStream_t s) {
+  constexpr int TW = 4;
+  const int tiles = fp.gx * fp.gy;
+  hipLaunchKernelGGL(k_contribution_tile<TW>, dim3((tiles + TW - 1) / TW), dim3(64 * TW), 0, s, fp, im.ranges, im.rangesB,
+                     im.quad_last, b.point_list, g.splats, im.n_contrib, reinterpret_cast<ContribRow*>(frame_rows));
+  return hipGetLastError();
 }
 
 // Near/far frames: summed-area table of the tiles that still have an unfinished quad after the near phase, and their

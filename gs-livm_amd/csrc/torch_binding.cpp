@@ -614,6 +614,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("want_drop") = false);
   n.def("visibility_remap", &nx::visibility_remap, py::arg("src"), py::arg("reasons"), py::arg("row_map"),
         py::arg("dst_words") = 0);
+  n.def("contribution", &nx::contribution, py::arg("geom"), py::arg("binning"), py::arg("img"), py::arg("P"), py::arg("R"),
+        py::arg("W"), py::arg("H"));
+  n.def("contribution_finish",
+        [opt](torch::Tensor rows, int64_t min_pixels, double min_weight, bool want_n_touched, bool want_weight_sum,
+              bool want_weight_max, bool want_mask, py::object stats) {
+          const nx::Contribution c = nx::contribution_finish(rows, min_pixels, min_weight, want_n_touched, want_weight_sum,
+                                                             want_weight_max, want_mask, opt(stats));
+          return std::make_tuple(c.n_touched, c.weight_sum, c.weight_max, c.mask);
+        },
+        py::arg("rows"), py::arg("min_pixels") = 1, py::arg("min_weight") = 0.0, py::arg("want_n_touched") = true,
+        py::arg("want_weight_sum") = true, py::arg("want_weight_max") = true, py::arg("want_mask") = true,
+        py::arg("stats") = py::none());
   n.def("init_gaussians", &nx::init_gaussians);
   n.def("pack_ply_rows", &nx::pack_ply_rows);
   n.def("write_ply", &nx::write_ply);

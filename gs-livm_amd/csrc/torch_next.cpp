@@ -765,6 +765,52 @@ torch::Tensor visibility_remap(const torch::Tensor& src, const torch::Tensor& re
   return dst;
 }
 
+torch::Tensor contribution(const torch::Tensor& geom, const torch::Tensor& binning, const torch::Tensor& img, int64_t P,
+                           int64_t R, int64_t W, int64_t H) {
+  torch::NoGradGuard no_grad;
+  const auto int32 = [](int64_t v) { return v >= 0 && v <= 0x7fffffffLL; };
+  if (!int32(P) || !int32(R) || !int32(W) || !int32(H))
+    throw std::invalid_argument("contribution: P, R, W and H are non-negative int32");
+  for (const torch::Tensor* t : {&geom, &binning, &img})
+    if (!t->defined() || !t->is_cuda() || !t->is_contiguous())
+      throw std::invalid_argument("contribution: the forward's three blobs, contiguous on the device");
+  const auto blob = [](const torch::Tensor& t) { return t.numel() ? static_cast<const char*>(t.data_ptr()) : nullptr; };
+  torch::Tensor rows = torch::empty({P, 2}, geom.options().dtype(torch::kInt64));
+  check(gsr_contribution(static_cast<int>(P), static_cast<int>(R), static_cast<int>(W), static_cast<int>(H), blob(geom),
+                         blob(binning), blob(img), P ? static_cast<char*>(rows.data_ptr()) : nullptr, current_stream()),
+        "gsr_contribution");
+  return rows;
+}
+
+Contribution contribution_finish(const torch::Tensor& rows, int64_t min_pixels, double min_weight, bool want_n_touched,
+                                 bool want_weight_sum, bool want_weight_max, bool want_mask, const torch::Tensor& stats) {
+  torch::NoGradGuard no_grad;
+  if (!rows.defined() || !rows.is_cuda() || rows.scalar_type() != torch::kInt64 || !rows.is_contiguous() ||
+      rows.dim() != 2 || rows.size(1) != 2)
+    throw std::invalid_argument("contribution_finish: rows is what contribution returned, [P, 2] int64 on the device");
+  const int64_t P = rows.size(0);
+  if (stats.defined() && (!stats.is_cuda() || stats.scalar_type() != torch::kFloat32 || !stats.is_contiguous() ||
+                          stats.dim() != 2 || stats.size(0) != P || stats.size(1) != 3))
+    throw std::invalid_argument("contribution_finish: stats is a contiguous [P, 3] float32 device tensor");
+  if (min_pixels < -0x7fffffffLL || min_pixels > 0x7fffffffLL)
+    throw std::invalid_argument("contribution_finish: min_pixels is int32");
+  Contribution out;
+  if (want_n_touched) out.n_touched = torch::empty({P}, rows.options().dtype(torch::kInt32));
+  if (want_weight_sum) out.weight_sum = torch::empty({P}, rows.options().dtype(torch::kFloat32));
+  if (want_weight_max) out.weight_max = torch::empty({P}, rows.options().dtype(torch::kFloat32));
+  if (want_mask) out.mask = torch::empty({P}, rows.options().dtype(torch::kByte));
+  if (P == 0) return out;  // (an empty model: empty outputs, nothing to launch)
+  check(gsr_contribution_finish(static_cast<int>(P), static_cast<const char*>(rows.data_ptr()),
+                                static_cast<int>(min_pixels), static_cast<float>(min_weight),
+                                want_n_touched ? out.n_touched.data_ptr<int>() : nullptr,
+                                want_weight_sum ? out.weight_sum.data_ptr<float>() : nullptr,
+                                want_weight_max ? out.weight_max.data_ptr<float>() : nullptr,
+                                want_mask ? out.mask.data_ptr<unsigned char>() : nullptr,
+                                stats.defined() ? stats.data_ptr<float>() : nullptr, current_stream()),
+        "gsr_contribution_finish");
+  return out;
+}
+
 namespace {
 // dst[k][row_map[i]] = src[k][i] where reasons[i] == 0, at most eighteen tensors: one launch
 void compact18(const std::vector<torch::Tensor>& src, const std::vector<torch::Tensor>& dst, const torch::Tensor& reasons,

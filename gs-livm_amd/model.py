@@ -320,6 +320,7 @@ class GrowableGaussians(GaussianParameters):
         self._buf, self._m, self._v = {}, {}, {}
         self._optimizer = None
         self._stats = None  # [capacity, 3] {grad_sum, views, max_radius}: enable_density_stats()
+        self._cstats = None  # [capacity, 3] {weight_sum_total, views, weight_max}: enable_contribution_stats()
         self._visibility = []  # covis.KeyframeVisibility records that follow a prune: attach_visibility()
         self.voxel_index = VoxelIndex(self.device)  # gs_hash_indexes_
         self._reserve(max(1, int(capacity)))
@@ -340,6 +341,10 @@ class GrowableGaussians(GaussianParameters):
             new = torch.zeros((capacity, 3), dtype=torch.float32, device=self.device)
             new[:self.P].copy_(self._stats[:self.P])
             self._stats = new
+        if self._cstats is not None:
+            new = torch.zeros((capacity, 3), dtype=torch.float32, device=self.device)
+            new[:self.P].copy_(self._cstats[:self.P])
+            self._cstats = new
         self.capacity = capacity
 
     def _bind(self):
@@ -442,6 +447,10 @@ class GrowableGaussians(GaussianParameters):
             stats = torch.zeros((self.capacity, 3), dtype=torch.float32, device=self.device)
             _capi.prune_compact([self._stats[:P]], [stats], reasons, row_map)
             self._stats = stats
+        if self._cstats is not None:  # ... and so do the contribution statistics
+            cstats = torch.zeros((self.capacity, 3), dtype=torch.float32, device=self.device)
+            _capi.prune_compact([self._cstats[:P]], [cstats], reasons, row_map)
+            self._cstats = cstats
         self._buf, self._m, self._v = fresh
         self.P = P_new
         self._bind()
@@ -456,6 +465,25 @@ class GrowableGaussians(GaussianParameters):
         fills and densify reads.  A model that never calls this runs none of the density-control code."""
         if self._stats is None:
             self._stats = torch.zeros((self.capacity, 3), dtype=torch.float32, device=self.device)
+
+    @torch.no_grad()
+    def enable_contribution_stats(self):
+        """Creates the zero [capacity, 3] statistics buffer {weight_sum_total, views, weight_max} that
+        contribution(..., stats=model.contribution_stats()) folds a view into (contribution.py).  `prune` compacts it
+        with its rows; rows appended by `densify` and `add_new_pointcloud` start at zero.  A model that never calls this
+        runs none of the contribution code."""
+        if self._cstats is None:
+            self._cstats = torch.zeros((self.capacity, 3), dtype=torch.float32, device=self.device)
+
+    def contribution_stats(self):
+        """The contribution statistics of the P rows, a [P, 3] view (None before enable_contribution_stats)."""
+        return None if self._cstats is None else self._cstats[:self.P]
+
+    @torch.no_grad()
+    def reset_contribution_stats(self):
+        """Zeroes the contribution statistics (the start of a new sweep over the keyframes)."""
+        if self._cstats is not None:
+            self._cstats.zero_()
 
     def density_stats(self):
         """The statistics of the P rows, a [P, 3] view (None before enable_density_stats)."""

@@ -756,6 +756,55 @@ int gsr_visibility_remap(int K, const unsigned long long* src, long long src_pit
                          const unsigned char* reasons, const int* row_map, unsigned long long* dst, long long dst_pitch,
                          int dst_words, void* stream);
 
+/* ---- per-Gaussian blend contribution: pixels, weight sum, largest weight (an extension) ----
+ * radii > 0 says that a Gaussian is in the frustum, not scale-culled and non-degenerate; it does not say that the
+ * Gaussian put anything into a pixel (a splat behind a wall of opaque ones has radii > 0 and contributes nothing).
+ * MonoGS builds covisibility and pruning on n_touched, the number of pixels a Gaussian contributed to; the reference's
+ * rasterizer has no such output.  This is a forward-only pass behind gsr_forward over the three blobs that forward left
+ * (it reads the tile ranges of both segments, point_list, the splat records, n_contrib and quad_last: no model tensor,
+ * no image, no background), so it works for one-chain and near/far frames and in both binning modes: the blobs carry
+ * the mode.  It is off unless called.
+ *
+ * A pixel TAKES the splat at position pos of its tile's list iff pos < n_contrib[pixel] (the forward's own termination
+ * cut), power <= 0 and alpha = min(0.99, opacity exp(power)) >= 1/255, with alpha recomputed by the blend's own device
+ * functions: exactly the (pixel, splat) pairs the forward blended.  Pixels outside the image never count.  Per
+ * Gaussian, over the pixels that take it:
+ *   n_touched   the number of those pixels;
+ *   weight_sum  sum of alpha T, T = the transmittance in front of the splat, carried front to back from 1 as the
+ *               forward carries it (the Gaussian's share of out_acc: the sums of all rows add up to sum out_acc);
+ *   weight_max  max of alpha T.
+ *
+ * gsr_contribution (the zero fill of frame_rows on the stream plus ONE launch; P, R, width, height as gsr_backward takes
+ * them, R = what gsr_forward returned) writes frame_rows, P rows of 16 bytes {u64 wsum_fx, u32 pixels, u32 wmax_bits}:
+ * a tile's weight sum is added over the tile's pixels in a fixed order in float32, rounded to units of 2^-32 and added
+ * to wsum_fx with a 64-bit integer atomic; the count with a 32-bit integer atomic; the maximum with an integer atomic
+ * max on the bits of the non-negative float.  The rows are therefore bitwise reproducible and independent of the order
+ * the tiles run in.  One frame cannot overflow them (pixels <= width * height < 2^31, wsum_fx < width * height * 2^32).
+ * P == 0 and R == 0 are legal: nothing is launched and (R == 0) the rows are zero; with R == 0 the blobs are not read
+ * and may be NULL.  gsr_contribution_workspace(P) = 16 * P bytes, 0 for P <= 0.
+ *
+ * gsr_contribution_finish (ONE launch, one thread per row) turns the rows into the outputs, each nullable:
+ *   n_touched [P] int32; weight_sum [P] f32 = (float)((double)wsum_fx * 2^-32); weight_max [P] f32;
+ *   mask [P] bytes = (n_touched >= min_pixels && weight_max >= min_weight) ? 1 : 0 -- what gsr_visibility_pack takes
+ *   as `mask`;
+ *   stats [P][3] f32 = {weight_sum_total, views, weight_max}, UPDATED in place: [0] += weight_sum, [1] += 1 where
+ *   n_touched > 0, [2] = max([2], weight_max) -- all floats, so that gsr_prune_compact moves the rows as one tensor of
+ *   width 3, the convention of the density statistics.
+ * Every element of every requested output is written, rows with radii <= 0 included: no tile lists them, they read 0.
+ *
+ * Refused (GSR_ERR_INVALID_ARGUMENT with a gsr_last_error text, nothing enqueued or written), IN THIS ORDER:
+ *   1. shape: a negative P or R, width or height not positive, width * height >= 2^31; a negative min_pixels, a
+ *      min_weight that is negative or NaN;
+ *   2. gsr_contribution_finish: none of the five outputs is asked for;
+ *   3. a null required pointer (P > 0: frame_rows; R > 0 as well: the three blobs);
+ *   4. a misaligned pointer: frame_rows 8 bytes, then the int32 / float arrays 4 bytes (mask: any address).
+ * No host synchronisation, no allocation, the caller's stream only.  Timed under the profiler id "k_visibility". */
+size_t gsr_contribution_workspace(int P);
+int gsr_contribution(int P, int R, int width, int height, const char* geom_buffer, const char* binning_buffer,
+                     const char* image_buffer, char* frame_rows, void* stream);
+int gsr_contribution_finish(int P, const char* frame_rows, int min_pixels, float min_weight, int* n_touched,
+                            float* weight_sum, float* weight_max, unsigned char* mask, float* stats, void* stream);
+
 /* Optional per-kernel device timing (hipEvent pairs recorded on the launch stream around every
  * kernel launch while enabled).  Measurement aid for bench.py's roofline line; the reference has only
  * host wall-clock timers (include/common/timer/timer.h:36-52).  Not thread-safe; off by default.
