@@ -74,7 +74,7 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_densify_apply", "gsr_pose_gradient", "gsr_pose_gradient_workspace", "gsr_exposure_loss",
            "gsr_exposure_loss_workspace", "gsr_apply_exposure", "gsr_visibility_words", "gsr_visibility_pack",
            "gsr_covisibility", "gsr_observation_count", "gsr_visibility_remap", "gsr_contribution_workspace",
-           "gsr_contribution", "gsr_contribution_finish")
+           "gsr_contribution", "gsr_contribution_finish", "gsr_weighted_loss", "gsr_weighted_loss_workspace")
 
 
 def lib():
@@ -178,6 +178,10 @@ def lib():
     L.gsr_exposure_loss_workspace.argtypes = [ci, ci, ci]
     L.gsr_exposure_loss.restype = ci
     L.gsr_exposure_loss.argtypes = [ci, ci, ci, vp, vp, vp, C.POINTER(cf), cf, vp, vp, vp, vp, sz, vp]
+    L.gsr_weighted_loss_workspace.restype = sz
+    L.gsr_weighted_loss_workspace.argtypes = [ci, ci, ci]
+    L.gsr_weighted_loss.restype = ci
+    L.gsr_weighted_loss.argtypes = [ci, ci, ci, vp, vp, vp, vp, cf, vp, C.POINTER(cf), cf, vp, vp, vp, vp, sz, vp]
     L.gsr_apply_exposure.restype = ci
     L.gsr_apply_exposure.argtypes = [ci, ci, ci, vp, vp, vp, vp]
     L.gsr_similarity_loss_workspace.restype = sz
@@ -669,6 +673,37 @@ def exposure_loss(img, gt, exposure, window11, lambda_dssim, want_grad=True):
     _check(lib().gsr_exposure_loss(Cn, H, W, _ptr(img), _ptr(gt), _ptr(exposure), win, float(lambda_dssim), _ptr(out3),
                                    _ptr(grad), _ptr(grad_e), _ptr(ws), nbytes, _stream()))
     return out3, grad, grad_e
+
+
+def weighted_loss(img, gt, weights, acc, acc_min, exposure, window11, lambda_dssim, want_grad=True, out=None):
+    """The photometric loss under per-pixel weights w = weights * [acc >= acc_min], normalised by their sum
+    (include/gsraster.h, gsr_weighted_loss).  weights, acc: [H,W] f32 on the device or None; exposure: [C,2] or None.
+    out: a contiguous device f32 [6] to write, or None.  Returns (out6 = [loss, l1, ssim, S, mse, psnr] device tensor,
+    dL_dimg or None, dL_dexposure [C,2] or None)."""
+    assert img.dim() == 3 and img.shape == gt.shape and img.is_cuda and img.dtype == torch.float32 == gt.dtype
+    Cn, H, W = (int(x) for x in img.shape)
+    img, gt = img.contiguous(), gt.contiguous()
+    planes = []
+    for t in (weights, acc):
+        if t is not None:
+            assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (H, W), "weights / acc: [H,W] float32"
+            t = t.contiguous()
+        planes.append(t)
+    if exposure is not None:
+        assert exposure.is_cuda and exposure.dtype == torch.float32 and tuple(exposure.shape) == (Cn, 2)
+        exposure = exposure.contiguous()
+    nbytes = int(lib().gsr_weighted_loss_workspace(Cn, H, W))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=img.device)
+    if out is None:
+        out = torch.empty(6, dtype=torch.float32, device=img.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.numel() == 6 and out.is_contiguous()
+    grad = torch.empty_like(img) if want_grad else None
+    grad_e = torch.empty_like(exposure) if want_grad and exposure is not None else None
+    win = (C.c_float * 11)(*[float(x) for x in window11])
+    _check(lib().gsr_weighted_loss(Cn, H, W, _ptr(img), _ptr(gt), _ptr(planes[0]), _ptr(planes[1]), float(acc_min),
+                                   _ptr(exposure), win, float(lambda_dssim), _ptr(out), _ptr(grad), _ptr(grad_e),
+                                   _ptr(ws), nbytes, _stream()))
+    return out, grad, grad_e
 
 
 def apply_exposure(img, exposure, out=None):

@@ -32,6 +32,7 @@ UNITS = {
     "optimizer.hip": [],
     "loss.hip": ["-fno-slp-vectorize"],  # (packing the 11-tap sums costs more moves than it saves: 944 -> 732 VALU in the backward)
     "exposure.hip": ["-fno-slp-vectorize"],  # (the loss kernels' arithmetic on the compensated image: built like loss.hip)
+    "weighted.hip": ["-fno-slp-vectorize"],  # (the exposure loss's arithmetic under per-pixel weights: built like loss.hip)
     "growth.hip": [],
     "simi.hip": [],
     "delta.hip": [],

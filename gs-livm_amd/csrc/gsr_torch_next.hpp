@@ -48,6 +48,27 @@ torch::Tensor exposure_photometric_loss(const torch::Tensor& image, const torch:
 torch::Tensor apply_exposure(const torch::Tensor& image, const torch::Tensor& exposure,
                              const torch::Tensor& out = torch::Tensor());
 
+// ---- the weighted photometric loss (an extension; csrc/weighted.hip) -------------------------------------------------
+// photometric_loss / exposure_photometric_loss over the pixels that carry a measurement, as ONE autograd node:
+// w = weights * [acc >= acc_min], L1, SSIM and the squared error weighted per pixel and divided by the weight sum.
+// weights (finite, >= 0: an undistortion border, a sky or dynamic-object mask) and acc (e.g. the render's silhouette;
+// detached, the gate has no gradient): [H,W] or [1,H,W] f32 on the device, undefined = absent.  exposure: as in
+// exposure_photometric_loss, undefined = none.  The SSIM windows see the whole images: a zero weight does not shield a
+// non-finite pixel from its neighbours.  Gradients w.r.t. image and exposure.  Returns the 0-dim loss.
+// (Like image_metrics, these two are not part of the oracle/ref_link link check, which stays as it is.)
+torch::Tensor weighted_photometric_loss(const torch::Tensor& image, const torch::Tensor& gt,
+                                        const torch::Tensor& weights = torch::Tensor(),
+                                        const torch::Tensor& acc = torch::Tensor(), float acc_min = 0.5f,
+                                        const torch::Tensor& exposure = torch::Tensor(), float lambda_dssim = 0.2f,
+                                        const torch::Tensor& window1d = torch::Tensor(), bool log_gain = false);
+// [loss, l1, ssim, weight sum, mse, psnr] of the same evaluation, no graph
+torch::Tensor weighted_photometric_loss_parts(const torch::Tensor& image, const torch::Tensor& gt,
+                                              const torch::Tensor& weights = torch::Tensor(),
+                                              const torch::Tensor& acc = torch::Tensor(), float acc_min = 0.5f,
+                                              const torch::Tensor& exposure = torch::Tensor(),
+                                              float lambda_dssim = 0.2f,
+                                              const torch::Tensor& window1d = torch::Tensor(), bool log_gain = false);
+
 // ---- the LiDAR similarity loss (optimize_vis step 3) ---------------------------------------------------------------
 // lambda * compute_min_distance(points, Get_xyz()[sel], Get_scaling()[sel]) (src/gs/gaussian.cu:87-114, 230-237) as ONE
 // autograd node on the kernels of csrc/simi.hip: points [m,3] f32 and sel [n] int32 (ascending unique rows) on the
@@ -90,9 +111,12 @@ torch::Tensor lidar_depth_loss(const torch::Tensor& depth, const torch::Tensor& 
 // channel is identical) and ::ssim (:43-70) of :2203-2207 in two launches.  totals: a device float64 [4] that
 // {psnr, ssim, l1, 1} is added to -- psnr_value, ssim_value and count of :2184-2231 without an .item() per frame.
 // (Like delta_depth_loss, not part of the oracle/ref_link link check, which keeps its twenty entry points.)
+// weights: [H,W] f32 on the device (finite, >= 0): the four numbers are then weighted_photometric_loss's, every sum
+// weighted per pixel and divided by the weight sum; undefined = today's call.
 torch::Tensor image_metrics(const torch::Tensor& image, const torch::Tensor& gt,
                             const torch::Tensor& window1d = torch::Tensor(),
-                            const torch::Tensor& totals = torch::Tensor());
+                            const torch::Tensor& totals = torch::Tensor(),
+                            const torch::Tensor& weights = torch::Tensor());
 torch::Tensor psnr(const torch::Tensor& image, const torch::Tensor& gt);  // image_metrics(...)[0], 0-dim
 // tensor2CvMat3X (:2113-2136) on the device: [3,H,W] f32 -> uint8 [H,W,3] (x * 255, clamp, truncate; NaN -> 0), BGR
 // for cv::imwrite unless bgr = false.  out: a uint8 [H,W,3] view to write into, e.g. a column slice of the [H,2W,3]

@@ -493,10 +493,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   n.def("lidar_depth_loss", &nx::lidar_depth_loss, py::arg("depth"), py::arg("acc"), py::arg("lidar_depth"),
         py::arg("acc_min") = 0.5f, py::arg("lambda_") = 1.0f);
   n.def("image_metrics",
-        [opt](torch::Tensor image, torch::Tensor gt, py::object window, py::object totals) {
-          return nx::image_metrics(image, gt, opt(window), opt(totals));
+        [opt](torch::Tensor image, torch::Tensor gt, py::object window, py::object totals, py::object weights) {
+          return nx::image_metrics(image, gt, opt(window), opt(totals), opt(weights));
         },
-        py::arg("image"), py::arg("gt"), py::arg("window1d") = py::none(), py::arg("totals") = py::none());
+        py::arg("image"), py::arg("gt"), py::arg("window1d") = py::none(), py::arg("totals") = py::none(),
+        py::arg("weights") = py::none());
+  n.def("weighted_photometric_loss",
+        [opt](torch::Tensor image, torch::Tensor gt, py::object weights, py::object acc, float acc_min,
+              py::object exposure, float lambda_dssim, py::object window, bool log_gain) {
+          return nx::weighted_photometric_loss(image, gt, opt(weights), opt(acc), acc_min, opt(exposure), lambda_dssim,
+                                               opt(window), log_gain);
+        },
+        py::arg("image"), py::arg("gt"), py::arg("weights") = py::none(), py::arg("acc") = py::none(),
+        py::arg("acc_min") = 0.5f, py::arg("exposure") = py::none(), py::arg("lambda_dssim") = 0.2f,
+        py::arg("window1d") = py::none(), py::arg("log_gain") = false);
+  n.def("weighted_photometric_loss_parts",
+        [opt](torch::Tensor image, torch::Tensor gt, py::object weights, py::object acc, float acc_min,
+              py::object exposure, float lambda_dssim, py::object window, bool log_gain) {
+          return nx::weighted_photometric_loss_parts(image, gt, opt(weights), opt(acc), acc_min, opt(exposure),
+                                                     lambda_dssim, opt(window), log_gain);
+        },
+        py::arg("image"), py::arg("gt"), py::arg("weights") = py::none(), py::arg("acc") = py::none(),
+        py::arg("acc_min") = 0.5f, py::arg("exposure") = py::none(), py::arg("lambda_dssim") = 0.2f,
+        py::arg("window1d") = py::none(), py::arg("log_gain") = false);
   n.def("psnr", &nx::psnr, py::arg("image"), py::arg("gt"));
   n.def("exposure_photometric_loss",
         [opt](torch::Tensor image, torch::Tensor gt, torch::Tensor exposure, float lambda_dssim, py::object window,

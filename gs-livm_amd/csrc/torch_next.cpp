@@ -143,6 +143,58 @@ struct ExposureLossFn : public torch::autograd::Function<ExposureLossFn> {
   }
 };
 
+// an [H,W] plane (weights, acc: [H,W] or [1,H,W]) of the image's size as a contiguous float32 device tensor; undefined
+// stays undefined
+torch::Tensor plane_of(const torch::Tensor& t, int64_t H, int64_t W, const char* what) {
+  if (!t.defined() || t.numel() == 0) return torch::Tensor();
+  if (t.numel() != H * W) throw std::invalid_argument(std::string(what) + ": one value per pixel, [H,W]");
+  return dev_f32(t.detach().reshape({H, W}), what);
+}
+
+// one evaluation of the weighted loss: out6 = [loss, l1, ssim, S, mse, psnr], dL/dimage and dL/dexposure (or undefined)
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> run_weighted(const torch::Tensor& image, const torch::Tensor& gt,
+                                                                     const torch::Tensor& weights, const torch::Tensor& acc,
+                                                                     float acc_min, const torch::Tensor& exposure,
+                                                                     float lambda, const torch::Tensor& window1d,
+                                                                     bool want_grad) {
+  const torch::Tensor img = dev_f32(image, "image"), ref = dev_f32(gt, "gt");
+  if (img.dim() != 3 || img.sizes() != ref.sizes())
+    throw std::invalid_argument("weighted_photometric_loss: [C,H,W] images of one shape");
+  const int C = img.size(0), H = img.size(1), W = img.size(2);
+  const torch::Tensor w = plane_of(weights, H, W, "weights"), a = plane_of(acc, H, W, "acc");
+  const torch::Tensor e = exposure.defined() && exposure.numel() ? dev_f32(exposure, "exposure") : torch::Tensor();
+  float taps[11];
+  window_taps(window1d, taps);
+  const size_t nbytes = gsr_weighted_loss_workspace(C, H, W);
+  torch::Tensor ws = workspace(nbytes, img);
+  torch::Tensor out6 = torch::empty({6}, img.options());
+  torch::Tensor grad = want_grad ? torch::empty_like(img) : torch::Tensor();
+  torch::Tensor grad_e = want_grad && e.defined() ? torch::empty_like(e) : torch::Tensor();
+  check(gsr_weighted_loss(C, H, W, fp(img), fp(ref), fp(w), fp(a), acc_min, fp(e), taps, lambda, out6.data_ptr<float>(),
+                          fp(grad), fp(grad_e), reinterpret_cast<char*>(ws.data_ptr()), nbytes, current_stream()),
+        "gsr_weighted_loss");
+  return {out6, grad, grad_e};
+}
+
+struct WeightedLossFn : public torch::autograd::Function<WeightedLossFn> {
+  static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor image, torch::Tensor gt,
+                               torch::Tensor weights, torch::Tensor acc, double acc_min, torch::Tensor exposure,
+                               double lambda, torch::Tensor window1d) {
+    const bool need_i = image.requires_grad(), need_e = exposure.numel() && exposure.requires_grad();
+    auto r = run_weighted(image, gt, weights, acc, static_cast<float>(acc_min), exposure, static_cast<float>(lambda),
+                          window1d, need_i || need_e);
+    const torch::Tensor none = torch::empty({0}, std::get<0>(r).options());
+    ctx->save_for_backward({need_i ? std::get<1>(r) : none, need_e ? std::get<2>(r) : none});
+    return std::get<0>(r)[0];
+  }
+  static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx,
+                                               torch::autograd::tensor_list grad_outputs) {
+    const auto saved = ctx->get_saved_variables();
+    return {scaled(saved[0], grad_outputs[0]), torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor(),
+            scaled(saved[1], grad_outputs[0]), torch::Tensor(), torch::Tensor()};
+  }
+};
+
 struct SimilarityLossFn : public torch::autograd::Function<SimilarityLossFn> {
   static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor points, torch::Tensor sel,
                                torch::Tensor xyz, torch::Tensor scaling, double lambda) {
@@ -306,6 +358,28 @@ torch::Tensor exposure_photometric_loss(const torch::Tensor& image, const torch:
                                static_cast<double>(lambda_dssim), window1d.defined() ? window1d : reference_window_1d());
 }
 
+torch::Tensor weighted_photometric_loss(const torch::Tensor& image, const torch::Tensor& gt, const torch::Tensor& weights,
+                                        const torch::Tensor& acc, float acc_min, const torch::Tensor& exposure,
+                                        float lambda_dssim, const torch::Tensor& window1d, bool log_gain) {
+  if (!image.defined() || image.dim() != 3) throw std::invalid_argument("weighted_photometric_loss: image is [C,H,W]");
+  // (an absent operand travels through apply() as an empty tensor: an undefined one has no device to guard)
+  const torch::Tensor none = torch::empty({0}, image.options());
+  const torch::Tensor e = exposure.defined() ? per_channel_exposure(exposure, image.size(0), log_gain) : none;
+  return WeightedLossFn::apply(image, gt, weights.defined() ? weights.detach() : none,
+                               acc.defined() ? acc.detach() : none, static_cast<double>(acc_min), e,
+                               static_cast<double>(lambda_dssim), window1d.defined() ? window1d : reference_window_1d());
+}
+
+torch::Tensor weighted_photometric_loss_parts(const torch::Tensor& image, const torch::Tensor& gt,
+                                              const torch::Tensor& weights, const torch::Tensor& acc, float acc_min,
+                                              const torch::Tensor& exposure, float lambda_dssim,
+                                              const torch::Tensor& window1d, bool log_gain) {
+  torch::NoGradGuard no_grad;
+  if (!image.defined() || image.dim() != 3) throw std::invalid_argument("weighted_photometric_loss: image is [C,H,W]");
+  const torch::Tensor e = exposure.defined() ? per_channel_exposure(exposure, image.size(0), log_gain) : exposure;
+  return std::get<0>(run_weighted(image, gt, weights, acc, acc_min, e, lambda_dssim, window1d, false));
+}
+
 torch::Tensor apply_exposure(const torch::Tensor& image, const torch::Tensor& exposure, const torch::Tensor& out) {
   torch::NoGradGuard no_grad;
   const torch::Tensor img = dev_f32(image.detach(), "image");
@@ -357,13 +431,23 @@ torch::Tensor lidar_depth_loss(const torch::Tensor& depth, const torch::Tensor& 
 }
 
 torch::Tensor image_metrics(const torch::Tensor& image, const torch::Tensor& gt, const torch::Tensor& window1d,
-                            const torch::Tensor& totals) {
+                            const torch::Tensor& totals, const torch::Tensor& weights) {
   torch::NoGradGuard no_grad;
   const torch::Tensor img = dev_f32(image, "image"), ref = dev_f32(gt, "gt");
   if (img.dim() != 3 || img.sizes() != ref.sizes()) throw std::invalid_argument("image_metrics: [C,H,W] images of one shape");
   if (totals.defined() && (!totals.is_cuda() || totals.scalar_type() != torch::kFloat64 || totals.numel() != 4 ||
                            !totals.is_contiguous()))
     throw std::invalid_argument("image_metrics: totals is a contiguous float64 tensor of 4 elements on the device");
+  if (weights.defined()) {  // the forward and finish of csrc/weighted.hip: {psnr, ssim, l1, mse} out of its six
+    const torch::Tensor out6 = std::get<0>(run_weighted(img, ref, weights, torch::Tensor(), 0.f, torch::Tensor(), 0.f,
+                                                        window1d, false));
+    const torch::Tensor out4 = out6.index({torch::tensor({5, 2, 1, 4}, torch::kLong).to(out6.device())});
+    if (totals.defined()) {
+      totals.slice(0, 0, 3) += out4.slice(0, 0, 3).to(torch::kFloat64);
+      totals.slice(0, 3, 4) += 1.0;
+    }
+    return out4;
+  }
   const int C = img.size(0), H = img.size(1), W = img.size(2);
   float taps[11];
   window_taps(window1d, taps);

@@ -3,7 +3,9 @@ csrc/loss.hip (SURVEY.md section 8(f) "next" row 2), and of its LiDAR similarity
 (GaussianModel::compute_min_distance, src/gs/gaussian.cu:87-114) on those of csrc/simi.hip, and of the delta-depth
 term between keyframe pairs (GaussianModel::calcDeltaSimi, src/gs/gaussian.cu:116-199, and the loop around it,
 src/liw/lioOptimization.cpp:1780-1801) on those of csrc/delta.hip, and the LiDAR depth supervision of csrc/lidar.hip
-(an extension: a sweep's z-buffer in a keyframe's view and the masked depth L1 of a render against it)."""
+(an extension: a sweep's z-buffer in a keyframe's view and the masked depth L1 of a render against it), and the weighted
+photometric loss of csrc/weighted.hip (an extension: per-pixel weights, a silhouette gate and the exposure in one
+term)."""
 import math
 
 import torch
@@ -91,6 +93,47 @@ def exposure_photometric_loss(img, gt, exposure, lambda_dssim=0.2, window11=None
         window11 = reference_window_1d()
     e = _per_channel(exposure, int(img.shape[0]), log_gain)
     return ExposureLoss.apply(img, gt, e, window11, float(lambda_dssim))
+
+
+class WeightedPhotometricLoss(torch.autograd.Function):
+    """The photometric loss taken where the caller says: w = weights * [acc >= acc_min], every sum normalised by the
+    weight sum, on x' = fma(g_c, img, b_c) when an exposure is given, as one node (csrc/weighted.hip).  Gradients
+    w.r.t. img and the [C,2] exposure only (gt, weights and acc are data; the gate is a step), both scaled by the
+    upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, img, gt, weights, acc, acc_min, exposure, window11, lambda_dssim):
+        need_e = exposure is not None and ctx.needs_input_grad[5]
+        want = ctx.needs_input_grad[0] or need_e
+        out6, grad, grad_e = _capi.weighted_loss(img, gt, weights, acc, acc_min, exposure, window11.tolist(),
+                                                 lambda_dssim, want_grad=want)
+        ctx.grads = (grad, grad_e)
+        ctx.parts = out6  # [loss, l1, ssim, weight sum, mse, psnr] for logging
+        return out6[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        grad, grad_e = ctx.grads
+        need_i, need_e = ctx.needs_input_grad[0], ctx.needs_input_grad[5] and grad_e is not None
+        return (grad * g if need_i else None), None, None, None, None, (grad_e * g if need_e else None), None, None
+
+
+def weighted_photometric_loss(img, gt, weights=None, acc=None, acc_min=0.5, exposure=None, lambda_dssim=0.2,
+                              window11=None, log_gain=False):
+    """photometric_loss / exposure_photometric_loss over the pixels that carry a measurement: weights ([H,W] f32 on the
+    device, finite and >= 0: an undistortion border, a sky or dynamic-object mask, a texture weight) times the gate
+    [acc >= acc_min] (acc: [H,W] or [1,H,W], e.g. the silhouette `render` returns -- it is detached, the gate has no
+    gradient), each optional.  L1, SSIM and the squared error are weighted per pixel and divided by the weight sum; the
+    SSIM windows still see the whole images, so a zero weight does not shield a non-finite pixel from its neighbours.
+    exposure: [C,2], [2] or (log_gain=True) log-gain, as in `exposure_photometric_loss`, or None.  Returns the 0-dim
+    loss; `.grad_fn.parts` holds {loss, l1, ssim, weight sum, mse, psnr}.  Gradients flow to img and exposure."""
+    if window11 is None:
+        window11 = reference_window_1d()
+    H, W = int(img.shape[1]), int(img.shape[2])
+    plane = lambda t: None if t is None else t.detach().reshape(H, W)  # noqa: E731
+    e = None if exposure is None else _per_channel(exposure, int(img.shape[0]), log_gain)
+    return WeightedPhotometricLoss.apply(img, gt, plane(weights), plane(acc), float(acc_min), e, window11,
+                                         float(lambda_dssim))
 
 
 def apply_exposure(img, exposure, out=None):

@@ -10,14 +10,34 @@ from .loss import apply_exposure, reference_window_1d
 from .render_utils import render
 
 
-def image_metrics(img, gt, window11=None, totals=None):
+def image_metrics(img, gt, window11=None, totals=None, weights=None):
     """-> device tensor [psnr, ssim, l1, mse] of img against gt ([C,H,W] f32 on the device), two launches, no host
     round trip.  psnr is the reference's mean of the per-channel PSNRs (+inf where a channel is identical); ssim and l1
     are those of `photometric_loss`.  totals: a device float64 [4] that {psnr, ssim, l1, 1} is added to (the running
-    sums and the frame count of a keyframe sweep)."""
+    sums and the frame count of a keyframe sweep).  weights: [H,W] f32 on the device, finite and >= 0 (an undistortion
+    border, a sky mask): the four numbers are then those of `weighted_photometric_loss` -- every sum weighted per pixel
+    and divided by the weight sum -- so that pixels without a measurement are not charged."""
     if window11 is None:
         window11 = reference_window_1d()
-    return _capi.image_metrics(img, gt, window11.tolist(), totals=totals)
+    if weights is None:
+        return _capi.image_metrics(img, gt, window11.tolist(), totals=totals)
+    return _weighted_metrics(img, gt, weights, window11.tolist(), None, totals)
+
+
+def _weighted_metrics(img, gt, weights, win, out, totals):
+    """{psnr, ssim, l1, mse} from the forward and finish of csrc/weighted.hip; `totals` as image_metrics adds to it."""
+    with torch.no_grad():
+        H, W = int(img.shape[1]), int(img.shape[2])
+        out6, _, _ = _capi.weighted_loss(img.detach(), gt.detach(), weights.detach().reshape(H, W), None, 0.0, None, win,
+                                         0.0, want_grad=False)
+        row = out6[[5, 2, 1, 4]]
+        if out is not None:
+            out.copy_(row)
+            row = out
+        if totals is not None:
+            totals[:3] += row[:3].double()
+            totals[3] += 1.0
+    return row
 
 
 def psnr(img, gt):
@@ -48,7 +68,7 @@ def depth_to_u8(depth, max_depth=50.0, out=None):
     return _capi.pack_depth_u8(depth, max_depth, out=out)
 
 
-def evaluate_keyframes(cameras, gts, model, bg, on_frame=None, window11=None, exposures=None):
+def evaluate_keyframes(cameras, gts, model, bg, on_frame=None, window11=None, exposures=None, weights=None):
     """The loop of saveRender (:2198-2231): every keyframe is rendered forward-only and measured against its ground
     truth ([3,H,W] f32 on the device); the per-frame metrics and their running float64 sums stay on the device and are
     copied to the host ONCE, after the last frame (the reference makes two .item() round trips per frame).
@@ -56,6 +76,7 @@ def evaluate_keyframes(cameras, gts, model, bg, on_frame=None, window11=None, ex
     exposures: one learnt exposure per keyframe ([C,2] or [2], `exposure_photometric_loss`) or None for a keyframe
     without one; the render is compensated in place (`apply_exposure`) before it is measured and handed to on_frame,
     so that the metrics are not charged for the camera's gain.
+    weights: one [H,W] weight map per keyframe (`image_metrics`' weights) or None for a keyframe measured on all pixels.
     -> dict(rows = CPU f32 [n,4] of {psnr, ssim, l1, mse} per frame, totals = CPU f64 [4] = {sum psnr, sum ssim,
     sum l1, n}, mean_psnr, mean_ssim, frames = n)."""
     cameras, gts = list(cameras), list(gts)
@@ -65,6 +86,9 @@ def evaluate_keyframes(cameras, gts, model, bg, on_frame=None, window11=None, ex
     exposures = [None] * n if exposures is None else list(exposures)
     if len(exposures) != n:
         raise ValueError("one exposure (or None) per camera")
+    weights = [None] * n if weights is None else list(weights)
+    if len(weights) != n:
+        raise ValueError("one weight map (or None) per camera")
     dev = model.Get_xyz().device
     win = (reference_window_1d() if window11 is None else window11).tolist()
     # one buffer, one copy: the four float64 totals in front (8-byte aligned), the n float32 rows behind them
@@ -75,7 +99,10 @@ def evaluate_keyframes(cameras, gts, model, bg, on_frame=None, window11=None, ex
             image, depth, _ = render(cam, model, bg)
             if exposures[i] is not None:
                 image = apply_exposure(image, exposures[i], out=image if image.is_contiguous() else None)
-            _capi.image_metrics(image, gt, win, out=rows[i], totals=totals)
+            if weights[i] is None:
+                _capi.image_metrics(image, gt, win, out=rows[i], totals=totals)
+            else:
+                _weighted_metrics(image, gt, weights[i], win, rows[i], totals)
             if on_frame is not None:
                 on_frame(i, image, depth)
     host = buf.cpu()

@@ -434,6 +434,40 @@ int gsr_exposure_loss(int channels, int height, int width, const float* img, con
 int gsr_apply_exposure(int channels, int height, int width, const float* img, const float* exposure,
                        float* out, void* stream);
 
+/* ---- the weighted photometric loss: per-pixel weights, a silhouette gate and the exposure, each optional (an
+ * extension: the reference has no such term; csrc/weighted.hip) ----
+ *   x'(p) = fma(g_c, x(p), b_c) with an exposure, x(p) without one
+ *   w(p)  = weights(p) * [acc(p) >= acc_min]          (absent weights: 1; absent acc: no gate; a NaN acc: weight 0)
+ *   S     = sum_p w(p)    over the H W pixels: weights and acc are [H][W] device f32, shared by the channels
+ *   l1    = sum_c sum_p w |x' - gt| / (C S)           ssim = sum_c sum_q w(q) SSIM_c(q) / (C S)
+ *   L     = (1 - lambda) l1 + lambda (1 - ssim)       mse_c = sum_p w (x' - gt)^2 / S
+ * SSIM_c is gsr_photometric_loss's, its windows over the FULL x' and gt (zero padding of the compensated image): the
+ * weights select where the loss is taken, not what the windows see.  For undistortion borders, sky and dynamic-object
+ * masks, texture weights and tracking over the mapped pixels only (acc = the render's silhouette).
+ * out6 (device) = {L, l1, ssim, S, mean_c mse_c, psnr}, psnr = gsr_image_metrics's rule on mse_c (+inf where mse_c = 0).
+ * With G = dL/dx' for upstream gradient 1:  dL_dimg[c][p] = g_c G(p) (G without an exposure),
+ * dL_dexposure[c] = (sum_p G x, sum_p G), x the ORIGINAL image.  Weights and acc get no gradient: the gate is a step.
+ * dL_dimg is nullable; dL_dexposure exists only with an exposure, and then both gradients are given or both null.
+ * Launches: forward and finish, and with a gradient the backward between them (three in all, as gsr_exposure_loss):
+ * 1 / (C S) is formed on the device by every workgroup of the backward, in one fixed order.  No host wait, no
+ * allocation, the caller's stream; deterministic (fixed-order reductions, no atomics).  The S of out6[3] and the S behind
+ * every gradient element are the same bits.
+ * S = 0 (nothing supervised): L = l1 = ssim = mse = 0, psnr = +inf, every gradient element zero, nothing non-finite.
+ * Weights are the caller's contract: finite and >= 0.  A ZERO WEIGHT DOES NOT PROTECT AGAINST A NON-FINITE PIXEL of
+ * img or gt: the SSIM windows of the weighted pixels within 5 pixels of it read it.
+ * With weights absent or all one and no gate, {L, l1, ssim}, dL_dimg and dL_dexposure equal gsr_exposure_loss's bit for
+ * bit (gsr_photometric_loss's without an exposure); weights scaled by a power of two change S and nothing else.
+ * Refusals, in this order: a non-positive dimension, a plane of 2^31 - 1 pixels or more, a null img / gt /
+ * window11_host / out6 / workspace, dL_dexposure without exposure, exposure with only one of dL_dimg and dL_dexposure,
+ * a non-finite acc_min with acc given, workspace_bytes below gsr_weighted_loss_workspace (which returns 0 for a refused
+ * shape); nothing is launched or written then.  The workspace may sit at any 4-byte aligned address. */
+size_t gsr_weighted_loss_workspace(int channels, int height, int width);
+int gsr_weighted_loss(int channels, int height, int width, const float* img, const float* gt,
+                      const float* weights /* device [H][W], nullable */, const float* acc /* device [H][W], nullable */,
+                      float acc_min, const float* exposure /* device [channels][2], nullable */,
+                      const float* window11_host, float lambda_dssim, float* out6, float* dL_dimg,
+                      float* dL_dexposure, char* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the LiDAR similarity loss (step 3 of optimize_vis), fused ----
  *   r = mean(scaling[sel]) (one scalar over the 3n selected elements),  d_ij = |points_i - xyz[sel_j]|,
  *   L = lambda * mean_i min_j max(d_ij - r, 0) = lambda / m * sum_i max(min_j d_ij - r, 0)
