@@ -74,7 +74,8 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_densify_apply", "gsr_pose_gradient", "gsr_pose_gradient_workspace", "gsr_exposure_loss",
            "gsr_exposure_loss_workspace", "gsr_apply_exposure", "gsr_visibility_words", "gsr_visibility_pack",
            "gsr_covisibility", "gsr_observation_count", "gsr_visibility_remap", "gsr_contribution_workspace",
-           "gsr_contribution", "gsr_contribution_finish", "gsr_weighted_loss", "gsr_weighted_loss_workspace")
+           "gsr_contribution", "gsr_contribution_finish", "gsr_weighted_loss", "gsr_weighted_loss_workspace",
+           "gsr_sweep_admit", "gsr_sweep_admit_workspace")
 
 
 def lib():
@@ -199,6 +200,11 @@ def lib():
     L.gsr_lidar_depth_loss_workspace.argtypes = [ci, ci]
     L.gsr_lidar_depth_loss.restype = ci
     L.gsr_lidar_depth_loss.argtypes = [ci, ci, vp, vp, vp, cf, cf, vp, vp, vp, vp, sz, vp]
+    L.gsr_sweep_admit_workspace.restype = sz
+    L.gsr_sweep_admit_workspace.argtypes = [ci, ci, ci]
+    L.gsr_sweep_admit.restype = ci
+    L.gsr_sweep_admit.argtypes = [ci, vp, vp, C.POINTER(cf), C.POINTER(cf), ci, ci, cf, cf, vp, vp, cf, cf, vp, ci, cf,
+                                  vp, vp, cf, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     L.gsr_image_metrics_workspace.restype = sz
     L.gsr_image_metrics_workspace.argtypes = [ci, ci, ci]
     L.gsr_image_metrics.restype = ci
@@ -805,6 +811,62 @@ def lidar_depth_loss(depth, acc, lidar_depth, acc_min, lambda_, want_grad_depth=
     _check(lib().gsr_lidar_depth_loss(H, W, _ptr(depth), _ptr(acc), _ptr(lidar_depth), float(acc_min), float(lambda_),
                                       _ptr(out3), _ptr(gd), _ptr(ga), _ptr(ws), nbytes, _stream()))
     return out3, gd, ga
+
+
+def sweep_admit(points_world, T_cw, K, height, width, depth_tol, occlusion_tol, depth=None, acc=None, image=None,
+                lidar_depth=None, covs=None, exposure=None, acc_min=0.5, occlusion_radius=1, footprint=1.0,
+                min_depth=0.2, max_depth=float("inf"), one_per_pixel=True, want_reasons=False, out=None, workspace=None):
+    """Sweep admission in five launches (include/gsraster.h, gsr_sweep_admit).  points_world: [n,3] f32 on the device
+    (n == 0 is legal); T_cw (3x4 or 4x4) and K (3x3) on the host; depth / acc / lidar_depth: [H,W] or [1,H,W]; image:
+    [3,H,W]; covs: [n,3,3] or [n,9]; exposure: [3,2] rows (g, b); all f32 on the device or None.  out: a dict of
+    contiguous device tensors of max(n, 1) rows to write (xyz [n,3], covs [n,9], rgb [n,3], index, pixel int32 [n], z [n]) or
+    None = new ones; workspace: a uint8 device tensor of at least the queried size or None.  No host wait.  Returns
+    (the dict with FULL-length outputs -- rows at and behind counts[0] are not written -- counts int32 [6] on the
+    device, reasons uint8 [n] or None)."""
+    assert points_world.is_cuda and points_world.dtype == torch.float32 and points_world.is_contiguous()
+    assert points_world.dim() == 2 and points_world.size(1) == 3
+    n, H, W = int(points_world.size(0)), int(height), int(width)
+    dev = points_world.device
+    T = torch.as_tensor(T_cw, dtype=torch.float64).reshape(-1, 4)[:3]
+    tcw, k9 = _host_floats(T, 12), _host_floats(K, 9)
+    for t in (depth, acc, lidar_depth):
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == H * W)
+    assert image is None or (image.is_cuda and image.is_contiguous() and image.dtype == torch.float32
+                             and tuple(image.shape) == (3, H, W))
+    assert covs is None or (covs.is_cuda and covs.is_contiguous() and covs.dtype == torch.float32
+                            and covs.numel() == 9 * n)
+    assert exposure is None or (exposure.is_cuda and exposure.is_contiguous() and exposure.dtype == torch.float32
+                                and tuple(exposure.shape) == (3, 2))
+    if out is None:
+        r = max(n, 1)   # (at least one row: the library refuses a null output even when n == 0)
+        out = dict(xyz=torch.empty((r, 3), dtype=torch.float32, device=dev),
+                   covs=torch.empty((r, 9), dtype=torch.float32, device=dev),
+                   rgb=torch.empty((r, 3), dtype=torch.float32, device=dev) if image is not None else None,
+                   index=torch.empty(r, dtype=torch.int32, device=dev),
+                   pixel=torch.empty(r, dtype=torch.int32, device=dev),
+                   z=torch.empty(r, dtype=torch.float32, device=dev))
+    nbytes = int(lib().gsr_sweep_admit_workspace(n, H, W))
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    counts = torch.empty(6, dtype=torch.int32, device=dev)
+    reasons = torch.empty(n, dtype=torch.uint8, device=dev) if want_reasons else None
+    _check(lib().gsr_sweep_admit(n, _ptr(points_world), _ptr(covs), tcw, k9, H, W, float(min_depth), float(max_depth),
+                                 _ptr(depth), _ptr(acc), float(acc_min), float(depth_tol), _ptr(lidar_depth),
+                                 int(occlusion_radius), float(occlusion_tol), _ptr(image), _ptr(exposure),
+                                 float(footprint), int(bool(one_per_pixel)), _out_ptr(out["xyz"]), _out_ptr(out["covs"]),
+                                 _out_ptr(out.get("rgb")), _out_ptr(out["index"]), _out_ptr(out.get("pixel")),
+                                 _out_ptr(out.get("z")), _ptr(reasons), C.c_void_p(counts.data_ptr()),
+                                 C.c_void_p(workspace.data_ptr()) if nbytes else None, min(nbytes, workspace.numel()),
+                                 _stream()))
+    return out, counts, reasons
+
+
+def _out_ptr(t):
+    """Device pointer of an output of sweep_admit (None -> NULL)."""
+    if t is None:
+        return None
+    assert t.is_cuda and t.is_contiguous()
+    return C.c_void_p(t.data_ptr())
 
 
 def image_metrics(img, gt, window11, out=None, totals=None):

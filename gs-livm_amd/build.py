@@ -37,6 +37,8 @@ UNITS = {
     "simi.hip": [],
     "delta.hip": [],
     "lidar.hip": [],
+    # sweep admission is restated bit for bit on dyadic inputs; its multiply-adds are explicit (gsr_lidar_project.hpp)
+    "seed.hip": ["-ffp-contract=off"],
     "prune.hip": [],
     "covis.hip": [],  # (integer arithmetic throughout: no floating-point flag bears on it)
     "contrib.hip": [],  # (entry points + the finish kernel; the walk is built with render.hip, whose alpha it recomputes)
@@ -47,6 +49,7 @@ UNITS = {
 }
 HEADERS = [os.path.join(CSRC, "gsr_internal.hpp"), os.path.join(CSRC, "gsr_api.hpp"), os.path.join(CSRC, "sort_core.hpp"),
            os.path.join(CSRC, "gsr_workgroup.hpp"), os.path.join(CSRC, "gsr_window.hpp"),
+           os.path.join(CSRC, "gsr_lidar_project.hpp"),
            os.path.join(ROOT, "include", "gsraster.h")]
 
 

@@ -10,6 +10,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <array>
 #include <limits>
 #include <string>
 #include <tuple>
@@ -104,6 +105,33 @@ torch::Tensor lidar_depth_image(const torch::Tensor& points_world, const torch::
 // (Like delta_depth_loss, these two are not part of the oracle/ref_link link check, which stays as it is.)
 torch::Tensor lidar_depth_loss(const torch::Tensor& depth, const torch::Tensor& acc, const torch::Tensor& lidar_depth,
                                float acc_min = 0.5f, float lambda = 1.0f);
+
+// ---- sweep admission (an extension; csrc/seed.hip, gsr_sweep_admit) ----------------------------------------------------
+// The points of a sweep that a keyframe's render does not explain yet, compacted in input order and ready for
+// GrowableGaussians::add_new_pointcloud: coloured from the keyframe's image (bilinear, the exposure inverted, times
+// 255) and sized by their pixel footprint unless covs is given.  An undefined tensor stands for an absent optional
+// input (depth and acc go together).  One host wait: the read of the counts.  The returned tensors are views of the
+// first `admitted` rows.  (Like delta_depth_loss, not part of the oracle/ref_link link check, which stays as it is.)
+struct SweepAdmitOptions {
+  float acc_min = 0.5f;
+  int occlusion_radius = 1;
+  float footprint = 1.0f;
+  float min_depth = 0.2f;
+  float max_depth = std::numeric_limits<float>::infinity();
+  bool one_per_pixel = true;
+  bool want_reasons = false;
+};
+struct Admitted {
+  torch::Tensor xyz, covs, rgbs, index, pixel, z;  // [m,3], [m,3,3], [m,3] or undefined, int32 [m], int32 [m], [m]
+  std::array<int64_t, 6> counts;                   // admitted, out, occluded, explained, behind, duplicate
+  torch::Tensor reasons;                           // uint8 [n] on the device (want_reasons) or undefined
+};
+Admitted admit_sweep(const torch::Tensor& points_world, const torch::Tensor& T_cw, const torch::Tensor& K,
+                     int64_t height, int64_t width, float depth_tol, float occlusion_tol,
+                     const torch::Tensor& depth = torch::Tensor(), const torch::Tensor& acc = torch::Tensor(),
+                     const torch::Tensor& image = torch::Tensor(), const torch::Tensor& lidar_depth = torch::Tensor(),
+                     const torch::Tensor& covs = torch::Tensor(), const torch::Tensor& exposure = torch::Tensor(),
+                     const SweepAdmitOptions& options = SweepAdmitOptions());
 
 // ---- the evaluation pass (saveRender, src/liw/lioOptimization.cpp:2182-2245; the status line of optimize_vis) ------
 // [psnr, ssim, l1, mse] of image against gt ([C,H,W] f32 on the device) on the kernels of csrc/metrics.hip, a device

@@ -6,7 +6,7 @@
 // 1. gsr_lidar_depth_image.  Per point x (world):
 //   p = R x + t, z = p.z                              [R | t] = T_cw, x_c = R x_w + t
 //   (X, Y) = (K p).xy / (K p).z                       N = M (x, 1) with M = K [R | t] composed on the host in double and
-//                                                     rounded once (launch_lidar_depth_image), as delta.hip's matrices
+//                                                     rounded once (lidar_compose, gsr_lidar_project.hpp), as delta.hip's matrices
 //   (ix, iy) = (floor(X + 0.5), floor(Y + 0.5))       pixel u covers [u - 0.5, u + 0.5): the rasterizer's ndc2Pix
 //   dropped: a coordinate of x, z, X or Y not finite; z <= min_depth; z > max_depth; |X| or |Y| beyond 2^30 (tested
 //   before any conversion to an integer, as delta_cell); the pixel outside the image
@@ -34,15 +34,10 @@
 // against +-2^30 and then against the image before the atomic.
 #include "gsr_api.hpp"
 #include "gsr_internal.hpp"
+#include "gsr_lidar_project.hpp"
 #include "gsr_workgroup.hpp"
 
 namespace gsr {
-
-struct LidarCam {   // composed on the host in double, rounded once
-  float m[12];      // M = K [R | t], row-major 3 x 4
-  float r2[3];      // third row of R
-  float tz;
-};
 
 struct LidarWorkspace {
   double* abs_part;   // [nblocks]
@@ -80,20 +75,11 @@ __global__ __launch_bounds__(256) void k_lidar_splat(const int n, const int W, c
   int kept = 0;
   if (i < n) {
     const float x = points[3 * (size_t)i], y = points[3 * (size_t)i + 1], w = points[3 * (size_t)i + 2];
-    const float z = __builtin_fmaf(cam.r2[0], x, __builtin_fmaf(cam.r2[1], y, __builtin_fmaf(cam.r2[2], w, cam.tz)));
-    const float nx = __builtin_fmaf(cam.m[0], x, __builtin_fmaf(cam.m[1], y, __builtin_fmaf(cam.m[2], w, cam.m[3])));
-    const float ny = __builtin_fmaf(cam.m[4], x, __builtin_fmaf(cam.m[5], y, __builtin_fmaf(cam.m[6], w, cam.m[7])));
-    const float nz = __builtin_fmaf(cam.m[8], x, __builtin_fmaf(cam.m[9], y, __builtin_fmaf(cam.m[10], w, cam.m[11])));
-    const float X = nx / nz, Y = ny / nz;
-    // every comparison is false for NaN; z <= max_depth with z finite (max_depth may be +inf)
-    const bool fin = fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(w) < INFINITY && fabsf(z) < INFINITY;
-    if (fin && z > min_depth && z <= max_depth && fabsf(X) <= COORD_MAX_ && fabsf(Y) <= COORD_MAX_) {
-      const int ix = (int)floorf(X + 0.5f), iy = (int)floorf(Y + 0.5f);
-      if (ix >= 0 && ix < W && iy >= 0 && iy < H) {
-        kept = 1;
-        // z > min_depth >= 0: a positive float, whose bits order like the float (result unused: no return)
-        atomicMin(&image[(size_t)iy * W + ix], __float_as_uint(z));
-      }
+    LidarHit h;   // (the projection and the drop rule: gsr_lidar_project.hpp, shared with seed.hip)
+    if (lidar_project(cam, x, y, w, min_depth, max_depth, W, H, h)) {
+      kept = 1;
+      // z > min_depth >= 0: a positive float, whose bits order like the float (result unused: no return)
+      atomicMin(&image[(size_t)h.iy * W + h.ix], __float_as_uint(h.z));
     }
   }
   if (counts2) {
@@ -190,15 +176,7 @@ static hipError_t launch_lidar_depth_image(int n, const float* points_world, con
     hipLaunchKernelGGL(k_lidar_clear, dim3(nblocks), dim3(256), 0, s, N, n ? LIDAR_EMPTY_ : 0u, image, counts2);
   }
   if (n == 0) return hipGetLastError();
-  LidarCam cam;
-  for (int r = 0; r < 3; r++)
-    for (int q = 0; q < 4; q++) {
-      double v = 0.0;
-      for (int k = 0; k < 3; k++) v += (double)K9[3 * r + k] * (double)T_cw12[4 * k + q];
-      cam.m[4 * r + q] = (float)v;
-    }
-  for (int q = 0; q < 3; q++) cam.r2[q] = T_cw12[8 + q];
-  cam.tz = T_cw12[11];
+  const LidarCam cam = lidar_compose(T_cw12, K9);
   {
     ProfScope ps(K_LIDAR_SPLAT, s);
     hipLaunchKernelGGL(k_lidar_splat, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0, s, n, W, H, cam, min_depth, max_depth,

@@ -492,6 +492,31 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("want_counts") = false);
   n.def("lidar_depth_loss", &nx::lidar_depth_loss, py::arg("depth"), py::arg("acc"), py::arg("lidar_depth"),
         py::arg("acc_min") = 0.5f, py::arg("lambda_") = 1.0f);
+  n.def("admit_sweep",
+        [opt](torch::Tensor points_world, torch::Tensor T_cw, torch::Tensor K, int64_t height, int64_t width,
+              float depth_tol, float occlusion_tol, py::object depth, py::object acc, py::object image,
+              py::object lidar_depth, py::object covs, py::object exposure, float acc_min, int occlusion_radius,
+              float footprint, float min_depth, float max_depth, bool one_per_pixel, bool want_reasons) {
+          nx::SweepAdmitOptions o;
+          o.acc_min = acc_min; o.occlusion_radius = occlusion_radius; o.footprint = footprint;
+          o.min_depth = min_depth; o.max_depth = max_depth; o.one_per_pixel = one_per_pixel;
+          o.want_reasons = want_reasons;
+          const nx::Admitted a = nx::admit_sweep(points_world, T_cw, K, height, width, depth_tol, occlusion_tol,
+                                                 opt(depth), opt(acc), opt(image), opt(lidar_depth), opt(covs),
+                                                 opt(exposure), o);
+          auto none_or = [](const torch::Tensor& t) -> py::object { return t.defined() ? py::cast(t) : py::none(); };
+          py::list counts;
+          for (int64_t c : a.counts) counts.append(c);
+          return py::make_tuple(a.xyz, a.covs, none_or(a.rgbs), a.index, a.pixel, a.z, py::tuple(counts),
+                                none_or(a.reasons));
+        },
+        py::arg("points_world"), py::arg("T_cw"), py::arg("K"), py::arg("height"), py::arg("width"),
+        py::arg("depth_tol"), py::arg("occlusion_tol"), py::arg("depth") = py::none(), py::arg("acc") = py::none(),
+        py::arg("image") = py::none(), py::arg("lidar_depth") = py::none(), py::arg("covs") = py::none(),
+        py::arg("exposure") = py::none(), py::arg("acc_min") = 0.5f, py::arg("occlusion_radius") = 1,
+        py::arg("footprint") = 1.0f, py::arg("min_depth") = 0.2f,
+        py::arg("max_depth") = std::numeric_limits<float>::infinity(), py::arg("one_per_pixel") = true,
+        py::arg("want_reasons") = false);
   n.def("image_metrics",
         [opt](torch::Tensor image, torch::Tensor gt, py::object window, py::object totals, py::object weights) {
           return nx::image_metrics(image, gt, opt(window), opt(totals), opt(weights));

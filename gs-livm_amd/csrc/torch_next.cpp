@@ -430,6 +430,55 @@ torch::Tensor lidar_depth_loss(const torch::Tensor& depth, const torch::Tensor& 
   return LidarDepthLossFn::apply(depth, acc, lidar_depth, static_cast<double>(acc_min), static_cast<double>(lambda));
 }
 
+Admitted admit_sweep(const torch::Tensor& points_world, const torch::Tensor& T_cw, const torch::Tensor& K,
+                     int64_t height, int64_t width, float depth_tol, float occlusion_tol, const torch::Tensor& depth,
+                     const torch::Tensor& acc, const torch::Tensor& image, const torch::Tensor& lidar_depth,
+                     const torch::Tensor& covs, const torch::Tensor& exposure, const SweepAdmitOptions& o) {
+  torch::NoGradGuard no_grad;
+  const torch::Tensor p = dev_f32(points_world, "points_world");
+  if (p.dim() != 2 || p.size(1) != 3) throw std::invalid_argument("admit_sweep: points_world is [n,3]");
+  const torch::Tensor tcw = host_rows3(T_cw, "T_cw"), k = host_rows3(K, "K");
+  if (tcw.numel() != 12 || k.numel() != 9) throw std::invalid_argument("admit_sweep: T_cw is 3x4 or 4x4, K is 3x3");
+  const int64_t n = p.size(0), HW = std::max<int64_t>(height, 0) * std::max<int64_t>(width, 0);
+  auto plane = [&](const torch::Tensor& t, const char* name, int64_t numel) {
+    if (!t.defined()) return torch::Tensor();
+    const torch::Tensor c = dev_f32(t.detach(), name);
+    if (c.numel() != numel) throw std::invalid_argument(std::string("admit_sweep: bad shape of ") + name);
+    return c;
+  };
+  const torch::Tensor d = plane(depth, "depth", HW), a = plane(acc, "acc", HW), zl = plane(lidar_depth, "lidar_depth", HW),
+                      img = plane(image, "image", 3 * HW), cv = plane(covs, "covs", 9 * n), e = plane(exposure, "exposure", 6);
+  const int64_t rows = std::max<int64_t>(n, 1);  // (at least one row: a null output is refused even when n == 0)
+  const auto i32 = p.options().dtype(torch::kInt32);
+  torch::Tensor xyz = torch::empty({rows, 3}, p.options()), cov = torch::empty({rows, 9}, p.options()),
+                rgb = img.defined() ? torch::empty({rows, 3}, p.options()) : torch::Tensor(),
+                index = torch::empty({rows}, i32), pixel = torch::empty({rows}, i32), z = torch::empty({rows}, p.options()),
+                counts = torch::empty({6}, i32),
+                reasons = o.want_reasons ? torch::empty({n}, p.options().dtype(torch::kByte)) : torch::Tensor();
+  const size_t nbytes = gsr_sweep_admit_workspace(static_cast<int>(n), static_cast<int>(height), static_cast<int>(width));
+  torch::Tensor ws = workspace(nbytes, p);
+  check(gsr_sweep_admit(static_cast<int>(n), fp(p), fp(cv), tcw.data_ptr<float>(), k.data_ptr<float>(),
+                        static_cast<int>(height), static_cast<int>(width), o.min_depth, o.max_depth, fp(d), fp(a),
+                        o.acc_min, depth_tol, fp(zl), o.occlusion_radius, occlusion_tol, fp(img), fp(e), o.footprint,
+                        o.one_per_pixel ? 1 : 0, xyz.data_ptr<float>(), cov.data_ptr<float>(), fp(rgb),
+                        index.data_ptr<int>(), pixel.data_ptr<int>(), z.data_ptr<float>(),
+                        reasons.defined() && n ? reasons.data_ptr<uint8_t>() : nullptr, counts.data_ptr<int>(),
+                        reinterpret_cast<char*>(ws.data_ptr<uint8_t>()), nbytes, current_stream()),
+        "gsr_sweep_admit");
+  Admitted out;
+  const torch::Tensor host = counts.to(torch::kCPU);  // the one host wait
+  for (int q = 0; q < 6; q++) out.counts[q] = host.data_ptr<int>()[q];
+  const int64_t m = out.counts[0];
+  out.xyz = xyz.slice(0, 0, m);
+  out.covs = cov.slice(0, 0, m).view({m, 3, 3});
+  if (rgb.defined()) out.rgbs = rgb.slice(0, 0, m);
+  out.index = index.slice(0, 0, m);
+  out.pixel = pixel.slice(0, 0, m);
+  out.z = z.slice(0, 0, m);
+  out.reasons = reasons;
+  return out;
+}
+
 torch::Tensor image_metrics(const torch::Tensor& image, const torch::Tensor& gt, const torch::Tensor& window1d,
                             const torch::Tensor& totals, const torch::Tensor& weights) {
   torch::NoGradGuard no_grad;

@@ -400,6 +400,23 @@ class GrowableGaussians(GaussianParameters):
         return lo, hi
 
     @torch.no_grad()
+    def add_unexplained(self, points_world, camera, depth, acc, image, scale_factor=1.0, **admit_arguments):
+        """Seeds Gaussians only where the map lacks them: `admit_sweep` (seed.py) of a sweep against the render
+        (depth, acc: the rasterizer's second and third outputs, or None for both while there is no model) and the
+        image ([3,H,W], 0..1) of `camera` (a render_utils.Camera: its pose through `world_to_camera`, its intrinsics
+        through `raster_K`), then `add_new_pointcloud` of the admitted points.  admit_arguments: depth_tol and
+        occlusion_tol (required) and admit_sweep's other keywords.  The appended rows belong to no voxel, as
+        densify's; group by the returned indices to register voxels.  One host wait (the admitted count).
+        Returns (lo, hi, counts): the row range of the new Gaussians and admit_sweep's six counts."""
+        from .loss import raster_K, world_to_camera
+        from .seed import admit_sweep
+        W, H = camera.Get_image_width(), camera.Get_image_height()
+        a = admit_sweep(points_world, world_to_camera(camera), raster_K(W, H, camera.Get_FoVx(), camera.Get_FoVy()), H, W,
+                        depth=depth, acc=acc, image=image, **admit_arguments)
+        lo, hi = self.add_new_pointcloud(a.xyz, a.covs, a.rgbs, scale_factor)
+        return lo, hi, a.counts
+
+    @torch.no_grad()
     def prune(self, min_opacity=1.0 / 255.0, max_scale=0.3, drop_nonfinite=True, drop=None):
         """Removes the rows that are dead to the rasterizer for good -- the shrinking counterpart of add_new_pointcloud,
         GaussianModel::prune_optimizer (src/gs/gaussian.cu:430-449) for all six groups at once.  A row leaves when

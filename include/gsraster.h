@@ -559,6 +559,55 @@ int gsr_lidar_depth_loss(int height, int width, const float* depth, const float*
                          float acc_min, float lambda, float* out3, float* dL_ddepth, float* dL_dacc, char* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- sweep admission: the points of a LiDAR sweep that a keyframe's render does not explain yet ----
+ * An extension (the reference seeds a voxel once, whatever the map holds, and colours the points on the host from the
+ * nearest pixel without an occlusion test): the producer-side step in front of gsr_init_gaussians.
+ *
+ * gsr_sweep_admit: every point x of points_world (device [n][3] f32) is projected exactly as gsr_lidar_depth_image
+ * projects it -- the same T_cw12 / K9 on the HOST, the same composed matrix, the same z, X, Y, ix, iy, bit for bit --
+ * and receives ONE reason code, decided in this order:
+ *   1 OUT        gsr_lidar_depth_image would drop the point (its rule, min_depth and max_depth included)
+ *   2 OCCLUDED   only with lidar_depth (nullable, device [H][W] f32, the image of gsr_lidar_depth_image): zmin = the
+ *                smallest POSITIVE value of lidar_depth over |dx|, |dy| <= occlusion_radius around (ix, iy), the window
+ *                clamped to the image; the code is 2 iff z - zmin > occlusion_tol * z (never without a positive value)
+ *   3 EXPLAINED  only with depth = D = sum z alpha T and acc = A = sum alpha T (nullable TOGETHER, device [H][W] f32,
+ *   4 BEHIND     the rasterizer's second and third outputs; absent = no model yet).  If !(A >= acc_min), NaN included,
+ *                the silhouette is missing and the point goes on.  Otherwise r = D / A:  r - z > depth_tol * z (the
+ *                measurement lies in front of the render): the point goes on;  z - r > depth_tol * z: 4;  anything
+ *                else, a NaN r included: 3.  Both comparisons are strict
+ *   5 DUPLICATE  only with one_per_pixel != 0: among the points that got this far a pixel keeps the one with the
+ *                smallest 64-bit key (bits(z) << 32) | index -- the nearest, and among equal z the lowest index
+ *   0 ADMITTED   everything else
+ * The admitted points are compacted STABLY (input order).  For the j-th of them, with source index i:
+ *   index_out[j] = i;  xyz_out[j] = the three input floats bit for bit;  pixel_out[j] = iy * width + ix and
+ *   z_out[j] = z (both nullable)
+ *   covs_out[j] = the nine floats of covs_in[i] (nullable, device [n][9]) bit for bit; without covs_in sigma^2 I,
+ *     sigma = ((footprint * z) * 2) / (fx + fy), fx = K9[0], fy = K9[4], the off-diagonal elements exact zeros
+ *   rgb_out[j] (written only with image: nullable, device [3][H][W] f32 in 0..1): the bilinear sample at (X, Y), pixel
+ *     centres at the integers, x0 = floor(X), y0 = floor(Y), the four taps clamped to the image (border replication),
+ *     two horizontal lerps then one vertical, each a + t * (b - a); with exposure (nullable, device [3][2], rows
+ *     (g, b) as gsr_apply_exposure takes them) inverted, (v - b) / g; then times 255.  No clamp
+ * Rows j >= admitted of every output are NOT written (each output holds n rows).  reasons (nullable, device n bytes)
+ * is written in every element; counts6 (device, 6 ints) = {admitted, out, occluded, explained, behind, duplicate},
+ * which sum to n.  n == 0 is legal: counts6 all zero, nothing else written, no workspace needed.
+ * Five launches (four without one_per_pixel, one when n == 0), 64-bit and 32-bit INTEGER atomics only (the minimum
+ * commutes: the same bits on every run), no host synchronisation, no allocation, the caller's stream only.
+ * Refused (GSR_ERR_INVALID_ARGUMENT, nothing launched or written), in this order: n < 0; height or width < 1;
+ * height * width >= 2^31; a null T_cw12, K9, xyz_out, covs_out, index_out or counts6, or a null points_world with
+ * n > 0; depth without acc or acc without depth; acc_min not finite or <= 0; depth_tol, occlusion_tol or footprint not
+ * finite or < 0; occlusion_radius outside 0..3; min_depth not finite or < 0; max_depth not greater than min_depth (+inf
+ * is allowed); workspace_bytes below the query (the message names the bytes needed); a null workspace with n > 0; a
+ * float or int32 array off 4-byte alignment.  The workspace needs no alignment; the query returns 0 for a refused
+ * shape (and for n == 0). */
+size_t gsr_sweep_admit_workspace(int n, int height, int width);
+int gsr_sweep_admit(int n, const float* points_world, const float* covs_in, const float* T_cw12, const float* K9,
+                    int height, int width, float min_depth, float max_depth, const float* depth, const float* acc,
+                    float acc_min, float depth_tol, const float* lidar_depth, int occlusion_radius,
+                    float occlusion_tol, const float* image, const float* exposure, float footprint,
+                    int one_per_pixel, float* xyz_out, float* covs_out, float* rgb_out, int* index_out, int* pixel_out,
+                    float* z_out, unsigned char* reasons, int* counts6, char* workspace, size_t workspace_bytes,
+                    void* stream);
+
 /* ---- the evaluation pass around a forward-only render: PSNR, SSIM and 8-bit frame export ----
  * gsr_image_metrics: out4 (device) = {psnr, ssim, l1, mse} of img against gt, [channels][H][W] device f32, in two
  * launches:
