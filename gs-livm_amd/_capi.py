@@ -75,7 +75,8 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_exposure_loss_workspace", "gsr_apply_exposure", "gsr_visibility_words", "gsr_visibility_pack",
            "gsr_covisibility", "gsr_observation_count", "gsr_visibility_remap", "gsr_contribution_workspace",
            "gsr_contribution", "gsr_contribution_finish", "gsr_weighted_loss", "gsr_weighted_loss_workspace",
-           "gsr_sweep_admit", "gsr_sweep_admit_workspace")
+           "gsr_sweep_admit", "gsr_sweep_admit_workspace", "gsr_lidar_occlusion_filter",
+           "gsr_lidar_depth_loss_robust", "gsr_lidar_depth_loss_robust_workspace")
 
 
 def lib():
@@ -200,6 +201,12 @@ def lib():
     L.gsr_lidar_depth_loss_workspace.argtypes = [ci, ci]
     L.gsr_lidar_depth_loss.restype = ci
     L.gsr_lidar_depth_loss.argtypes = [ci, ci, vp, vp, vp, cf, cf, vp, vp, vp, vp, sz, vp]
+    L.gsr_lidar_occlusion_filter.restype = ci
+    L.gsr_lidar_occlusion_filter.argtypes = [ci, ci, vp, ci, cf, vp, vp, vp]
+    L.gsr_lidar_depth_loss_robust_workspace.restype = sz
+    L.gsr_lidar_depth_loss_robust_workspace.argtypes = [ci, ci]
+    L.gsr_lidar_depth_loss_robust.restype = ci
+    L.gsr_lidar_depth_loss_robust.argtypes = [ci, ci, vp, vp, vp, cf, cf, cf, cf, cf, cf, vp, vp, vp, vp, sz, vp]
     L.gsr_sweep_admit_workspace.restype = sz
     L.gsr_sweep_admit_workspace.argtypes = [ci, ci, ci]
     L.gsr_sweep_admit.restype = ci
@@ -811,6 +818,45 @@ def lidar_depth_loss(depth, acc, lidar_depth, acc_min, lambda_, want_grad_depth=
     _check(lib().gsr_lidar_depth_loss(H, W, _ptr(depth), _ptr(acc), _ptr(lidar_depth), float(acc_min), float(lambda_),
                                       _ptr(out3), _ptr(gd), _ptr(ga), _ptr(ws), nbytes, _stream()))
     return out3, gd, ga
+
+
+def lidar_occlusion_filter(lidar_depth, radius, tol, want_counts=False):
+    """The occlusion filter of a LiDAR depth image in one launch (include/gsraster.h, gsr_lidar_occlusion_filter).
+    lidar_depth: [H,W] or [1,H,W] f32 on the device.  Returns a new image of the same shape -- the input's bits, or 0
+    where the pixel is empty or a return nearer by more than tol * z lies within radius pixels -- and, with
+    want_counts, an int32 device tensor {pixels kept, pixels removed} beside it."""
+    assert lidar_depth.is_cuda and lidar_depth.dtype == torch.float32 and lidar_depth.is_contiguous()
+    assert lidar_depth.dim() >= 2
+    H, W = int(lidar_depth.shape[-2]), int(lidar_depth.shape[-1])
+    assert lidar_depth.numel() == H * W
+    out = torch.empty_like(lidar_depth)
+    counts = torch.empty(2, dtype=torch.int32, device=lidar_depth.device) if want_counts else None
+    _check(lib().gsr_lidar_occlusion_filter(H, W, _ptr(lidar_depth), int(radius), float(tol), _ptr(out), _ptr(counts),
+                                            _stream()))
+    return (out, counts) if want_counts else out
+
+
+def lidar_depth_loss_robust(depth, acc, lidar_depth, acc_min, lambda_, huber_abs, huber_rel, clip_abs, clip_rel,
+                            want_grad_depth=True, want_grad_acc=True, out4=None):
+    """The depth loss with a Huber residual and a clip in three launches (include/gsraster.h,
+    gsr_lidar_depth_loss_robust); the operands of lidar_depth_loss.  Returns (out4 = [loss, mean |depth error| in
+    metres over the supervised pixels, supervised share, clipped share] device tensor, dL/ddepth or None, dL/dacc or
+    None).  out4: a contiguous f32 [4] device view to write into (a row of a caller's result buffer)."""
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    for t in (depth, acc, lidar_depth):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == H * W
+    nbytes = int(lib().gsr_lidar_depth_loss_robust_workspace(H, W))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=depth.device)
+    if out4 is None:
+        out4 = torch.empty(4, dtype=torch.float32, device=depth.device)
+    assert out4.is_cuda and out4.is_contiguous() and out4.dtype == torch.float32 and out4.numel() == 4
+    gd = torch.empty_like(depth) if want_grad_depth else None
+    ga = torch.empty_like(acc) if want_grad_acc else None
+    _check(lib().gsr_lidar_depth_loss_robust(H, W, _ptr(depth), _ptr(acc), _ptr(lidar_depth), float(acc_min),
+                                             float(lambda_), float(huber_abs), float(huber_rel), float(clip_abs),
+                                             float(clip_rel), _ptr(out4), _ptr(gd), _ptr(ga), _ptr(ws), nbytes,
+                                             _stream()))
+    return out4, gd, ga
 
 
 def sweep_admit(points_world, T_cw, K, height, width, depth_tol, occlusion_tol, depth=None, acc=None, image=None,

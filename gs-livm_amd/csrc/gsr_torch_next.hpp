@@ -105,6 +105,20 @@ torch::Tensor lidar_depth_image(const torch::Tensor& points_world, const torch::
 // (Like delta_depth_loss, these two are not part of the oracle/ref_link link check, which stays as it is.)
 torch::Tensor lidar_depth_loss(const torch::Tensor& depth, const torch::Tensor& acc, const torch::Tensor& lidar_depth,
                                float acc_min = 0.5f, float lambda = 1.0f);
+// lidar_occlusion_filter: the LiDAR depth image ([H,W] or [1,H,W] f32 on the device) without the returns seen through
+// the gaps of a nearer surface (gsr_lidar_occlusion_filter: sweep admission's OCCLUDED rule on the supervision image);
+// called once per keyframe behind lidar_depth_image.  radius (0..3) and tol have no default: the caller's policy.
+// Returns a new image; counts (optional) receives an int32 device tensor {pixels kept, pixels removed}.
+torch::Tensor lidar_occlusion_filter(const torch::Tensor& lidar_depth, int64_t radius, float tol,
+                                     torch::Tensor* counts = nullptr);
+// lidar_depth_loss_robust: lidar_depth_loss with a Huber residual (quadratic below huber_abs + huber_rel z_L) and a
+// clip (|depth error| above clip_abs + clip_rel z_L is not supervised; clip_abs = +inf: no clip) as ONE autograd node
+// (gsr_lidar_depth_loss_robust).  At huber_abs = huber_rel = clip_rel = 0 and clip_abs = +inf it returns
+// lidar_depth_loss's bits.  (Like the two above, these are not part of the oracle/ref_link link check, which stays as
+// it is: that check links the reference's own callers, and the reference has no LiDAR depth term.)
+torch::Tensor lidar_depth_loss_robust(const torch::Tensor& depth, const torch::Tensor& acc,
+                                      const torch::Tensor& lidar_depth, float acc_min, float lambda, float huber_abs,
+                                      float huber_rel, float clip_abs, float clip_rel);
 
 // ---- sweep admission (an extension; csrc/seed.hip, gsr_sweep_admit) ----------------------------------------------------
 // The points of a sweep that a keyframe's render does not explain yet, compacted in input order and ready for

@@ -492,6 +492,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("want_counts") = false);
   n.def("lidar_depth_loss", &nx::lidar_depth_loss, py::arg("depth"), py::arg("acc"), py::arg("lidar_depth"),
         py::arg("acc_min") = 0.5f, py::arg("lambda_") = 1.0f);
+  n.def("lidar_occlusion_filter",
+        [](torch::Tensor lidar_depth, int64_t radius, float tol, bool want_counts) -> py::object {
+          torch::Tensor counts;
+          torch::Tensor out = nx::lidar_occlusion_filter(lidar_depth, radius, tol, want_counts ? &counts : nullptr);
+          if (!want_counts) return py::cast(out);
+          return py::make_tuple(out, counts);
+        },
+        py::arg("lidar_depth"), py::arg("radius"), py::arg("tol"), py::arg("want_counts") = false);
+  n.def("lidar_depth_loss_robust", &nx::lidar_depth_loss_robust, py::arg("depth"), py::arg("acc"),
+        py::arg("lidar_depth"), py::arg("acc_min"), py::arg("lambda_"), py::arg("huber_abs"), py::arg("huber_rel"),
+        py::arg("clip_abs"), py::arg("clip_rel"));
   n.def("admit_sweep",
         [opt](torch::Tensor points_world, torch::Tensor T_cw, torch::Tensor K, int64_t height, int64_t width,
               float depth_tol, float occlusion_tol, py::object depth, py::object acc, py::object image,

@@ -292,6 +292,40 @@ struct LidarDepthLossFn : public torch::autograd::Function<LidarDepthLossFn> {
   }
 };
 
+struct RobustLidarDepthLossFn : public torch::autograd::Function<RobustLidarDepthLossFn> {
+  static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor depth, torch::Tensor acc,
+                               torch::Tensor lidar_depth, double acc_min, double lambda, double huber_abs,
+                               double huber_rel, double clip_abs, double clip_rel) {
+    const torch::Tensor d = dev_f32(depth, "depth"), a = dev_f32(acc, "acc"), zl = dev_f32(lidar_depth, "lidar_depth");
+    if (d.dim() < 2) throw std::invalid_argument("lidar_depth_loss_robust: [H,W] or [1,H,W] images");
+    const int64_t H = d.size(-2), W = d.size(-1);
+    if (d.numel() != H * W || a.numel() != H * W || zl.numel() != H * W)
+      throw std::invalid_argument("lidar_depth_loss_robust: three images of one shape [H,W] or [1,H,W]");
+    torch::Tensor gd = depth.requires_grad() ? torch::empty_like(d) : torch::Tensor();
+    torch::Tensor ga = acc.requires_grad() ? torch::empty_like(d) : torch::Tensor();
+    const size_t nbytes = gsr_lidar_depth_loss_robust_workspace(static_cast<int>(H), static_cast<int>(W));
+    torch::Tensor ws = workspace(nbytes, d);
+    torch::Tensor out4 = torch::empty({4}, d.options());
+    check(gsr_lidar_depth_loss_robust(static_cast<int>(H), static_cast<int>(W), fp(d), fp(a), fp(zl),
+                                      static_cast<float>(acc_min), static_cast<float>(lambda),
+                                      static_cast<float>(huber_abs), static_cast<float>(huber_rel),
+                                      static_cast<float>(clip_abs), static_cast<float>(clip_rel),
+                                      out4.data_ptr<float>(), fp(gd), fp(ga), reinterpret_cast<char*>(ws.data_ptr()),
+                                      nbytes, current_stream()),
+          "gsr_lidar_depth_loss_robust");
+    ctx->save_for_backward({gd.defined() ? gd : torch::empty({0}, d.options()),
+                            ga.defined() ? ga.view_as(acc) : torch::empty({0}, d.options())});
+    return out4[0];
+  }
+  static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx,
+                                               torch::autograd::tensor_list grad_outputs) {
+    const auto saved = ctx->get_saved_variables();
+    const torch::Tensor gd = saved[0], ga = saved[1], g = grad_outputs[0];
+    return {scaled(gd, g), scaled(ga, g), torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor(),
+            torch::Tensor(), torch::Tensor(), torch::Tensor()};
+  }
+};
+
 struct ActivateFn : public torch::autograd::Function<ActivateFn> {
   static torch::autograd::tensor_list forward(torch::autograd::AutogradContext* ctx, torch::Tensor scaling_raw,
                                               torch::Tensor rotation_raw, torch::Tensor opacity_raw,
@@ -428,6 +462,32 @@ torch::Tensor lidar_depth_image(const torch::Tensor& points_world, const torch::
 torch::Tensor lidar_depth_loss(const torch::Tensor& depth, const torch::Tensor& acc, const torch::Tensor& lidar_depth,
                                float acc_min, float lambda) {
   return LidarDepthLossFn::apply(depth, acc, lidar_depth, static_cast<double>(acc_min), static_cast<double>(lambda));
+}
+
+torch::Tensor lidar_occlusion_filter(const torch::Tensor& lidar_depth, int64_t radius, float tol,
+                                     torch::Tensor* counts) {
+  torch::NoGradGuard no_grad;
+  const torch::Tensor zl = dev_f32(lidar_depth.detach(), "lidar_depth");
+  if (zl.dim() < 2) throw std::invalid_argument("lidar_occlusion_filter: an [H,W] or [1,H,W] image");
+  const int64_t H = zl.size(-2), W = zl.size(-1);
+  if (zl.numel() != H * W) throw std::invalid_argument("lidar_occlusion_filter: an [H,W] or [1,H,W] image");
+  torch::Tensor out = torch::empty_like(zl);
+  torch::Tensor c2 = counts ? torch::empty({2}, zl.options().dtype(torch::kInt32)) : torch::Tensor();
+  check(gsr_lidar_occlusion_filter(static_cast<int>(H), static_cast<int>(W), fp(zl),
+                                   static_cast<int>(std::max<int64_t>(std::min<int64_t>(radius, 1 << 20), -1)), tol,
+                                   fp(out), counts ? c2.data_ptr<int>() : nullptr, current_stream()),
+        "gsr_lidar_occlusion_filter");
+  if (counts) *counts = c2;
+  return out;
+}
+
+torch::Tensor lidar_depth_loss_robust(const torch::Tensor& depth, const torch::Tensor& acc,
+                                      const torch::Tensor& lidar_depth, float acc_min, float lambda, float huber_abs,
+                                      float huber_rel, float clip_abs, float clip_rel) {
+  return RobustLidarDepthLossFn::apply(depth, acc, lidar_depth, static_cast<double>(acc_min),
+                                       static_cast<double>(lambda), static_cast<double>(huber_abs),
+                                       static_cast<double>(huber_rel), static_cast<double>(clip_abs),
+                                       static_cast<double>(clip_rel));
 }
 
 Admitted admit_sweep(const torch::Tensor& points_world, const torch::Tensor& T_cw, const torch::Tensor& K,

@@ -253,11 +253,50 @@ class LidarDepthLoss(torch.autograd.Function):
         return (gd * g if gd is not None else None), (ga * g if ga is not None else None), None, None, None
 
 
-def lidar_depth_loss(depth, acc, lidar_depth, acc_min=0.5, lambda_=1.0):
+def lidar_occlusion_filter(lidar_depth, radius, tol, want_counts=False):
+    """The LiDAR depth image without the returns seen through the gaps of a nearer surface: a pixel whose window of
+    `radius` pixels (0..3) holds a return nearer by more than tol * z is set to 0, every other pixel keeps its bits
+    (0, negatives and NaN become 0).  The rule of sweep admission's OCCLUDED code, applied to the image the depth loss
+    trains on; called once per keyframe, behind `lidar_depth_image`.  radius and tol have no default: they are the
+    caller's policy, as admit_sweep's tolerances.  Returns a new image; want_counts adds an int32 device tensor
+    {pixels kept, pixels removed}."""
+    return _capi.lidar_occlusion_filter(lidar_depth.detach().contiguous(), radius, tol, want_counts)
+
+
+class RobustLidarDepthLoss(torch.autograd.Function):
+    """LidarDepthLoss with a Huber residual and a clip as one node (csrc/lidar.hip, gsr_lidar_depth_loss_robust): per
+    candidate pixel tau = huber_abs + huber_rel z_L and clip = clip_abs + clip_rel z_L; |e| > clip is not supervised,
+    |e| < tau is quadratic (0.5 e^2 / tau), the rest linear (|e| - tau / 2).  Gradients w.r.t. the rendered depth and
+    silhouette only, scaled by the upstream scalar."""
+
+    @staticmethod
+    def forward(ctx, depth, acc, lidar_depth, acc_min, lambda_, huber_abs, huber_rel, clip_abs, clip_rel):
+        need_d, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        out4, gd, ga = _capi.lidar_depth_loss_robust(depth.contiguous(), acc.contiguous(), lidar_depth.contiguous(),
+                                                     acc_min, lambda_, huber_abs, huber_rel, clip_abs, clip_rel,
+                                                     want_grad_depth=need_d, want_grad_acc=need_a)
+        ctx.grads = (gd, ga)
+        ctx.parts = out4  # [loss, mean |depth error| in metres, supervised share, clipped share] for logging
+        return out4[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        gd, ga = ctx.grads
+        return ((gd * g if gd is not None else None), (ga * g if ga is not None else None)) + (None,) * 7
+
+
+def lidar_depth_loss(depth, acc, lidar_depth, acc_min=0.5, lambda_=1.0, huber=0.0, huber_rel=0.0, clip=float("inf"),
+                     clip_rel=0.0):
     """depth, acc: the second and third outputs of `render` ([H,W] or [1,H,W] f32 on the device, un-normalised);
-    lidar_depth: `lidar_depth_image` of the same view.  acc_min = 0.5 is the threshold of the reference's silhouette
-    masks (lioOptimization.cpp:1786-1792).  Returns the 0-dim loss."""
-    return LidarDepthLoss.apply(depth, acc, lidar_depth, float(acc_min), float(lambda_))
+    lidar_depth: `lidar_depth_image` of the same view (`lidar_occlusion_filter`ed or not).  acc_min = 0.5 is the
+    threshold of the reference's silhouette masks (lioOptimization.cpp:1786-1792).  huber, huber_rel: the residual is
+    quadratic below huber + huber_rel * z_L metres; clip, clip_rel: a pixel whose |depth error| exceeds
+    clip + clip_rel * z_L is not supervised.  At their defaults (no quadratic zone, no clip) this is the plain masked
+    L1 of `LidarDepthLoss`, the same node as ever; otherwise `RobustLidarDepthLoss`.  Returns the 0-dim loss."""
+    if huber == 0.0 and huber_rel == 0.0 and clip == float("inf") and clip_rel == 0.0:
+        return LidarDepthLoss.apply(depth, acc, lidar_depth, float(acc_min), float(lambda_))
+    return RobustLidarDepthLoss.apply(depth, acc, lidar_depth, float(acc_min), float(lambda_), float(huber),
+                                      float(huber_rel), float(clip), float(clip_rel))
 
 
 def raster_K(width, height, FoVx, FoVy):

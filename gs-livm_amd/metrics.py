@@ -68,7 +68,8 @@ def depth_to_u8(depth, max_depth=50.0, out=None):
     return _capi.pack_depth_u8(depth, max_depth, out=out)
 
 
-def evaluate_keyframes(cameras, gts, model, bg, on_frame=None, window11=None, exposures=None, weights=None):
+def evaluate_keyframes(cameras, gts, model, bg, on_frame=None, window11=None, exposures=None, weights=None,
+                       lidar_depths=None, acc_min=0.5):
     """The loop of saveRender (:2198-2231): every keyframe is rendered forward-only and measured against its ground
     truth ([3,H,W] f32 on the device); the per-frame metrics and their running float64 sums stay on the device and are
     copied to the host ONCE, after the last frame (the reference makes two .item() round trips per frame).
@@ -77,8 +78,14 @@ def evaluate_keyframes(cameras, gts, model, bg, on_frame=None, window11=None, ex
     without one; the render is compensated in place (`apply_exposure`) before it is measured and handed to on_frame,
     so that the metrics are not charged for the camera's gain.
     weights: one [H,W] weight map per keyframe (`image_metrics`' weights) or None for a keyframe measured on all pixels.
+    lidar_depths: one [H,W] LiDAR depth image (`lidar_depth_image`, filtered or not) per keyframe or None for a
+    keyframe without one; the render's depth is measured against it forward-only (the plain masked L1 of
+    gsr_lidar_depth_loss_robust at lambda = 1, silhouette threshold acc_min) into a row of the same result buffer.
     -> dict(rows = CPU f32 [n,4] of {psnr, ssim, l1, mse} per frame, totals = CPU f64 [4] = {sum psnr, sum ssim,
-    sum l1, n}, mean_psnr, mean_ssim, frames = n)."""
+    sum l1, n}, mean_psnr, mean_ssim, frames = n); with lidar_depths also depth_rows = CPU f32 [n,4] of {mean |depth
+    error| in metres, the same, supervised share, clipped share = 0} per frame (a NaN row for a keyframe without an
+    image) and mean_depth_error = the mean of the per-frame errors over the keyframes with an image and at least one
+    supervised pixel (NaN when there is none)."""
     cameras, gts = list(cameras), list(gts)
     if len(cameras) != len(gts):
         raise ValueError("one ground-truth image per camera")
@@ -89,24 +96,42 @@ def evaluate_keyframes(cameras, gts, model, bg, on_frame=None, window11=None, ex
     weights = [None] * n if weights is None else list(weights)
     if len(weights) != n:
         raise ValueError("one weight map (or None) per camera")
+    if lidar_depths is not None:
+        lidar_depths = list(lidar_depths)
+        if len(lidar_depths) != n:
+            raise ValueError("one LiDAR depth image (or None) per camera")
     dev = model.Get_xyz().device
     win = (reference_window_1d() if window11 is None else window11).tolist()
     # one buffer, one copy: the four float64 totals in front (8-byte aligned), the n float32 rows behind them
-    buf = torch.zeros(32 + 16 * n, dtype=torch.uint8, device=dev)
-    totals, rows = buf[:32].view(torch.float64), buf[32:].view(torch.float32).view(n, 4)
+    # (and, with LiDAR images, the n float32 depth rows behind those)
+    buf = torch.zeros(32 + 16 * n * (1 if lidar_depths is None else 2), dtype=torch.uint8, device=dev)
+    totals, rows = buf[:32].view(torch.float64), buf[32:32 + 16 * n].view(torch.float32).view(n, 4)
+    if lidar_depths is not None:
+        drows = buf[32 + 16 * n:].view(torch.float32).view(n, 4)
+        drows.fill_(float("nan"))
     with torch.no_grad():
         for i, (cam, gt) in enumerate(zip(cameras, gts)):
-            image, depth, _ = render(cam, model, bg)
+            image, depth, acc = render(cam, model, bg)
             if exposures[i] is not None:
                 image = apply_exposure(image, exposures[i], out=image if image.is_contiguous() else None)
             if weights[i] is None:
                 _capi.image_metrics(image, gt, win, out=rows[i], totals=totals)
             else:
                 _weighted_metrics(image, gt, weights[i], win, rows[i], totals)
+            if lidar_depths is not None and lidar_depths[i] is not None:
+                _capi.lidar_depth_loss_robust(depth.contiguous(), acc.contiguous(), lidar_depths[i].contiguous(),
+                                              acc_min, 1.0, 0.0, 0.0, float("inf"), 0.0, want_grad_depth=False,
+                                              want_grad_acc=False, out4=drows[i])
             if on_frame is not None:
                 on_frame(i, image, depth)
     host = buf.cpu()
-    totals, rows = host[:32].view(torch.float64).clone(), host[32:].view(torch.float32).view(n, 4).clone()
+    totals, rows = host[:32].view(torch.float64).clone(), host[32:32 + 16 * n].view(torch.float32).view(n, 4).clone()
     count = float(totals[3])
     mean = lambda s: float(s) / count if n else float("nan")  # noqa: E731  (the reference divides by count all the same)
-    return dict(rows=rows, totals=totals, mean_psnr=mean(totals[0]), mean_ssim=mean(totals[1]), frames=n)
+    result = dict(rows=rows, totals=totals, mean_psnr=mean(totals[0]), mean_ssim=mean(totals[1]), frames=n)
+    if lidar_depths is not None:
+        drows = host[32 + 16 * n:].view(torch.float32).view(n, 4).clone()
+        seen = drows[:, 2] > 0          # (false for the NaN rows)
+        result["depth_rows"] = drows
+        result["mean_depth_error"] = float(drows[seen, 1].double().mean()) if bool(seen.any()) else float("nan")
+    return result

@@ -559,6 +559,48 @@ int gsr_lidar_depth_loss(int height, int width, const float* depth, const float*
                          float acc_min, float lambda, float* out3, float* dL_ddepth, float* dL_dacc, char* workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- robust LiDAR depth supervision: the occlusion filter of the supervision image, Huber and clip ----
+ * Beside the two calls above, which keep their code and their bits.  The alignment contract is unchanged: float and
+ * int32 arrays need 4-byte alignment and nothing more (no 16-byte access is made), the workspace needs none.
+ *
+ * gsr_lidar_occlusion_filter: lidar_depth and filtered are device [H][W] f32, out of place.  Per pixel, z = lidar_depth[p]:
+ *   !(z > 0) (0, negatives, NaN)                       filtered[p] = +0.0f
+ *   zmin = the smallest q > 0 of lidar_depth over |dx|, |dy| <= radius around the pixel, the window clamped to the
+ *          image and including the pixel itself
+ *   zmin < INFINITY && z - zmin > tol * z              filtered[p] = +0.0f (removed: a return seen through a gap of a
+ *                                                      nearer surface -- the test of gsr_sweep_admit's code 2, in
+ *                                                      float32: one subtraction, one product, one compare)
+ *   otherwise                                          filtered[p] = the bits of z
+ * Every element is WRITTEN.  counts2 (nullable, device, 2 ints) = {pixels kept, pixels removed}.  radius 0 is a
+ * cleaning copy.  One launch (and an 8-byte clear of counts2 on the stream in front of it), no workspace, integer
+ * atomics only (the two counts): the output does not depend on the order of anything, bit for bit.
+ * Refused (GSR_ERR_INVALID_ARGUMENT, nothing launched or written): height or width < 1, height * width >= 2^31, a null
+ * lidar_depth or filtered, radius outside 0..3, tol not finite or < 0, and filtered OVERLAPPING lidar_depth in any
+ * byte (the window reads neighbours: the filter cannot run in place).
+ *
+ * gsr_lidar_depth_loss_robust: gsr_lidar_depth_loss with a quadratic zone near zero and a rejection of outliers.  Per
+ * CANDIDATE pixel (lidar_depth > 0 and A >= acc_min, the comparisons of gsr_lidar_depth_loss), with z_L = lidar_depth:
+ *   q = D / A,  e = q - z_L,  a = |e|,  tau = huber_abs + huber_rel z_L,  clip = clip_abs + clip_rel z_L
+ *   a > clip   CLIPPED: not supervised and not in n_sup, counted in n_clip, both gradients 0 (a NaN a compares false
+ *              and stays supervised, as in gsr_lidar_depth_loss)
+ *   a < tau    rho = 0.5 a (a / tau),  psi = e / tau
+ *   otherwise  rho = a - 0.5 tau,      psi = sign(e), sign(0) = 0
+ *   L = lambda * sum rho / max(n_sup, 1)
+ *   out4 (device) = {L, sum a / max(n_sup, 1) over the supervised pixels (metres), n_sup / (H W), n_clip / (H W)}
+ *   dL/dD = (c psi) / A,  dL/dA = -(dL/dD) q,  c = lambda / n_sup narrowed once; 0 elsewhere; every element WRITTEN.
+ * With huber_abs = huber_rel = clip_rel = 0 and clip_abs = +inf, out4[0..2] and both gradients are those of
+ * gsr_lidar_depth_loss BIT FOR BIT and out4[3] == 0.  Three launches (two without gradients), deterministic, no host
+ * synchronisation, no allocation, no float atomics.
+ * Refused as gsr_lidar_depth_loss refuses, and: huber_abs, huber_rel or clip_rel negative, NaN or infinite; clip_abs
+ * negative or NaN (+inf is allowed: no clip); workspace_bytes below gsr_lidar_depth_loss_robust_workspace. */
+int gsr_lidar_occlusion_filter(int height, int width, const float* lidar_depth, int radius, float tol, float* filtered,
+                               int* counts2, void* stream);
+size_t gsr_lidar_depth_loss_robust_workspace(int height, int width);
+int gsr_lidar_depth_loss_robust(int height, int width, const float* depth, const float* acc, const float* lidar_depth,
+                                float acc_min, float lambda, float huber_abs, float huber_rel, float clip_abs,
+                                float clip_rel, float* out4, float* dL_ddepth, float* dL_dacc, char* workspace,
+                                size_t workspace_bytes, void* stream);
+
 /* ---- sweep admission: the points of a LiDAR sweep that a keyframe's render does not explain yet ----
  * An extension (the reference seeds a voxel once, whatever the map holds, and colours the points on the host from the
  * nearest pixel without an occlusion test): the producer-side step in front of gsr_init_gaussians.
