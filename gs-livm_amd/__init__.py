@@ -7,6 +7,8 @@ Layout (only what the hot path needs):
   render_utils.py  Camera (rasterizer-facing part) and render() as in include/gs/gs/render_utils.cuh
   seed.py          sweep admission: the points of a LiDAR sweep a keyframe's render does not explain yet, coloured from
                    the keyframe and sized by their pixel footprint, ready for add_new_pointcloud (csrc/seed.hip)
+  voxelmap.py      the sweep voxel map: a persistent device voxel table with exact moments, one oriented Gaussian per
+                   matured voxel, the voxel key of every sweep point (csrc/voxel.hip)
   loss.py          fused L1 + SSIM photometric loss (SURVEY.md 8(f) "next" row 2); fused LiDAR similarity loss; fused
                    delta-depth loss between keyframe pairs; LiDAR depth supervision (sweep z-buffer + masked depth L1,
                    its occlusion filter, Huber residual and clip);
@@ -39,6 +41,7 @@ from .metrics import depth_to_u8, evaluate_keyframes, image_metrics, psnr, side_
 from .model import FusedActivations, FusedAdam, GaussianParameters, GrowableAdam, GrowableGaussians, VoxelIndex, prune_rows  # noqa: F401
 from . import ply  # noqa: F401
 from .seed import Admitted, admit_sweep  # noqa: F401
+from .voxelmap import SweepVoxelMap, VoxelSeeds  # noqa: F401
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer,  # noqa: F401
                          rasterize_gaussians)
 from .render_utils import Camera, get_projection_matrix, render, render_full, se3_exp  # noqa: F401
@@ -61,5 +64,5 @@ def torch_ops():
     return mod
 
 
-__all__ = ["Admitted", "admit_sweep", "WeightedPhotometricLoss", "weighted_photometric_loss", "Contribution", "contribution", "render_contribution", "low_contribution", "KeyframeVisibility", "visibility_pack", "covisibility", "observation_count", "visibility_remap", "iou", "overlap_coefficient", "ExposureLoss", "exposure_photometric_loss", "apply_exposure", "identity_exposure", "LidarDepthLoss", "RobustLidarDepthLoss", "lidar_occlusion_filter", "lidar_depth_image", "lidar_depth_loss", "raster_K", "world_to_camera", "prune_rows", "image_metrics", "psnr", "to_u8", "side_by_side", "depth_to_u8", "evaluate_keyframes", "DeltaDepthLoss", "delta_depth_loss", "delta_pose", "SimilarityLoss", "similarity_loss", "VoxelIndex", "PhotometricLoss", "photometric_loss", "reference_window_1d", "FusedActivations", "FusedAdam", "GaussianParameters", "GrowableAdam", "GrowableGaussians", "ply", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "Camera", "render", "render_full", "se3_exp", "pose_gradient", "get_projection_matrix", "rasterize_forward",
+__all__ = ["Admitted", "admit_sweep", "SweepVoxelMap", "VoxelSeeds", "WeightedPhotometricLoss", "weighted_photometric_loss", "Contribution", "contribution", "render_contribution", "low_contribution", "KeyframeVisibility", "visibility_pack", "covisibility", "observation_count", "visibility_remap", "iou", "overlap_coefficient", "ExposureLoss", "exposure_photometric_loss", "apply_exposure", "identity_exposure", "LidarDepthLoss", "RobustLidarDepthLoss", "lidar_occlusion_filter", "lidar_depth_image", "lidar_depth_loss", "raster_K", "world_to_camera", "prune_rows", "image_metrics", "psnr", "to_u8", "side_by_side", "depth_to_u8", "evaluate_keyframes", "DeltaDepthLoss", "delta_depth_loss", "delta_pose", "SimilarityLoss", "similarity_loss", "VoxelIndex", "PhotometricLoss", "photometric_loss", "reference_window_1d", "FusedActivations", "FusedAdam", "GaussianParameters", "GrowableAdam", "GrowableGaussians", "ply", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "Camera", "render", "render_full", "se3_exp", "pose_gradient", "get_projection_matrix", "rasterize_forward",
            "rasterize_backward", "mark_visible", "state_views", "set_reference_rects", "reference_rects", "last_num_rendered", "set_binning_capacity_hint", "speculation_stats", "emit_guard_trips", "mailbox_slow_path_last", "set_near_far", "set_near_far_thread", "set_reference_rects_thread", "async_outcomes_pending", "set_near_far_hints", "last_near_far", "set_far_speculation", "last_far_skipped", "NumRendered", "lib", "torch_ops", "synthetic", "multiview", "GsrError", "LIB_PATH"]

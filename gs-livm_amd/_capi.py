@@ -76,7 +76,8 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_covisibility", "gsr_observation_count", "gsr_visibility_remap", "gsr_contribution_workspace",
            "gsr_contribution", "gsr_contribution_finish", "gsr_weighted_loss", "gsr_weighted_loss_workspace",
            "gsr_sweep_admit", "gsr_sweep_admit_workspace", "gsr_lidar_occlusion_filter",
-           "gsr_lidar_depth_loss_robust", "gsr_lidar_depth_loss_robust_workspace")
+           "gsr_lidar_depth_loss_robust", "gsr_lidar_depth_loss_robust_workspace", "gsr_voxel_table_bytes",
+           "gsr_voxel_sweep_workspace", "gsr_voxel_sweep", "gsr_voxel_rehash")
 
 
 def lib():
@@ -212,6 +213,14 @@ def lib():
     L.gsr_sweep_admit.restype = ci
     L.gsr_sweep_admit.argtypes = [ci, vp, vp, C.POINTER(cf), C.POINTER(cf), ci, ci, cf, cf, vp, vp, cf, cf, vp, ci, cf,
                                   vp, vp, cf, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.gsr_voxel_table_bytes.restype = sz
+    L.gsr_voxel_table_bytes.argtypes = [C.c_longlong]
+    L.gsr_voxel_sweep_workspace.restype = sz
+    L.gsr_voxel_sweep_workspace.argtypes = [ci]
+    L.gsr_voxel_sweep.restype = ci
+    L.gsr_voxel_sweep.argtypes = [ci, vp, vp, cf, ci, cf, cf, vp, C.c_longlong, ci] + [vp] * 11 + [vp, sz, vp]
+    L.gsr_voxel_rehash.restype = ci
+    L.gsr_voxel_rehash.argtypes = [vp, C.c_longlong, vp, C.c_longlong, vp]
     L.gsr_image_metrics_workspace.restype = sz
     L.gsr_image_metrics_workspace.argtypes = [ci, ci, ci]
     L.gsr_image_metrics.restype = ci
@@ -913,6 +922,61 @@ def _out_ptr(t):
         return None
     assert t.is_cuda and t.is_contiguous()
     return C.c_void_p(t.data_ptr())
+
+
+def voxel_table(capacity, device):
+    """A zeroed voxel table of `capacity` slots (a power of two): int64 [capacity, 16] on `device`."""
+    nbytes = int(lib().gsr_voxel_table_bytes(int(capacity)))
+    if nbytes == 0:
+        raise GsrError("voxel_table: capacity %r is not a power of two up to 2^26" % (capacity,))
+    return torch.zeros((nbytes // 128, 16), dtype=torch.int64, device=device)
+
+
+def voxel_sweep(points, colors, grid, min_points, min_sigma, scale_factor, table, live_before, out=None,
+                workspace=None):
+    """One sweep into the voxel table in four launches (include/gsraster.h, gsr_voxel_sweep).  points: [n,3] f32 on the
+    device (n == 0 is legal); colors: [n,3] f32 (0..255) or None; table: int64 [capacity,16] (voxel_table), changed in
+    place; live_before: the live keys the previous call reported.  out: a dict of contiguous device tensors of max(n, 1)
+    rows to write (status uint8 [n], point_keys int64 [n], xyz [n,3], covs [n,9], rgb [n,3], keys int64 [n], points
+    int32 [n], scaling [n,3], rotation [n,4], normal [n,3]) or None = new ones.  No host wait.  Returns (the dict with
+    FULL-length outputs -- seed rows at and behind counts[4] are not written -- and counts int32 [6] on the device)."""
+    assert points.is_cuda and points.dtype == torch.float32 and points.is_contiguous()
+    assert points.dim() == 2 and points.size(1) == 3
+    n, dev = int(points.size(0)), points.device
+    assert colors is None or (colors.is_cuda and colors.is_contiguous() and colors.dtype == torch.float32
+                              and tuple(colors.shape) == (n, 3))
+    assert table.is_cuda and table.is_contiguous() and table.dtype == torch.int64 and table.dim() == 2 \
+        and table.size(1) == 16
+    if out is None:
+        r = max(n, 1)
+        f = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
+        out = dict(status=torch.empty(r, dtype=torch.uint8, device=dev),
+                   point_keys=torch.empty(r, dtype=torch.int64, device=dev), xyz=f(r, 3), covs=f(r, 9),
+                   rgb=f(r, 3) if colors is not None else None, keys=torch.empty(r, dtype=torch.int64, device=dev),
+                   points=torch.empty(r, dtype=torch.int32, device=dev), scaling=f(r, 3), rotation=f(r, 4),
+                   normal=f(r, 3))
+    nbytes = int(lib().gsr_voxel_sweep_workspace(n))
+    if workspace is None:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    counts = torch.empty(6, dtype=torch.int32, device=dev)
+    _check(lib().gsr_voxel_sweep(n, _ptr(points), _ptr(colors), float(grid), int(min_points), float(min_sigma),
+                                 float(scale_factor), C.c_void_p(table.data_ptr()), int(table.size(0)),
+                                 int(live_before), _out_ptr(out["status"]), _out_ptr(out["point_keys"]),
+                                 _out_ptr(out["xyz"]), _out_ptr(out["covs"]), _out_ptr(out.get("rgb")),
+                                 _out_ptr(out["keys"]), _out_ptr(out["points"]), _out_ptr(out["scaling"]),
+                                 _out_ptr(out["rotation"]), _out_ptr(out["normal"]), C.c_void_p(counts.data_ptr()),
+                                 C.c_void_p(workspace.data_ptr()) if nbytes else None, min(nbytes, workspace.numel()),
+                                 _stream()))
+    return out, counts
+
+
+def voxel_rehash(src, dst):
+    """Every record of the voxel table src into the zeroed, not smaller table dst (gsr_voxel_rehash): one launch."""
+    for t in (src, dst):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.int64 and t.dim() == 2 and t.size(1) == 16
+    _check(lib().gsr_voxel_rehash(C.c_void_p(src.data_ptr()), int(src.size(0)), C.c_void_p(dst.data_ptr()),
+                                  int(dst.size(0)), _stream()))
+    return dst
 
 
 def image_metrics(img, gt, window11, out=None, totals=None):

@@ -39,6 +39,8 @@ UNITS = {
     "lidar.hip": [],
     # sweep admission is restated bit for bit on dyadic inputs; its multiply-adds are explicit (gsr_lidar_project.hpp)
     "seed.hip": ["-ffp-contract=off"],
+    # the voxel map's float64 means and covariances are restated operation for operation on the host (tests/voxel_ref.py)
+    "voxel.hip": ["-ffp-contract=off"],
     "prune.hip": [],
     "covis.hip": [],  # (integer arithmetic throughout: no floating-point flag bears on it)
     "contrib.hip": [],  # (entry points + the finish kernel; the walk is built with render.hip, whose alpha it recomputes)

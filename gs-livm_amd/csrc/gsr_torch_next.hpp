@@ -147,6 +147,31 @@ Admitted admit_sweep(const torch::Tensor& points_world, const torch::Tensor& T_c
                      const torch::Tensor& covs = torch::Tensor(), const torch::Tensor& exposure = torch::Tensor(),
                      const SweepAdmitOptions& options = SweepAdmitOptions());
 
+// ---- the sweep voxel map (an extension; csrc/voxel.hip, gsr_voxel_sweep) -----------------------------------------------
+// A persistent voxel table on the device with exact, order-independent per-voxel moments, and one oriented Gaussian per
+// voxel that matures: what stands between admit_sweep and GrowableGaussians::add_new_pointcloud, where the reference
+// walks an unordered_map on the host (GpMap::splitPointsIntoCell / dividePointsIntoCellInitMap, src/gp3d/map.cpp).
+// grid, min_points and min_sigma have no default: the caller's policy.  voxel_sweep doubles the table BEFORE the launch
+// while live + n > capacity / 2, so no point is ever FULL; one host wait: the read of the counts.  The seed tensors
+// are views of the first `matured` rows, in the order of first appearance; status / point_keys have one entry per
+// point.  (Like admit_sweep, not part of the oracle/ref_link link check, which stays as it is.)
+struct VoxelMap {
+  torch::Tensor table;  // int64 [capacity,16] on the device: voxel_table()
+  int64_t live = 0;     // the keys it holds
+  float grid = 0.f, min_sigma = 0.f;
+  int64_t min_points = 0;
+};
+struct VoxelSeeds {
+  torch::Tensor xyz, covs, rgbs, keys, points, scaling_raw, rotation, normal;  // [v,3] [v,3,3] [v,3]|undefined i64[v] i32[v] [v,3] [v,4] [v,3]
+  torch::Tensor status, point_keys;                                           // uint8 [n], int64 [n]
+  std::array<int64_t, 6> counts;                                               // accumulated, seeded, out, full, matured, live keys
+};
+torch::Tensor voxel_table(int64_t capacity, const torch::Tensor& like);  // zeroed; capacity a power of two
+// every record of `table` in a new zeroed table of `capacity` slots (gsr_voxel_rehash)
+torch::Tensor voxel_rehash(const torch::Tensor& table, int64_t capacity);
+VoxelSeeds voxel_sweep(VoxelMap& map, const torch::Tensor& points, const torch::Tensor& colors = torch::Tensor(),
+                       float scale_factor = 1.0f);
+
 // ---- the evaluation pass (saveRender, src/liw/lioOptimization.cpp:2182-2245; the status line of optimize_vis) ------
 // [psnr, ssim, l1, mse] of image against gt ([C,H,W] f32 on the device) on the kernels of csrc/metrics.hip, a device
 // tensor, no graph: gaussian_splatting::psnr (loss_utils.cuh:89-93, the mean of the per-channel PSNRs, +inf where a

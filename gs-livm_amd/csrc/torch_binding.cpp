@@ -528,6 +528,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("footprint") = 1.0f, py::arg("min_depth") = 0.2f,
         py::arg("max_depth") = std::numeric_limits<float>::infinity(), py::arg("one_per_pixel") = true,
         py::arg("want_reasons") = false);
+  n.def("voxel_table", &nx::voxel_table, py::arg("capacity"), py::arg("like"));
+  n.def("voxel_rehash", &nx::voxel_rehash, py::arg("table"), py::arg("capacity"));
+  n.def("voxel_sweep",
+        [opt](torch::Tensor table, int64_t live, torch::Tensor points, py::object colors, float grid,
+              int64_t min_points, float min_sigma, float scale_factor) {
+          nx::VoxelMap map;
+          map.table = table; map.live = live; map.grid = grid; map.min_points = min_points; map.min_sigma = min_sigma;
+          const nx::VoxelSeeds v = nx::voxel_sweep(map, points, opt(colors), scale_factor);
+          auto none_or = [](const torch::Tensor& t) -> py::object { return t.defined() ? py::cast(t) : py::none(); };
+          py::list counts;
+          for (int64_t c : v.counts) counts.append(c);
+          return py::make_tuple(py::make_tuple(v.xyz, v.covs, none_or(v.rgbs), v.keys, v.points, v.scaling_raw,
+                                               v.rotation, v.normal, v.status, v.point_keys, py::tuple(counts)),
+                                map.table, map.live);
+        },
+        py::arg("table"), py::arg("live"), py::arg("points"), py::arg("colors"), py::arg("grid"),
+        py::arg("min_points"), py::arg("min_sigma"), py::arg("scale_factor") = 1.0f);
   n.def("image_metrics",
         [opt](torch::Tensor image, torch::Tensor gt, py::object window, py::object totals, py::object weights) {
           return nx::image_metrics(image, gt, opt(window), opt(totals), opt(weights));

@@ -539,6 +539,74 @@ Admitted admit_sweep(const torch::Tensor& points_world, const torch::Tensor& T_c
   return out;
 }
 
+torch::Tensor voxel_table(int64_t capacity, const torch::Tensor& like) {
+  const size_t nbytes = gsr_voxel_table_bytes(capacity);
+  if (!nbytes) throw std::invalid_argument("voxel_table: the capacity is a power of two up to 2^26");
+  return torch::zeros({capacity, 16}, like.options().dtype(torch::kInt64));
+}
+
+torch::Tensor voxel_rehash(const torch::Tensor& table, int64_t capacity) {
+  if (!table.defined() || !table.is_cuda() || table.scalar_type() != torch::kInt64 || table.dim() != 2 ||
+      table.size(1) != 16 || !table.is_contiguous())
+    throw std::invalid_argument("voxel_rehash: the table is a contiguous int64 [capacity,16] tensor on the device");
+  torch::Tensor dst = voxel_table(capacity, table);
+  check(gsr_voxel_rehash(reinterpret_cast<const long long*>(table.data_ptr<int64_t>()), table.size(0),
+                         reinterpret_cast<long long*>(dst.data_ptr<int64_t>()), capacity, current_stream()),
+        "gsr_voxel_rehash");
+  return dst;
+}
+
+VoxelSeeds voxel_sweep(VoxelMap& map, const torch::Tensor& points, const torch::Tensor& colors, float scale_factor) {
+  torch::NoGradGuard no_grad;
+  const torch::Tensor p = dev_f32(points.detach(), "points");
+  if (p.dim() != 2 || p.size(1) != 3) throw std::invalid_argument("voxel_sweep: points is [n,3]");
+  const int64_t n = p.size(0);
+  torch::Tensor c;
+  if (colors.defined()) {
+    c = dev_f32(colors.detach(), "colors");
+    if (c.dim() != 2 || c.size(0) != n || c.size(1) != 3) throw std::invalid_argument("voxel_sweep: colors is [n,3]");
+  }
+  if (!map.table.defined() || map.table.scalar_type() != torch::kInt64 || map.table.dim() != 2 ||
+      map.table.size(1) != 16 || !map.table.is_contiguous() || map.table.device() != p.device())
+    throw std::invalid_argument("voxel_sweep: the table is a contiguous int64 [capacity,16] tensor on the points' device");
+  while (2 * (map.live + n) > map.table.size(0)) map.table = voxel_rehash(map.table, 2 * map.table.size(0));
+  const int64_t rows = std::max<int64_t>(n, 1);
+  const auto i32 = p.options().dtype(torch::kInt32), i64 = p.options().dtype(torch::kInt64);
+  torch::Tensor status = torch::empty({rows}, p.options().dtype(torch::kByte)), point_keys = torch::empty({rows}, i64),
+                xyz = torch::empty({rows, 3}, p.options()), cov = torch::empty({rows, 9}, p.options()),
+                rgb = c.defined() ? torch::empty({rows, 3}, p.options()) : torch::Tensor(),
+                keys = torch::empty({rows}, i64), pts = torch::empty({rows}, i32),
+                scaling = torch::empty({rows, 3}, p.options()), rotation = torch::empty({rows, 4}, p.options()),
+                normal = torch::empty({rows, 3}, p.options()), counts = torch::empty({6}, i32);
+  const size_t nbytes = gsr_voxel_sweep_workspace(static_cast<int>(n));
+  torch::Tensor ws = workspace(nbytes, p);
+  check(gsr_voxel_sweep(static_cast<int>(n), fp(p), fp(c), map.grid, static_cast<int>(map.min_points), map.min_sigma,
+                        scale_factor, reinterpret_cast<long long*>(map.table.data_ptr<int64_t>()), map.table.size(0),
+                        static_cast<int>(map.live), status.data_ptr<uint8_t>(),
+                        reinterpret_cast<long long*>(point_keys.data_ptr<int64_t>()), xyz.data_ptr<float>(),
+                        cov.data_ptr<float>(), fp(rgb), reinterpret_cast<long long*>(keys.data_ptr<int64_t>()),
+                        pts.data_ptr<int>(), scaling.data_ptr<float>(), rotation.data_ptr<float>(),
+                        normal.data_ptr<float>(), counts.data_ptr<int>(), reinterpret_cast<char*>(ws.data_ptr<uint8_t>()),
+                        nbytes, current_stream()),
+        "gsr_voxel_sweep");
+  VoxelSeeds out;
+  const torch::Tensor host = counts.to(torch::kCPU);  // the one host wait
+  for (int q = 0; q < 6; q++) out.counts[q] = host.data_ptr<int>()[q];
+  const int64_t v = out.counts[4];
+  map.live = out.counts[5];
+  out.xyz = xyz.slice(0, 0, v);
+  out.covs = cov.slice(0, 0, v).view({v, 3, 3});
+  if (rgb.defined()) out.rgbs = rgb.slice(0, 0, v);
+  out.keys = keys.slice(0, 0, v);
+  out.points = pts.slice(0, 0, v);
+  out.scaling_raw = scaling.slice(0, 0, v);
+  out.rotation = rotation.slice(0, 0, v);
+  out.normal = normal.slice(0, 0, v);
+  out.status = status.slice(0, 0, n);
+  out.point_keys = point_keys.slice(0, 0, n);
+  return out;
+}
+
 torch::Tensor image_metrics(const torch::Tensor& image, const torch::Tensor& gt, const torch::Tensor& window1d,
                             const torch::Tensor& totals, const torch::Tensor& weights) {
   torch::NoGradGuard no_grad;

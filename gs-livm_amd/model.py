@@ -417,6 +417,24 @@ class GrowableGaussians(GaussianParameters):
         return lo, hi, a.counts
 
     @torch.no_grad()
+    def add_voxel_seeds(self, seeds, oriented=True, scale_factor=1.0):
+        """Appends the Gaussians of voxelmap.SweepVoxelMap.sweep (`seeds`, a VoxelSeeds from a sweep WITH colours), one
+        per matured voxel, each registered in `self.voxel_index` under its voxel key with count 1 -- so that
+        calc_simi_loss selects them.  `add_new_pointcloud` initialises the rows (from the covariances' diagonals, as it
+        always does, with `scale_factor`); with `oriented` the scaling and the rotation are then overwritten by the
+        seeds' own, which hold the SWEEP's scale_factor: flat surfels along the voxel's axes instead of axis-aligned
+        boxes.  oriented=False is exactly add_new_pointcloud.  Returns the row range."""
+        if seeds.rgbs is None:
+            raise ValueError("add_voxel_seeds: the sweep had no colours")
+        v = int(seeds.xyz.size(0))
+        lo, hi = self.add_new_pointcloud(seeds.xyz, seeds.covs, seeds.rgbs, scale_factor,
+                                         voxel_keys=seeds.keys.tolist(), voxel_counts=[1] * v)
+        if oriented and v:
+            self._buf["_scaling"][lo:hi].copy_(seeds.scaling_raw)
+            self._buf["_rotation"][lo:hi].copy_(seeds.rotation)
+        return lo, hi
+
+    @torch.no_grad()
     def prune(self, min_opacity=1.0 / 255.0, max_scale=0.3, drop_nonfinite=True, drop=None):
         """Removes the rows that are dead to the rasterizer for good -- the shrinking counterpart of add_new_pointcloud,
         GaussianModel::prune_optimizer (src/gs/gaussian.cu:430-449) for all six groups at once.  A row leaves when

@@ -650,6 +650,76 @@ int gsr_sweep_admit(int n, const float* points_world, const float* covs_in, cons
                     float* z_out, unsigned char* reasons, int* counts6, char* workspace, size_t workspace_bytes,
                     void* stream);
 
+/* ---- the sweep voxel map: fused voxel moments and one oriented Gaussian per matured voxel ----
+ * An extension between gsr_sweep_admit and gsr_init_gaussians: where the reference voxelises a sweep with a serial
+ * unordered_map walk on the host (GpMap::splitPointsIntoCell / dividePointsIntoCellInitMap, src/gp3d/map.cpp) and runs
+ * a Gaussian-process regression per voxel, this keeps a PERSISTENT voxel table on the device with exact,
+ * order-independent moments and seeds ONE oriented Gaussian (a surfel) per voxel from them.
+ *
+ * Definitions, with g = (double)grid and Q = 2^20, for a point p (three f32):
+ *   t_k = (double)p_k / g,  c_k = floor(t_k)  (floor, not truncation: -1e-9 lies in cell -1);  the point is OUT when a
+ *     t_k is not finite or |c_k| >= Q
+ *   key = ((c_x + Q) << 42) | ((c_y + Q) << 21) | (c_z + Q): injective, positive, never 0 (0 marks an empty slot)
+ *   q_k = min(Q - 1, (int64)floor((t_k - c_k) * Q))  (the clamp matters: for p = -1e-30, t - c rounds to 1.0)
+ *   per voxel, unsigned 64-bit, added with INTEGER atomics only: count;  S1[3] = sum q_k;  S2[6] = sum q_i q_j in the
+ *     order (xx, xy, xz, yy, yz, zz);  with colors (nullable, device [n][3] f32, 0..255):
+ *     SC[3] = sum clamp(llrint(c * 256), 0, 65535), a NaN counting as 0
+ *   Integer addition commutes: the sums are the same bits for every thread order and every permutation of the sweep.
+ *   n <= 2^22 per call, min_points <= 2^20 and a matured voxel closes, so count < 2^23 and S2 < 2^63.
+ *   From the sums, in float64, uncontracted, in this order:
+ *     a_k = S1_k / count;  mean m_k = (c_k + (a_k + 0.5) / Q) * g
+ *     population covariance C_ij = (S2_ij / count - a_i * a_j) * ((g / Q) * (g / Q));  colour SC / (256 * count)
+ *
+ * The table is the caller's: capacity slots of 16 int64 (128 bytes: key, closed, count, S1, S2, SC, and a word that is
+ * zero between calls), capacity a power of two up to 2^26, ZEROED before its first use, 8-byte aligned.
+ * gsr_voxel_table_bytes(capacity) = 128 * capacity, or 0 for a refused capacity.
+ *
+ * gsr_voxel_sweep: one call per sweep, four launches (one when n == 0), no host synchronisation, no allocation.
+ *   insert   every point finds or claims its voxel's slot (open addressing, 64-bit compare-and-swap on the key, at
+ *            most `capacity` probes) and gets status[i] (device, n bytes) and point_keys[i] (device int64, -1 for OUT):
+ *              0 ACCUMULATED  the sums above were added
+ *              1 SEEDED       the voxel matured in an EARLIER call: nothing changes (a similarity-loss point)
+ *              2 OUT          out of range or not finite
+ *              3 FULL         no slot within `capacity` probes: nothing changes
+ *            The status is decided by the closed flag as the previous call left it; nothing in the call's insert
+ *            writes that flag.  Below a full table both outputs are deterministic; slot numbers are never exposed.
+ *   harvest  a voxel matures when this call accumulated into it and count >= min_points.  The matured voxels are
+ *            emitted in the order of their smallest point index in this call -- the order of first appearance -- and
+ *            closed.  Row j of the outputs (each holds n rows; rows at and behind the matured count are NOT written):
+ *              xyz_out[j]       the mean;  keys_out[j] the key (int64);  points_out[j] the count
+ *              covs_out[j]      [3][3] f32, symmetric: V diag(lam) V^T, lam the eigenvalues of C in DESCENDING order,
+ *                               each clamped below at min_sigma^2, V's columns the axes, made right-handed (cyclic
+ *                               Jacobi in float64, a fixed number of sweeps: the same bits on every run)
+ *              scaling_out[j]   log(sqrt(lam * scale_factor)): gsr_init_gaussians' scaling of a diagonal covariance
+ *              rotation_out[j]  the quaternion (w, x, y, z), w >= 0, normalised, of the rotation R whose columns are
+ *                               the axes: Sigma = R S^2 R^T, what the rasterizer builds from (scale, rotation)
+ *              normal_out[j]    the axis of the smallest eigenvalue (its sign is arbitrary)
+ *              rgb_out[j]       the colour, written only with colors
+ *   counts6 (device, 6 ints) = {accumulated, seeded, out, full, matured, live keys}; the first four sum to n; live keys
+ *   = live_before + the keys this call inserted, live_before being what the previous call on this table reported
+ *   (0 for a zeroed table, unchanged by gsr_voxel_rehash).
+ * Keep live keys + n <= capacity / 2 (grow with gsr_voxel_rehash first) and no point is ever FULL.
+ * gsr_voxel_sweep_workspace(n): the bytes of workspace the call needs (0 for n == 0 or a refused n); any alignment.
+ *
+ * gsr_voxel_rehash: every record of src into dst, a ZEROED table that is not smaller; one launch, one thread per source
+ * slot.  The two tables hold the same records afterwards.
+ *
+ * Refused (GSR_ERR_INVALID_ARGUMENT, nothing launched or written), in this order: n outside 0..2^22; min_points
+ * outside 1..2^20; grid, min_sigma or scale_factor not finite or <= 0; capacity not a power of two in 1..2^26;
+ * live_before outside 0..capacity; a null table or counts6, or with n > 0 a null points, status, point_keys or seed
+ * output (rgb_out only with colors); workspace_bytes below the query; a null workspace with n > 0; a float or int32
+ * array off 4-byte alignment; the table, point_keys or keys_out off 8-byte alignment.  gsr_voxel_rehash: a refused
+ * capacity; capacity_dst < capacity_src; a null or misaligned table; src == dst. */
+size_t gsr_voxel_table_bytes(long long capacity);
+size_t gsr_voxel_sweep_workspace(int n);
+int gsr_voxel_sweep(int n, const float* points, const float* colors, float grid, int min_points, float min_sigma,
+                    float scale_factor, long long* table, long long capacity, int live_before, unsigned char* status,
+                    long long* point_keys, float* xyz_out, float* covs_out, float* rgb_out, long long* keys_out,
+                    int* points_out, float* scaling_out, float* rotation_out, float* normal_out, int* counts6,
+                    char* workspace, size_t workspace_bytes, void* stream);
+int gsr_voxel_rehash(const long long* src, long long capacity_src, long long* dst, long long capacity_dst,
+                     void* stream);
+
 /* ---- the evaluation pass around a forward-only render: PSNR, SSIM and 8-bit frame export ----
  * gsr_image_metrics: out4 (device) = {psnr, ssim, l1, mse} of img against gt, [channels][H][W] device f32, in two
  * launches:
