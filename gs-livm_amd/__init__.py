@@ -9,7 +9,8 @@ Layout (only what the hot path needs):
                    the keyframe and sized by their pixel footprint, ready for add_new_pointcloud (csrc/seed.hip)
   voxelmap.py      the sweep voxel map: a persistent device voxel table with exact moments, one oriented Gaussian per
                    matured voxel, the voxel key of every sweep point (csrc/voxel.hip)
-  loss.py          fused L1 + SSIM photometric loss (SURVEY.md 8(f) "next" row 2); fused LiDAR similarity loss; fused
+  loss.py          fused L1 + SSIM photometric loss (SURVEY.md 8(f) "next" row 2); fused LiDAR similarity loss; the fused
+                   point-to-plane loss on oriented surfels (csrc/surfel.hip); fused
                    delta-depth loss between keyframe pairs; LiDAR depth supervision (sweep z-buffer + masked depth L1,
                    its occlusion filter, Huber residual and clip);
                    per-keyframe exposure compensation fused into the photometric loss; the weighted photometric loss
@@ -28,11 +29,11 @@ from . import multiview, synthetic  # noqa: F401
 from ._capi import (GsrError, LIB_PATH, NumRendered, emit_guard_trips, last_num_rendered, lib, mailbox_slow_path_last, mark_visible,
                     set_binning_capacity_hint, speculation_stats, set_near_far, set_near_far_thread, set_reference_rects_thread, async_outcomes_pending, set_near_far_hints, last_near_far, set_far_speculation, last_far_skipped, profile_enable, profile_read,  # noqa: F401
                     pose_gradient, rasterize_backward, rasterize_forward, reference_rects, set_reference_rects, state_views)
-from .loss import (DeltaDepthLoss, ExposureLoss, LidarDepthLoss, RobustLidarDepthLoss, PhotometricLoss, SimilarityLoss, WeightedPhotometricLoss, delta_depth_loss, delta_pose,  # noqa: F401
+from .loss import (DeltaDepthLoss, ExposureLoss, LidarDepthLoss, RobustLidarDepthLoss, PhotometricLoss, SimilarityLoss, SurfelPlaneLoss, WeightedPhotometricLoss, delta_depth_loss, delta_pose,  # noqa: F401
                    weighted_photometric_loss,
                    apply_exposure, exposure_photometric_loss, identity_exposure, lidar_depth_image, lidar_depth_loss,
                    lidar_occlusion_filter,
-                   photometric_loss, raster_K, reference_window_1d, similarity_loss,
+                   photometric_loss, raster_K, reference_window_1d, similarity_loss, surfel_plane_loss,
                    world_to_camera)
 from .covis import (KeyframeVisibility, covisibility, iou, observation_count, overlap_coefficient,  # noqa: F401
                     visibility_pack, visibility_remap)
@@ -64,5 +65,5 @@ def torch_ops():
     return mod
 
 
-__all__ = ["Admitted", "admit_sweep", "SweepVoxelMap", "VoxelSeeds", "WeightedPhotometricLoss", "weighted_photometric_loss", "Contribution", "contribution", "render_contribution", "low_contribution", "KeyframeVisibility", "visibility_pack", "covisibility", "observation_count", "visibility_remap", "iou", "overlap_coefficient", "ExposureLoss", "exposure_photometric_loss", "apply_exposure", "identity_exposure", "LidarDepthLoss", "RobustLidarDepthLoss", "lidar_occlusion_filter", "lidar_depth_image", "lidar_depth_loss", "raster_K", "world_to_camera", "prune_rows", "image_metrics", "psnr", "to_u8", "side_by_side", "depth_to_u8", "evaluate_keyframes", "DeltaDepthLoss", "delta_depth_loss", "delta_pose", "SimilarityLoss", "similarity_loss", "VoxelIndex", "PhotometricLoss", "photometric_loss", "reference_window_1d", "FusedActivations", "FusedAdam", "GaussianParameters", "GrowableAdam", "GrowableGaussians", "ply", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "Camera", "render", "render_full", "se3_exp", "pose_gradient", "get_projection_matrix", "rasterize_forward",
+__all__ = ["Admitted", "admit_sweep", "SweepVoxelMap", "VoxelSeeds", "WeightedPhotometricLoss", "weighted_photometric_loss", "Contribution", "contribution", "render_contribution", "low_contribution", "KeyframeVisibility", "visibility_pack", "covisibility", "observation_count", "visibility_remap", "iou", "overlap_coefficient", "ExposureLoss", "exposure_photometric_loss", "apply_exposure", "identity_exposure", "LidarDepthLoss", "RobustLidarDepthLoss", "lidar_occlusion_filter", "lidar_depth_image", "lidar_depth_loss", "raster_K", "world_to_camera", "prune_rows", "image_metrics", "psnr", "to_u8", "side_by_side", "depth_to_u8", "evaluate_keyframes", "DeltaDepthLoss", "delta_depth_loss", "delta_pose", "SimilarityLoss", "similarity_loss", "SurfelPlaneLoss", "surfel_plane_loss", "VoxelIndex", "PhotometricLoss", "photometric_loss", "reference_window_1d", "FusedActivations", "FusedAdam", "GaussianParameters", "GrowableAdam", "GrowableGaussians", "ply", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "Camera", "render", "render_full", "se3_exp", "pose_gradient", "get_projection_matrix", "rasterize_forward",
            "rasterize_backward", "mark_visible", "state_views", "set_reference_rects", "reference_rects", "last_num_rendered", "set_binning_capacity_hint", "speculation_stats", "emit_guard_trips", "mailbox_slow_path_last", "set_near_far", "set_near_far_thread", "set_reference_rects_thread", "async_outcomes_pending", "set_near_far_hints", "last_near_far", "set_far_speculation", "last_far_skipped", "NumRendered", "lib", "torch_ops", "synthetic", "multiview", "GsrError", "LIB_PATH"]

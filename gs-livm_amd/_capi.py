@@ -77,7 +77,8 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_contribution", "gsr_contribution_finish", "gsr_weighted_loss", "gsr_weighted_loss_workspace",
            "gsr_sweep_admit", "gsr_sweep_admit_workspace", "gsr_lidar_occlusion_filter",
            "gsr_lidar_depth_loss_robust", "gsr_lidar_depth_loss_robust_workspace", "gsr_voxel_table_bytes",
-           "gsr_voxel_sweep_workspace", "gsr_voxel_sweep", "gsr_voxel_rehash")
+           "gsr_voxel_sweep_workspace", "gsr_voxel_sweep", "gsr_voxel_rehash", "gsr_surfel_plane_loss",
+           "gsr_surfel_plane_loss_workspace")
 
 
 def lib():
@@ -191,6 +192,10 @@ def lib():
     L.gsr_similarity_loss_workspace.argtypes = [ci, ci]
     L.gsr_similarity_loss.restype = ci
     L.gsr_similarity_loss.argtypes = [ci, ci, ci, vp, vp, vp, vp, cf, vp, vp, vp, ci, vp, sz, vp]
+    L.gsr_surfel_plane_loss_workspace.restype = sz
+    L.gsr_surfel_plane_loss_workspace.argtypes = [ci, ci]
+    L.gsr_surfel_plane_loss.restype = ci
+    L.gsr_surfel_plane_loss.argtypes = [ci, ci, ci, vp, vp, vp, vp, vp, cf, cf, cf, cf, vp, vp, vp, vp, ci, vp, sz, vp]
     L.gsr_delta_depth_loss_workspace.restype = sz
     L.gsr_delta_depth_loss_workspace.argtypes = [ci, ci]
     L.gsr_delta_depth_loss.restype = ci
@@ -761,6 +766,32 @@ def similarity_loss(points, sel, xyz, scaling, lambda_, grad_xyz=None, grad_scal
                                      _ptr(out3), _ptr(grad_xyz), _ptr(grad_scaling), int(bool(accumulate)), _ptr(ws),
                                      nbytes, _stream()))
     return out3
+
+
+def surfel_plane_loss(points, sel, xyz, scaling, rotation, lambda_, huber=0.0, max_dist=float("inf"), lambda_flat=0.0,
+                      grad_xyz=None, grad_scaling=None, grad_rotation=None, accumulate=False):
+    """The point-to-plane loss of LiDAR points against the thinnest axis of their nearest selected Gaussian, plus the
+    flatness prior, in three launches (include/gsraster.h, gsr_surfel_plane_loss).  points [m,3] f32, sel [n] int32
+    (ascending, unique, < P), xyz / scaling [P,3] and rotation [P,4] f32 (scaling and rotation ACTIVATED), all on the
+    device.  grad_xyz / grad_scaling [P,3], grad_rotation [P,4]: buffers whose selected rows are written
+    (accumulate=False) or added to (accumulate=True); None = not wanted.  Returns out4 = [loss, mean rho, mean
+    thinnest scale, share of points inside max_dist] (device tensor)."""
+    P, m, n = int(xyz.size(0)), int(points.size(0)), int(sel.size(0))
+    assert xyz.is_cuda and xyz.shape == (P, 3) and scaling.shape == (P, 3) and rotation.shape == (P, 4)
+    assert points.shape == (m, 3) and sel.dtype == torch.int32 and sel.dim() == 1
+    for t in (points, xyz, scaling, rotation, grad_xyz, grad_scaling, grad_rotation):
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32)
+    assert sel.is_cuda and sel.is_contiguous()
+    for g, width in ((grad_xyz, 3), (grad_scaling, 3), (grad_rotation, 4)):
+        assert g is None or g.shape == (P, width)
+    nbytes = int(lib().gsr_surfel_plane_loss_workspace(m, n))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=xyz.device)
+    out4 = torch.empty(4, dtype=torch.float32, device=xyz.device)
+    _check(lib().gsr_surfel_plane_loss(P, m, n, _ptr(points), _ptr(sel), _ptr(xyz), _ptr(scaling), _ptr(rotation),
+                                       float(lambda_), float(huber), float(max_dist), float(lambda_flat), _ptr(out4),
+                                       _ptr(grad_xyz), _ptr(grad_scaling), _ptr(grad_rotation),
+                                       int(bool(accumulate)), _ptr(ws), nbytes, _stream()))
+    return out4
 
 
 def _host_floats(m, n):

@@ -35,6 +35,9 @@ UNITS = {
     "weighted.hip": ["-fno-slp-vectorize"],  # (the exposure loss's arithmetic under per-pixel weights: built like loss.hip)
     "growth.hip": [],
     "simi.hip": [],
+    # accumulate = 1 adds the very bits accumulate = 0 writes: no product may fuse into the add behind it (the multiply-adds
+    # of the nearest-centre search and of the residual are written out, as in simi.hip)
+    "surfel.hip": ["-ffp-contract=off"],
     "delta.hip": [],
     "lidar.hip": [],
     # sweep admission is restated bit for bit on dyadic inputs; its multiply-adds are explicit (gsr_lidar_project.hpp)

@@ -78,6 +78,17 @@ torch::Tensor weighted_photometric_loss_parts(const torch::Tensor& image, const 
 torch::Tensor similarity_loss(const torch::Tensor& points, const torch::Tensor& sel, const torch::Tensor& xyz,
                               const torch::Tensor& scaling, float lambda = 0.2f);
 
+// ---- the point-to-plane LiDAR loss on oriented surfels (an extension; csrc/surfel.hip) -------------------------------
+// lambda * mean_i [d_i <= max_dist] rho(n_j . (p_i - xyz_j)) + lambda_flat * mean_j min_k scaling[j][k] as ONE autograd
+// node: every point against the thinnest axis n_j (a column of R(rotation_j)) of its nearest selected Gaussian j; rho is
+// |e| for huber = 0 and the Huber function otherwise (include/gsraster.h, gsr_surfel_plane_loss).  points, sel, xyz as
+// similarity_loss; scaling [P,3] and rotation [P,4] ACTIVATED.  Gradients w.r.t. xyz, scaling and rotation, dense and
+// zero outside the selection.  lambda has no default: the term has no reference value.  Returns the 0-dim loss.
+torch::Tensor surfel_plane_loss(const torch::Tensor& points, const torch::Tensor& sel, const torch::Tensor& xyz,
+                                const torch::Tensor& scaling, const torch::Tensor& rotation, float lambda,
+                                float huber = 0.f, float max_dist = std::numeric_limits<float>::infinity(),
+                                float lambda_flat = 0.f);
+
 // ---- the delta-depth loss between a history keyframe and its successor (optimize_vis step 5) ------------------------
 // The body of the loop at src/liw/lioOptimization.cpp:1780-1801 -- calcDeltaSimi (src/gs/gaussian.cu:116-199), the two
 // inv_depth, the masks, lambda * mean -- as ONE autograd node on the kernels of csrc/delta.hip.  depth_* / acc_*: the

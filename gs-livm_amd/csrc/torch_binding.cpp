@@ -476,6 +476,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("image"), py::arg("gt"), py::arg("lambda_dssim") = 0.2f, py::arg("window1d") = py::none());
   n.def("similarity_loss", &nx::similarity_loss, py::arg("points"), py::arg("sel"), py::arg("xyz"), py::arg("scaling"),
         py::arg("lambda_") = 0.2f);
+  n.def("surfel_plane_loss", &nx::surfel_plane_loss, py::arg("points"), py::arg("sel"), py::arg("xyz"),
+        py::arg("scaling"), py::arg("rotation"), py::arg("lambda_"), py::arg("huber") = 0.f,
+        py::arg("max_dist") = std::numeric_limits<float>::infinity(), py::arg("lambda_flat") = 0.f);
   n.def("delta_depth_loss", &nx::delta_depth_loss, py::arg("depth_src"), py::arg("acc_src"), py::arg("depth_ref"),
         py::arg("acc_ref"), py::arg("inv_K_src"), py::arg("K_ref"), py::arg("T_rel"), py::arg("lambda_") = 0.2f);
   n.def("lidar_depth_image",

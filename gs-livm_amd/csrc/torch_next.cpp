@@ -226,6 +226,43 @@ struct SimilarityLossFn : public torch::autograd::Function<SimilarityLossFn> {
   }
 };
 
+struct SurfelPlaneLossFn : public torch::autograd::Function<SurfelPlaneLossFn> {
+  static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor points, torch::Tensor sel,
+                               torch::Tensor xyz, torch::Tensor scaling, torch::Tensor rotation, double lambda,
+                               double huber, double max_dist, double lambda_flat) {
+    const torch::Tensor p = dev_f32(points, "points"), x = dev_f32(xyz, "xyz"), s = dev_f32(scaling, "scaling"),
+                        q = dev_f32(rotation, "rotation");
+    if (!sel.defined() || !sel.is_cuda() || sel.scalar_type() != torch::kInt32 || sel.dim() != 1)
+      throw std::invalid_argument("surfel_plane_loss: sel is a 1-d int32 tensor on the device");
+    if (p.dim() != 2 || p.size(1) != 3 || x.dim() != 2 || x.size(1) != 3 || s.sizes() != x.sizes() || q.dim() != 2 ||
+        q.size(0) != x.size(0) || q.size(1) != 4)
+      throw std::invalid_argument("surfel_plane_loss: points [m,3], xyz [P,3], scaling [P,3], rotation [P,4]");
+    const torch::Tensor rows = sel.contiguous();
+    const int P = x.size(0), m = p.size(0), n = rows.size(0);
+    torch::Tensor gx = xyz.requires_grad() ? torch::zeros_like(x) : torch::Tensor();
+    torch::Tensor gs = scaling.requires_grad() ? torch::zeros_like(s) : torch::Tensor();
+    torch::Tensor gq = rotation.requires_grad() ? torch::zeros_like(q) : torch::Tensor();
+    const size_t nbytes = gsr_surfel_plane_loss_workspace(m, n);
+    torch::Tensor ws = workspace(nbytes, x);
+    torch::Tensor out4 = torch::empty({4}, x.options());
+    check(gsr_surfel_plane_loss(P, m, n, fp(p), n ? rows.data_ptr<int>() : nullptr, fp(x), fp(s), fp(q),
+                                static_cast<float>(lambda), static_cast<float>(huber), static_cast<float>(max_dist),
+                                static_cast<float>(lambda_flat), out4.data_ptr<float>(), fp(gx), fp(gs), fp(gq), 0,
+                                reinterpret_cast<char*>(ws.data_ptr()), nbytes, current_stream()),
+          "gsr_surfel_plane_loss");
+    const torch::Tensor none = torch::empty({0}, x.options());
+    ctx->save_for_backward({gx.defined() ? gx : none, gs.defined() ? gs : none, gq.defined() ? gq : none});
+    return out4[0];
+  }
+  static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx,
+                                               torch::autograd::tensor_list grad_outputs) {
+    const auto saved = ctx->get_saved_variables();
+    const torch::Tensor g = grad_outputs[0];
+    return {torch::Tensor(), torch::Tensor(), scaled(saved[0], g), scaled(saved[1], g), scaled(saved[2], g),
+            torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor()};
+  }
+};
+
 struct DeltaDepthLossFn : public torch::autograd::Function<DeltaDepthLossFn> {
   static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor depth_src, torch::Tensor acc_src,
                                torch::Tensor depth_ref, torch::Tensor acc_ref, torch::Tensor inv_K_src,
@@ -431,6 +468,14 @@ torch::Tensor apply_exposure(const torch::Tensor& image, const torch::Tensor& ex
 torch::Tensor similarity_loss(const torch::Tensor& points, const torch::Tensor& sel, const torch::Tensor& xyz,
                               const torch::Tensor& scaling, float lambda) {
   return SimilarityLossFn::apply(points, sel, xyz, scaling, static_cast<double>(lambda));
+}
+
+torch::Tensor surfel_plane_loss(const torch::Tensor& points, const torch::Tensor& sel, const torch::Tensor& xyz,
+                                const torch::Tensor& scaling, const torch::Tensor& rotation, float lambda, float huber,
+                                float max_dist, float lambda_flat) {
+  return SurfelPlaneLossFn::apply(points, sel, xyz, scaling, rotation, static_cast<double>(lambda),
+                                  static_cast<double>(huber), static_cast<double>(max_dist),
+                                  static_cast<double>(lambda_flat));
 }
 
 torch::Tensor delta_depth_loss(const torch::Tensor& depth_src, const torch::Tensor& acc_src,

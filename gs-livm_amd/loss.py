@@ -177,6 +177,38 @@ def similarity_loss(points, sel, xyz, scaling, lambda_=0.2):
     return SimilarityLoss.apply(points, sel, xyz, scaling, float(lambda_))
 
 
+class SurfelPlaneLoss(torch.autograd.Function):
+    """The point-to-plane term on oriented surfels (csrc/surfel.hip; an extension, the reference has none) as one
+    node; gradients w.r.t. xyz, the ACTIVATED scaling and the ACTIVATED rotation (points and sel are data).  As
+    SimilarityLoss, the gradients are dense tensors that are zero outside the selection, allocated only for the inputs
+    that need one, so autograd adds them to the rasterizer's on either activation path of model.py."""
+
+    @staticmethod
+    def forward(ctx, points, sel, xyz, scaling, rotation, lambda_, huber, max_dist, lambda_flat):
+        xyz_c, scaling_c, rotation_c = xyz.contiguous(), scaling.contiguous(), rotation.contiguous()
+        need = ctx.needs_input_grad[2:5]
+        gx, gs, gr = (torch.zeros_like(t) if want else None for t, want in zip((xyz_c, scaling_c, rotation_c), need))
+        out4 = _capi.surfel_plane_loss(points.contiguous(), sel.contiguous(), xyz_c, scaling_c, rotation_c, lambda_,
+                                       huber, max_dist, lambda_flat, gx, gs, gr)
+        ctx.grads = (gx, gs, gr)
+        ctx.parts = out4  # [loss, mean rho, mean thinnest scale, share of points inside max_dist] for logging
+        return out4[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        return (None, None) + tuple(t * g if t is not None else None for t in ctx.grads) + (None, None, None, None)
+
+
+def surfel_plane_loss(points, sel, xyz, scaling, rotation, lambda_, huber=0.0, max_dist=float("inf"), lambda_flat=0.0):
+    """lambda_ * mean_i [d_i <= max_dist] rho(n_j . (p_i - xyz_j)) + lambda_flat * mean_j min_k scaling[j][k]: every
+    point against the thinnest axis n_j of its nearest selected Gaussian j (include/gsraster.h,
+    gsr_surfel_plane_loss).  points [m,3] f32 and sel [n] int32 come from `VoxelIndex.select`; xyz is the model's _xyz,
+    scaling and rotation the activated values of the iteration's `activated()`.  `lambda_` has no default: the term is
+    an extension without a reference value.  Returns the 0-dim loss."""
+    return SurfelPlaneLoss.apply(points, sel, xyz, scaling, rotation, float(lambda_), float(huber), float(max_dist),
+                                 float(lambda_flat))
+
+
 class DeltaDepthLoss(torch.autograd.Function):
     """loss = lambda * mean|inv_depth(calcDeltaSimi(src, ref)) mask - inv_depth(depth_ref) mask|
     (src/liw/lioOptimization.cpp:1780-1801) as one node; gradients w.r.t. the two rendered DEPTH images only (the

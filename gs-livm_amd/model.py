@@ -589,6 +589,23 @@ class GrowableGaussians(GaussianParameters):
             scaling = self.Get_scaling()
         return similarity_loss(points, sel, self._xyz, scaling, lambda_)
 
+    def calc_plane_loss(self, losses, lambda_, scaling=None, rotation=None, huber=0.0, max_dist=float("inf"),
+                        lambda_flat=0.0, max_points=500, generator=None):
+        """The point-to-plane term (loss.surfel_plane_loss) on calc_simi_loss's selection: the LiDAR points in `losses`
+        against the thinnest axis of their nearest Gaussian among those of their voxels, or None where calc_simi_loss
+        returns None.  scaling, rotation: the activated values of this iteration's `activated()` call, so that the
+        term shares the rasterizer's node on both activation paths; None runs the getter."""
+        from .loss import surfel_plane_loss
+        picked = self.voxel_index.select(losses, max_points=max_points, generator=generator)
+        if picked is None:
+            return None
+        points, sel = picked
+        if scaling is None or rotation is None:
+            _, _, act_scaling, act_rotation, _ = self.activated()
+            scaling = act_scaling if scaling is None else scaling
+            rotation = act_rotation if rotation is None else rotation
+        return surfel_plane_loss(points, sel, self._xyz, scaling, rotation, lambda_, huber, max_dist, lambda_flat)
+
 
 @torch.no_grad()
 def prune_rows(tensors, reasons, row_map, P_new):

@@ -490,6 +490,42 @@ int gsr_similarity_loss(int P, int m, int n, const float* points, const int* sel
                         const float* scaling, float lambda, float* out3, float* grad_xyz, float* grad_scaling,
                         int accumulate, char* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the point-to-plane LiDAR loss on oriented surfels (an extension: the reference has no such term), fused ----
+ * The similarity loss above never reads the rotation; this term holds a surfel's thinnest axis to the points near it.
+ * points [m,3], sel [n] (ascending unique rows < P), xyz [P,3]: as gsr_similarity_loss takes them; scaling [P,3] and
+ * rotation [P,4] are the ACTIVATED values, the quaternion (w, x, y, z) used as given and NOT renormalised, as the
+ * rasterizer uses it.  R(q) =
+ *   [[1-2(y^2+z^2), 2(xy-wz), 2(xz+wy)], [2(xy+wz), 1-2(x^2+z^2), 2(yz-wx)], [2(xz-wy), 2(yz+wx), 1-2(x^2+y^2)]]
+ * and its column k is the axis that belongs to scaling[.][k] (Sigma = R S^2 R^T).
+ * Per selected row j: k*_j = index of the smallest of its three scales (strict < from index 0: the lowest index wins
+ * a tie), n_j = column k*_j of R(q_j).
+ * Per point i: j(i) = the nearest selected centre by the similarity loss's rule (the same FMA chain, strict comparison,
+ * the lower position in sel on a bit-equal tie), v_i = p_i - xyz_j, d_i = |v_i|, g_i = [d_i <= max_dist], e_i = n_j . v_i,
+ *   rho(e)  = |e| for huber = 0;  e^2 / (2 huber) where |e| <= huber, |e| - huber / 2 beyond it, for huber > 0
+ *   rho'(e) = sign(e) with sign(0) = 0;  e / huber inside the knee
+ *   L_plane = lambda / m * sum_i g_i rho(e_i)  (normalised by all m points),  L_flat = lambda_flat / n * sum_j scaling[j][k*_j]
+ * out4 (device) = {L_plane + L_flat, sum_i g_i rho(e_i) / m, sum_j scaling[j][k*_j] / n, sum_i g_i / m}.
+ * grad_xyz [P,3], grad_scaling [P,3], grad_rotation [P,4] (each nullable) for upstream gradient 1, with
+ * A_j = sum_{i -> j} g_i rho'(e_i) and B_j = sum_{i -> j} g_i rho'(e_i) v_i:
+ *   grad_xyz[j] = -(lambda / m) A_j n_j;  grad_rotation[j] = (dn_j/dq)^T (lambda / m) B_j, the 3x4 Jacobian of the column
+ *   of the polynomial above, w included, with no normalisation term (the activation's backward owns that);
+ *   grad_scaling[j][k*_j] = lambda_flat / n and 0 in the other two elements (the choice of k* carries no gradient).
+ * accumulate = 0 / 1 as gsr_similarity_loss: selected rows are WRITTEN or ADDED TO, every other row is untouched.
+ * A non-finite point or centre that wins no comparison contributes 0 and writes nothing.  m == 0 or n == 0: returns 0
+ * with out4 = {0, 0, 0, 0}, no gradient.
+ * Refused (GSR_ERR_INVALID_ARGUMENT, nothing launched or written), in this order: negative P, m or n; n > P; n beyond
+ * gsr_similarity_loss's bound; lambda, huber or lambda_flat not finite or negative; max_dist NaN or <= 0 (+inf is
+ * allowed: no gate); a null out4; with m, n > 0 a null points / sel / xyz / scaling / rotation / workspace;
+ * workspace_bytes below the query (which returns 0 for a refused or empty shape); a float or int array off 4-byte
+ * alignment.  The workspace itself needs no alignment.
+ * Deterministic (no float atomics, fixed-order reductions), three launches on the caller's stream, no host
+ * synchronisation, no allocation.  Profiled under k_simi_nearest / k_simi_points / k_simi_grads (the id word is full). */
+size_t gsr_surfel_plane_loss_workspace(int m, int n);
+int gsr_surfel_plane_loss(int P, int m, int n, const float* points, const int* sel, const float* xyz,
+                          const float* scaling, const float* rotation, float lambda, float huber, float max_dist,
+                          float lambda_flat, float* out4, float* grad_xyz, float* grad_scaling, float* grad_rotation,
+                          int accumulate, char* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the delta-depth loss between a history keyframe and its successor (step 5 of optimize_vis), fused ----
  * For every SOURCE pixel (u, v) with d = depth_src[v][u]:
  *   p' = R_rel inv_K_src (u d, v d, d) + t_rel,  Z'[v][u] = p'.z,  (X, Y) = (K_ref p').xy / (K_ref p').z
