@@ -35,8 +35,9 @@ UNITS = {
     "weighted.hip": ["-fno-slp-vectorize"],  # (the exposure loss's arithmetic under per-pixel weights: built like loss.hip)
     "growth.hip": [],
     "simi.hip": [],
-    # accumulate = 1 adds the very bits accumulate = 0 writes: no product may fuse into the add behind it (the multiply-adds
-    # of the nearest-centre search and of the residual are written out, as in simi.hip)
+    # accumulate = 1 adds the very bits accumulate = 0 writes: no product may fuse into the add behind it (the multiply-add
+    # of the residual is written out; the nearest-centre search it shares with simi.hip, gsr_nearest.hpp, gives the same
+    # bits under either setting)
     "surfel.hip": ["-ffp-contract=off"],
     "delta.hip": [],
     "lidar.hip": [],
@@ -54,7 +55,7 @@ UNITS = {
 }
 HEADERS = [os.path.join(CSRC, "gsr_internal.hpp"), os.path.join(CSRC, "gsr_api.hpp"), os.path.join(CSRC, "sort_core.hpp"),
            os.path.join(CSRC, "gsr_workgroup.hpp"), os.path.join(CSRC, "gsr_window.hpp"),
-           os.path.join(CSRC, "gsr_lidar_project.hpp"),
+           os.path.join(CSRC, "gsr_lidar_project.hpp"), os.path.join(CSRC, "gsr_nearest.hpp"),
            os.path.join(ROOT, "include", "gsraster.h")]
 
 

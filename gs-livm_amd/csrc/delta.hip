@@ -75,10 +75,7 @@ struct DeltaWorkspace {
   size_t bytes;
   static DeltaWorkspace carve(char* base, int H, int W) {
     const size_t N = (size_t)H * W, nblocks = (N + 255) / 256;
-    // the caller's workspace need not be aligned: the carving starts at the next multiple of ALIGN (the slack is part
-    // of `bytes`)
-    char* b = base ? reinterpret_cast<char*>(align_up(reinterpret_cast<uintptr_t>(base))) : nullptr;
-    Carver cv(b);
+    Carver cv = Carver::aligned(base);
     DeltaWorkspace w;
     w.zp = cv.take<float>(N);
     w.xy = cv.take<float2>(N);
@@ -88,7 +85,7 @@ struct DeltaWorkspace {
     w.gap_part = cv.take<double>(nblocks);
     w.cnt_part = cv.take<int>(nblocks);
     w.maxbits = cv.take<unsigned int>(1);
-    w.bytes = align_up(cv.off) + ALIGN;
+    w.bytes = cv.bytes();
     return w;
   }
 };

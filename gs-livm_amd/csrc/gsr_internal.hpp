@@ -31,6 +31,12 @@ struct Carver {
   char* base;
   size_t off = 0;
   explicit Carver(char* b) : base(b) {}
+  // For a workspace the caller need not align: the carving starts at the next multiple of ALIGN (bytes() has the slack).
+  static Carver aligned(char* b) {
+    return Carver(b ? reinterpret_cast<char*>(align_up(reinterpret_cast<uintptr_t>(b))) : nullptr);
+  }
+  // What a blob carved so far must hold.
+  size_t bytes() const { return align_up(off) + ALIGN; }
   template <typename T>
   T* take(size_t count) {
     off = align_up(off);
@@ -164,7 +170,7 @@ struct GeomState {
     g.touched = c.take<uint8_t>(P);
     g.tlist = c.take<uint32_t>(P);
     DepthSortScratch::carve(c, P, g.dsort);
-    if (bytes) *bytes = align_up(c.off) + ALIGN;
+    if (bytes) *bytes = c.bytes();
     return g;
   }
 };
@@ -193,7 +199,7 @@ struct ImageState {
     s.rangesB = c.take<uint2>(tiles);
     s.quad_done = c.take<uint8_t>(tiles * 4);
     s.live_sat = c.take<uint32_t>((size_t)((W + TILE - 1) / TILE + 1) * ((H + TILE - 1) / TILE + 1));
-    if (bytes) *bytes = align_up(c.off) + ALIGN;
+    if (bytes) *bytes = c.bytes();
     return s;
   }
 };
@@ -239,7 +245,7 @@ struct BinningState {
     b.inst_flag = c.take<uint8_t>(R);
     b.chunk_first = c.take<uint32_t>(R / EMIT_CHUNK + 2);
     b.chunk_firstB = c.take<uint32_t>(R / EMIT_CHUNK + 2);
-    if (bytes) *bytes = align_up(c.off) + ALIGN;
+    if (bytes) *bytes = c.bytes();
     return b;
   }
 };

@@ -50,14 +50,12 @@ struct LidarWorkspace {
   size_t bytes;
   static LidarWorkspace carve(char* base, int H, int W) {
     const size_t N = (size_t)H * W, nblocks = (N + 255) / 256;
-    // (the caller's workspace need not be aligned: as DeltaWorkspace)
-    char* b = base ? reinterpret_cast<char*>(align_up(reinterpret_cast<uintptr_t>(base))) : nullptr;
-    Carver cv(b);
+    Carver cv = Carver::aligned(base);
     LidarWorkspace w;
     w.abs_part = cv.take<double>(nblocks);
     w.cnt_part = cv.take<int>(nblocks);
     w.scale = cv.take<float>(1);
-    w.bytes = align_up(cv.off) + ALIGN;
+    w.bytes = cv.bytes();
     return w;
   }
 };
@@ -271,15 +269,14 @@ struct LidarRobustWorkspace {
   size_t bytes;
   static LidarRobustWorkspace carve(char* base, int H, int W) {
     const size_t N = (size_t)H * W, nblocks = (N + 255) / 256;
-    char* b = base ? reinterpret_cast<char*>(align_up(reinterpret_cast<uintptr_t>(base))) : nullptr;
-    Carver cv(b);
+    Carver cv = Carver::aligned(base);
     LidarRobustWorkspace w;
     w.rho_part = cv.take<double>(nblocks);
     w.abs_part = cv.take<double>(nblocks);
     w.sup_part = cv.take<int>(nblocks);
     w.clip_part = cv.take<int>(nblocks);
     w.scale = cv.take<float>(1);
-    w.bytes = align_up(cv.off) + ALIGN;
+    w.bytes = cv.bytes();
     return w;
   }
 };

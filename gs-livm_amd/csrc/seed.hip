@@ -51,14 +51,12 @@ struct SeedWorkspace {
   size_t bytes;
   static SeedWorkspace carve(char* base, int n, int H, int W) {
     const size_t N = (size_t)H * W, nblocks = ((size_t)n + WG_THREADS - 1) / WG_THREADS;
-    // (the caller's workspace need not be aligned: as LidarWorkspace)
-    char* b = base ? reinterpret_cast<char*>(align_up(reinterpret_cast<uintptr_t>(base))) : nullptr;
-    Carver cv(b);
+    Carver cv = Carver::aligned(base);
     SeedWorkspace w;
     w.plane = cv.take<unsigned long long>(N);
     w.totals = cv.take<int>(SEED_CODES * nblocks);
     w.codes = cv.take<unsigned char>((size_t)n);
-    w.bytes = align_up(cv.off) + ALIGN;
+    w.bytes = cv.bytes();
     return w;
   }
 };

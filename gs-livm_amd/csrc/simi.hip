@@ -6,53 +6,25 @@
 // Reference: GaussianModel::compute_min_distance (src/gs/gaussian.cu:87-114) called from calcSimiLoss (:201-239) at
 // src/liw/lioOptimization.cpp:1675 with lambda_depth_simi (config/basic_common.yaml:64).  The reference expands
 // m x n x 3 floats several times over, forward and backward; since r is ONE scalar, clamp and min commute and the term
-// is a nearest-neighbour search followed by one clamp per point:
-//   k_simi_nearest   lane = point, workgroup = 64 points x one chunk of the gathered centres (staged through LDS 256 at
-//                    a time, each of the four waves scans a quarter of a tile): per (point, chunk) the smallest squared
-//                    distance and its position in `sel`; the workgroups of the first point block also sum their chunk's
-//                    scales (f64, fixed order)
-//   k_simi_points    thread = point: fixed-order minimum over the chunks, r from the chunk sums, the clamp, and the
-//                    point's gradient record (position of its nearest centre or -1, and -lambda/m (p - x)/d);
-//                    per-workgroup partial sums of the clamped distances (f64) and counts of points outside r
-//   k_simi_grads     thread = selected row: walks the m records in ascending point order and sums those that name it
-//                    (several points may share a nearest Gaussian: a deterministic many-to-one accumulation without
-//                    atomics); every selected scale element receives dL/dr / (3n); workgroup 0 writes
-//                    {loss, mean clamped distance, r}
+// is a nearest-neighbour search followed by one clamp per point.  The search, its tie rule, the launch plan and the
+// walk of the records are gsr_nearest.hpp's (its header has the shape of the three launches); what is this term's:
+//   k_simi_nearest   side job of the search: the workgroups of the first point block sum their chunk's scales (f64,
+//                    fixed order)
+//   k_simi_points    r from the chunk sums, the clamp, and the point's gradient record (position of its nearest centre
+//                    or -1, and -lambda/m (p - x)/d); per-workgroup partial sums of the clamped distances (f64) and
+//                    counts of points outside r
+//   k_simi_grads     the summed records ARE the row of dL/dxyz; every selected scale element receives dL/dr / (3n);
+//                    workgroup 0 writes {loss, mean clamped distance, r}
 // No float atomics, every reduction in a fixed order (bitwise reproducible), no host synchronisation, three launches
-// on the caller's stream.  Ties (two centres at bit-equal squared distance) go to the lower position in `sel`; a point
-// at exactly d == r contributes nothing (the reference leaves both undefined).  m and n are bounded by int only: the
-// 500-point cap of the reference (MAX_SIMI, include/gs/gp3d/gp_types.h:15) is the host's policy.
+// on the caller's stream.  A point at exactly d == r contributes nothing (the reference leaves that undefined, as it
+// does a tie between two centres).  m and n are bounded by int only: the 500-point cap of the reference (MAX_SIMI,
+// include/gs/gp3d/gp_types.h:15) is the host's policy.
 #include "gsr_api.hpp"
 #include "gsr_internal.hpp"
+#include "gsr_nearest.hpp"
 #include "gsr_workgroup.hpp"
 
 namespace gsr {
-
-constexpr int SM_PTS_ = 64;        // points per workgroup of k_simi_nearest (one per lane)
-constexpr int SM_TILE_ = 256;      // centres staged per LDS tile (one per thread)
-constexpr int SM_TARGET_WGS_ = 1024;  // k_simi_nearest's grid aims at four workgroups on each of the 256 CUs, once
-constexpr int SM_REC_TILE_ = 1024;  // records staged per LDS tile of k_simi_grads
-
-struct SimiPlan {
-  int pblocks, ntiles, tiles_per_chunk, nchunks, nblocks2;
-};
-
-static SimiPlan simi_plan(int m, int n) {
-  SimiPlan p;
-  p.pblocks = (m + SM_PTS_ - 1) / SM_PTS_;
-  p.ntiles = (n + SM_TILE_ - 1) / SM_TILE_;
-  // the work is latency-bound at the sizes of the loop (4-16 M distances): as many chunks as fill the device once, no
-  // more (every chunk costs each point one partial record)
-  int want = SM_TARGET_WGS_ / (p.pblocks > 0 ? p.pblocks : 1);
-  if (want < 1) want = 1;
-  if (want > p.ntiles) want = p.ntiles;
-  if (want < 1) want = 1;
-  p.tiles_per_chunk = (p.ntiles + want - 1) / want;
-  if (p.tiles_per_chunk < 1) p.tiles_per_chunk = 1;
-  p.nchunks = (p.ntiles + p.tiles_per_chunk - 1) / p.tiles_per_chunk;  // (no empty chunk)
-  p.nblocks2 = (m + 255) / 256;
-  return p;
-}
 
 struct SimiWorkspace {
   float* part_d2;    // [nchunks][m] smallest squared distance of the point inside the chunk
@@ -65,7 +37,7 @@ struct SimiWorkspace {
   float* r;          // [1]
   size_t bytes;
   static SimiWorkspace carve(char* base, int m, int n) {
-    const SimiPlan p = simi_plan(m, n);
+    const NearestPlan p = nearest_plan(m, n);
     Carver cv(base);
     SimiWorkspace w;
     w.part_d2 = cv.take<float>((size_t)p.nchunks * m);
@@ -76,14 +48,10 @@ struct SimiWorkspace {
     w.hinge_part = cv.take<double>((size_t)p.nblocks2);
     w.count_part = cv.take<int>((size_t)p.nblocks2);
     w.r = cv.take<float>(1);
-    w.bytes = align_up(cv.off) + ALIGN;
+    w.bytes = cv.bytes();
     return w;
   }
 };
-
-// A row index of `sel` as the kernels use it for READS: clamped into [0, P), so that a selection that breaks its
-// contract (each < P) reads a wrong row instead of foreign memory; writes test the unclamped index and are skipped.
-__device__ __forceinline__ int clamp_row(int row, int P) { return min(max(row, 0), P - 1); }
 
 __global__ __launch_bounds__(256) void k_simi_nearest(const int P, const int m, const int n, const int tiles_per_chunk,
                                                       const int ntiles, const float* __restrict__ points,
@@ -91,60 +59,12 @@ __global__ __launch_bounds__(256) void k_simi_nearest(const int P, const int m, 
                                                       const float* __restrict__ scaling,
                                                       float* __restrict__ part_d2, int* __restrict__ part_k,
                                                       double* __restrict__ scale_part) {
-  __shared__ float4 cs[SM_TILE_];   // one broadcast ds_read_b128 per centre
-  __shared__ float wd2[4][SM_PTS_];
-  __shared__ int wk[4][SM_PTS_];
   __shared__ double shsum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int i = blockIdx.x * SM_PTS_ + lane;
-  const int ic = min(i, m - 1);
-  const float px = points[3 * (size_t)ic], py = points[3 * (size_t)ic + 1], pz = points[3 * (size_t)ic + 2];
-  const int t0 = blockIdx.y * tiles_per_chunk, t1 = min(t0 + tiles_per_chunk, ntiles);
-  const bool sums = blockIdx.x == 0;  // (uniform over the workgroup)
-  float best = __builtin_inff();
-  int bestk = -1;
   double ssum = 0.0;
-  for (int t = t0; t < t1; t++) {
-    const int k = t * SM_TILE_ + (int)threadIdx.x;
-    // a slot past the end holds a centre no finite point is near: its squared distance overflows to +inf, which never
-    // passes the strict comparison
-    float4 c = make_float4(3e38f, 3e38f, 3e38f, 0.f);
-    if (k < n) {
-      const size_t row = (size_t)clamp_row(sel[k], P);
-      c.x = xyz[3 * row]; c.y = xyz[3 * row + 1]; c.z = xyz[3 * row + 2];
-      if (sums) ssum += ((double)scaling[3 * row] + (double)scaling[3 * row + 1]) + (double)scaling[3 * row + 2];
-    }
-    __syncthreads();  // (the previous tile has been scanned)
-    cs[threadIdx.x] = c;
-    __syncthreads();
-    const int j0 = wave * 64;
-#pragma unroll 8
-    for (int j = 0; j < 64; j++) {
-      const float4 q = cs[j0 + j];
-      const float dx = px - q.x, dy = py - q.y, dz = pz - q.z;
-      const float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-      if (d2 < best) { best = d2; bestk = t * SM_TILE_ + j0 + j; }  // ascending positions, strict: the lowest wins a tie
-    }
-  }
-  wd2[wave][lane] = best;
-  wk[wave][lane] = bestk;
-  __syncthreads();
-  if (wave == 0 && i < m) {
-    float b = wd2[0][lane];
-    int bk = wk[0][lane];
-#pragma unroll
-    for (int w = 1; w < 4; w++) {
-      const float d = wd2[w][lane];
-      const int kk = wk[w][lane];
-      // within a tile the waves scan ascending quarters, but over several tiles wave 0 may hold a LATER position than
-      // wave 1: equal distances are settled by the position itself
-      if (d < b || (d == b && kk >= 0 && (bk < 0 || kk < bk))) { b = d; bk = kk; }
-    }
-    const size_t o = (size_t)blockIdx.y * m + i;
-    part_d2[o] = b;
-    part_k[o] = bk;
-  }
-  if (sums) {
+  nearest_chunk_scan(P, m, n, tiles_per_chunk, ntiles, points, sel, xyz, part_d2, part_k, [&](int, size_t row3) {
+    ssum += ((double)scaling[row3] + (double)scaling[row3 + 1]) + (double)scaling[row3 + 2];
+  });
+  if (blockIdx.x == 0) {  // (uniform over the workgroup: the workgroups whose threads ran the side job)
     const double s = block_sum(ssum, shsum);
     if (threadIdx.x == 0) scale_part[blockIdx.y] = s;
   }
@@ -167,13 +87,9 @@ __global__ __launch_bounds__(256) void k_simi_points(const int P, const int m, c
   float hinge = 0.f;
   int active = 0;
   if (i < m) {
-    float best = __builtin_inff();
-    int bk = -1;
-    for (int c = 0; c < nchunks; c++) {  // ascending chunks hold ascending positions: strict, the lowest wins a tie
-      const float d = part_d2[(size_t)c * m + i];
-      const int kk = part_k[(size_t)c * m + i];
-      if (d < best) { best = d; bk = kk; }
-    }
+    const NearestHit hit = nearest_over_chunks(part_d2, part_k, m, nchunks, i);
+    const float best = hit.d2;
+    const int bk = hit.k;
     int rk = -1;
     float gx = 0.f, gy = 0.f, gz = 0.f;
     if (bk >= 0) {
@@ -212,7 +128,6 @@ __global__ __launch_bounds__(256) void k_simi_grads(const int P, const int m, co
                                                     const float lambda, const int accumulate,
                                                     float* __restrict__ out3, float* __restrict__ grad_xyz,
                                                     float* __restrict__ grad_scaling) {
-  __shared__ __attribute__((aligned(16))) int sk[SM_REC_TILE_];
   __shared__ double shsum[4];
   // number of points outside r (integers: exact in any order) and, for workgroup 0, the loss
   double hs, cnt;
@@ -228,45 +143,17 @@ __global__ __launch_bounds__(256) void k_simi_grads(const int P, const int m, co
   if (!grad_xyz && !grad_scaling) return;  // (uniform)
   const int k = blockIdx.x * 256 + (int)threadIdx.x;
   const int kq = k < n ? k : -2;  // (-2 matches no record; the thread still helps to stage)
-  float ax = 0.f, ay = 0.f, az = 0.f;
-  if (grad_xyz) {
-    for (int base = 0; base < m; base += SM_REC_TILE_) {
-      __syncthreads();
-#pragma unroll
-      for (int q = 0; q < SM_REC_TILE_ / 256; q++) {
-        const int i = base + q * 256 + (int)threadIdx.x;
-        sk[q * 256 + threadIdx.x] = i < m ? rec_k[i] : -1;
-      }
-      __syncthreads();
-      const int cntv = min(SM_REC_TILE_, m - base);
-      for (int q = 0; q < cntv; q += 4) {  // ascending point order: the sum of a shared row has ONE order
-        const int4 v = *reinterpret_cast<const int4*>(&sk[q]);
-        if (v.x == kq || v.y == kq || v.z == kq || v.w == kq) {
-          const int e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int u = 0; u < 4; u++)
-            if (e[u] == kq) {
-              const size_t i = (size_t)(base + q + u);
-              ax += rec_g[3 * i]; ay += rec_g[3 * i + 1]; az += rec_g[3 * i + 2];
-            }
-        }
-      }
-    }
-  }
+  float a[3] = {0.f, 0.f, 0.f};
+  if (grad_xyz) sum_records(m, rec_k, rec_g, kq, a);
   if (k >= n) return;
   const int row = sel[k];
   if (row < 0 || row >= P) return;  // (a selection that breaks its contract writes nothing)
-  if (grad_xyz) {
-    float* g = grad_xyz + 3 * (size_t)row;
-    if (accumulate) { g[0] += ax; g[1] += ay; g[2] += az; }
-    else { g[0] = ax; g[1] = ay; g[2] = az; }
-  }
+  if (grad_xyz) store_row(grad_xyz + 3 * (size_t)row, a, accumulate);
   if (grad_scaling) {
     // dL/dr = -lambda/m * (points outside r), spread evenly over the 3n elements r averages
     const float gs = (float)(-((double)lambda / (double)m) * cnt / (3.0 * (double)n));
-    float* g = grad_scaling + 3 * (size_t)row;
-    if (accumulate) { g[0] += gs; g[1] += gs; g[2] += gs; }
-    else { g[0] = gs; g[1] = gs; g[2] = gs; }
+    const float v[3] = {gs, gs, gs};
+    store_row(grad_scaling + 3 * (size_t)row, v, accumulate);
   }
 }
 
@@ -284,7 +171,7 @@ static hipError_t launch_similarity_loss(int P, int m, int n, const float* point
     hipLaunchKernelGGL(k_simi_zero3, dim3(1), dim3(64), 0, s, out3);
     return hipGetLastError();
   }
-  const SimiPlan p = simi_plan(m, n);
+  const NearestPlan p = nearest_plan(m, n);
   const SimiWorkspace w = SimiWorkspace::carve(workspace, m, n);
   {
     ProfScope ps(K_SIMI_NEAREST, s);
@@ -313,7 +200,7 @@ using namespace gsr;
 extern "C" {
 
 size_t gsr_similarity_loss_workspace(int m, int n) {
-  if (m <= 0 || n <= 0 || n > 0x7fffffff - 1024) return 0;
+  if (m <= 0 || n <= 0 || n > NEAREST_MAX_N) return 0;
   return simi_workspace_bytes(m, n);
 }
 
@@ -321,9 +208,7 @@ int gsr_similarity_loss(int P, int m, int n, const float* points, const int* sel
                         const float* scaling, float lambda, float* out3, float* grad_xyz, float* grad_scaling,
                         int accumulate, char* workspace, size_t workspace_bytes, void* stream_) {
   clear_error();
-  if (P < 0 || m < 0 || n < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/m/n");
-  if (n > P) return fail(GSR_ERR_INVALID_ARGUMENT, "n = %d selected rows of P = %d (the selection is unique)", n, P);
-  if (n > 0x7fffffff - 1024) return fail(GSR_ERR_INVALID_ARGUMENT, "n too large");
+  if (int e = check_selection_sizes(P, m, n)) return e;
   if (!out3) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");
   if (m > 0 && n > 0) {
     if (!points || !sel || !xyz || !scaling || !workspace) return fail(GSR_ERR_INVALID_ARGUMENT, "null pointer");

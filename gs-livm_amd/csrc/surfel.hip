@@ -4,63 +4,37 @@
 //   n_j  = column k*_j of R(q_j), q = (w, x, y, z) as given (NOT renormalised, as the rasterizer uses it),
 //          R = [[1-2(y^2+z^2), 2(xy-wz), 2(xz+wy)], [2(xy+wz), 1-2(x^2+z^2), 2(yz-wx)], [2(xz-wy), 2(yz+wx), 1-2(x^2+y^2)]]
 //          (column k is the axis of scaling[.][k]: Sigma = R S^2 R^T, cov3d_from_scale_rot in preprocess.hip)
-//   j(i) = the nearest selected centre of point i (the similarity loss's rule: csrc/simi.hip)
+//   j(i) = the nearest selected centre of point i, ties to the lower position in `sel` (gsr_nearest.hpp)
 //   v_i = p_i - x_j,  d_i = |v_i|,  g_i = [d_i <= max_dist],  e_i = n_j . v_i
 //   rho(e) = |e| (huber = 0);  e^2 / (2 huber) for |e| <= huber, |e| - huber / 2 beyond it (huber > 0)
 //   L = lambda / m * sum_i g_i rho(e_i)  +  lambda_flat / n * sum_j scaling[j][k*_j]
 //
-// Three launches, the shape of simi.hip's:
-//   k_surfel_nearest  lane = point, workgroup = 64 points x one chunk of the gathered centres (staged through LDS 256
-//                     at a time, each of the four waves scans a quarter of a tile): per (point, chunk) the smallest
-//                     squared distance and its position in `sel` -- k_simi_nearest's arithmetic and tie rule; the
-//                     workgroups of the first point block also write k* per selected row and sum their chunk's
-//                     smallest scales (f64, fixed order)
-//   k_surfel_points   thread = point: fixed-order minimum over the chunks, the winner's centre, quaternion and k*, the
-//                     normal, gate, residual, rho and rho'; the point's 20-byte record (position in sel or -1, rho',
-//                     rho' v); per-workgroup partial sums of rho (f64) and counts of gated-in points
-//   k_surfel_grads    thread = selected row: walks the m records in ascending point order through LDS tiles and sums
-//                     those that name it (A = sum rho', B = sum rho' v: one order for a row many points share, no
-//                     atomics), then dL/dxyz = -(lambda/m) A n, dL/drotation = (dn/dq)^T (lambda/m) B (the 3x4 Jacobian
-//                     of the column, w included, no normalisation term: the activation's backward owns that) and
-//                     dL/dscaling[k*] = lambda_flat / n; workgroup 0 writes out4
+// The search, the launch plan and the row stores are gsr_nearest.hpp's (its header has the shape of the three
+// launches).  The walk of the 16-byte records stays written out in k_surfel_grads: taken from the header's
+// sum_records<4> the same walk measured 4 % on the whole call (0.126 against 0.121 ms at 3 000 x 50 000), written in
+// place it costs nothing; order and comparisons are sum_records'.  What is this term's:
+//   k_surfel_nearest  side job of the search: the workgroups of the first point block write k* per selected row and sum
+//                     their chunk's smallest scales (f64, fixed order)
+//   k_surfel_points   the winner's centre, quaternion and k*, the normal, gate, residual, rho and rho'; the point's
+//                     20-byte record (position in sel or -1, rho', rho' v); per-workgroup partial sums of rho (f64) and
+//                     counts of gated-in points
+//   k_surfel_grads    from the summed records (A = sum rho', B = sum rho' v) dL/dxyz = -(lambda/m) A n,
+//                     dL/drotation = (dn/dq)^T (lambda/m) B (the 3x4 Jacobian of the column, w included, no
+//                     normalisation term: the activation's backward owns that) and dL/dscaling[k*] = lambda_flat / n;
+//                     workgroup 0 writes out4
 // No float atomics, every reduction in a fixed order (bitwise reproducible), no host synchronisation, no allocation,
 // the caller's stream only.  The profiler's id word is full: the three launches are timed under K_SIMI_NEAREST /
-// K_SIMI_POINTS / K_SIMI_GRADS, whose kernels they resemble (gsr_kernel_count() stays 64).
+// K_SIMI_POINTS / K_SIMI_GRADS, the ids of the family's three launches (gsr_kernel_count() stays 64).
 // Built with -ffp-contract=off (build.py): accumulate = 1 adds the very bits accumulate = 0 writes, so no product may
-// fuse into the add behind it; the multiply-adds of the search and of the residual are written out.
+// fuse into the add behind it; the multiply-add of the residual is written out.
 // Every global access is a 4-byte one (the doubles live in the workspace, which is carved from the next multiple of
 // 256): the caller's arrays need 4-byte alignment only.
 #include "gsr_api.hpp"
 #include "gsr_internal.hpp"
+#include "gsr_nearest.hpp"
 #include "gsr_workgroup.hpp"
 
 namespace gsr {
-
-constexpr int SF_PTS_ = 64;        // points per workgroup of k_surfel_nearest (one per lane)
-constexpr int SF_TILE_ = 256;      // centres staged per LDS tile (one per thread; 4 KiB: occupancy is not LDS-bound)
-constexpr int SF_TARGET_WGS_ = 1024;  // k_surfel_nearest's grid aims at four workgroups on each of the 256 CUs, once
-constexpr int SF_REC_TILE_ = 1024;  // records staged per LDS tile of k_surfel_grads
-
-struct SurfelPlan {
-  int pblocks, ntiles, tiles_per_chunk, nchunks, nblocks2;
-};
-
-// (simi_plan's rule: as many chunks over `sel` as fill the device once, no more -- every chunk costs each point one
-// partial record)
-static SurfelPlan surfel_plan(int m, int n) {
-  SurfelPlan p;
-  p.pblocks = (m + SF_PTS_ - 1) / SF_PTS_;
-  p.ntiles = (n + SF_TILE_ - 1) / SF_TILE_;
-  int want = SF_TARGET_WGS_ / (p.pblocks > 0 ? p.pblocks : 1);
-  if (want < 1) want = 1;
-  if (want > p.ntiles) want = p.ntiles;
-  if (want < 1) want = 1;
-  p.tiles_per_chunk = (p.ntiles + want - 1) / want;
-  if (p.tiles_per_chunk < 1) p.tiles_per_chunk = 1;
-  p.nchunks = (p.ntiles + p.tiles_per_chunk - 1) / p.tiles_per_chunk;  // (no empty chunk)
-  p.nblocks2 = (m + 255) / 256;
-  return p;
-}
 
 struct SurfelWorkspace {
   float* part_d2;     // [nchunks][m] smallest squared distance of the point inside the chunk
@@ -73,11 +47,8 @@ struct SurfelWorkspace {
   int* gate_part;     // [nblocks2]
   size_t bytes;
   static SurfelWorkspace carve(char* base, int m, int n) {
-    const SurfelPlan p = surfel_plan(m, n);
-    // the caller's workspace need not be aligned: the carving starts at the next multiple of ALIGN (the slack is part
-    // of `bytes`), as DeltaWorkspace
-    char* b = base ? reinterpret_cast<char*>(align_up(reinterpret_cast<uintptr_t>(base))) : nullptr;
-    Carver cv(b);
+    const NearestPlan p = nearest_plan(m, n);
+    Carver cv = Carver::aligned(base);
     SurfelWorkspace w;
     w.part_d2 = cv.take<float>((size_t)p.nchunks * m);
     w.part_k = cv.take<int>((size_t)p.nchunks * m);
@@ -87,14 +58,10 @@ struct SurfelWorkspace {
     w.rec_g = cv.take<float>((size_t)m * 4);
     w.rho_part = cv.take<double>((size_t)p.nblocks2);
     w.gate_part = cv.take<int>((size_t)p.nblocks2);
-    w.bytes = align_up(cv.off) + ALIGN;
+    w.bytes = cv.bytes();
     return w;
   }
 };
-
-// A row index of `sel` as the kernels use it for READS: clamped into [0, P) (simi.hip's clamp_row: a selection that
-// breaks its contract reads a wrong row instead of foreign memory; writes test the unclamped index and are skipped).
-__device__ __forceinline__ int surfel_row(int row, int P) { return min(max(row, 0), P - 1); }
 
 // Column k of R(q), q = (w, x, y, z) as given.
 __device__ __forceinline__ void surfel_axis(const int k, const float w, const float x, const float y, const float z,
@@ -115,67 +82,18 @@ __global__ __launch_bounds__(256) void k_surfel_nearest(const int P, const int m
                                                         const float* __restrict__ scaling,
                                                         float* __restrict__ part_d2, int* __restrict__ part_k,
                                                         int* __restrict__ kstar, double* __restrict__ flat_part) {
-  __shared__ float4 cs[SF_TILE_];   // one broadcast ds_read_b128 per centre
-  __shared__ float wd2[4][SF_PTS_];
-  __shared__ int wk[4][SF_PTS_];
   __shared__ double shsum[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int i = blockIdx.x * SF_PTS_ + lane;
-  const int ic = min(i, m - 1);
-  const float px = points[3 * (size_t)ic], py = points[3 * (size_t)ic + 1], pz = points[3 * (size_t)ic + 2];
-  const int t0 = blockIdx.y * tiles_per_chunk, t1 = min(t0 + tiles_per_chunk, ntiles);
-  const bool sums = blockIdx.x == 0;  // (uniform over the workgroup)
-  float best = __builtin_inff();
-  int bestk = -1;
   double ssum = 0.0;
-  for (int t = t0; t < t1; t++) {
-    const int k = t * SF_TILE_ + (int)threadIdx.x;
-    // a slot past the end holds a centre no finite point is near: its squared distance overflows to +inf, which never
-    // passes the strict comparison
-    float4 c = make_float4(3e38f, 3e38f, 3e38f, 0.f);
-    if (k < n) {
-      const size_t row = (size_t)surfel_row(sel[k], P);
-      c.x = xyz[3 * row]; c.y = xyz[3 * row + 1]; c.z = xyz[3 * row + 2];
-      if (sums) {
-        float smin = scaling[3 * row];
-        int ks = 0;
-        const float s1 = scaling[3 * row + 1], s2 = scaling[3 * row + 2];
-        if (s1 < smin) { smin = s1; ks = 1; }
-        if (s2 < smin) { smin = s2; ks = 2; }
-        kstar[k] = ks;
-        ssum += (double)smin;
-      }
-    }
-    __syncthreads();  // (the previous tile has been scanned)
-    cs[threadIdx.x] = c;
-    __syncthreads();
-    const int j0 = wave * 64;
-#pragma unroll 8
-    for (int j = 0; j < 64; j++) {
-      const float4 q = cs[j0 + j];
-      const float dx = px - q.x, dy = py - q.y, dz = pz - q.z;
-      const float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-      if (d2 < best) { best = d2; bestk = t * SF_TILE_ + j0 + j; }  // ascending positions, strict: the lowest wins a tie
-    }
-  }
-  wd2[wave][lane] = best;
-  wk[wave][lane] = bestk;
-  __syncthreads();
-  if (wave == 0 && i < m) {
-    float b = wd2[0][lane];
-    int bk = wk[0][lane];
-#pragma unroll
-    for (int w = 1; w < 4; w++) {
-      const float d = wd2[w][lane];
-      const int kk = wk[w][lane];
-      // over several tiles wave 0 may hold a LATER position than wave 1: equal distances are settled by the position
-      if (d < b || (d == b && kk >= 0 && (bk < 0 || kk < bk))) { b = d; bk = kk; }
-    }
-    const size_t o = (size_t)blockIdx.y * m + i;
-    part_d2[o] = b;
-    part_k[o] = bk;
-  }
-  if (sums) {
+  nearest_chunk_scan(P, m, n, tiles_per_chunk, ntiles, points, sel, xyz, part_d2, part_k, [&](int k, size_t row3) {
+    float smin = scaling[row3];
+    int ks = 0;
+    const float s1 = scaling[row3 + 1], s2 = scaling[row3 + 2];
+    if (s1 < smin) { smin = s1; ks = 1; }
+    if (s2 < smin) { smin = s2; ks = 2; }
+    kstar[k] = ks;
+    ssum += (double)smin;
+  });
+  if (blockIdx.x == 0) {  // (uniform over the workgroup: the workgroups whose threads ran the side job)
     const double s = block_sum(ssum, shsum);
     if (threadIdx.x == 0) flat_part[blockIdx.y] = s;
   }
@@ -196,19 +114,15 @@ __global__ __launch_bounds__(256) void k_surfel_points(const int P, const int m,
   float rho = 0.f;
   int gated = 0;
   if (i < m) {
-    float best = __builtin_inff();
-    int bk = -1;
-    for (int c = 0; c < nchunks; c++) {  // ascending chunks hold ascending positions: strict, the lowest wins a tie
-      const float d = part_d2[(size_t)c * m + i];
-      const int kk = part_k[(size_t)c * m + i];
-      if (d < best) { best = d; bk = kk; }
-    }
+    const NearestHit hit = nearest_over_chunks(part_d2, part_k, m, nchunks, i);
+    const float best = hit.d2;
+    const int bk = hit.k;
     int rk = -1;
     float dr = 0.f, bx = 0.f, by = 0.f, bz = 0.f;
     // (bk < 0: no centre compared below +inf -- a non-finite point or centre: nothing is added, nothing is written;
     // bk >= n: a padding slot of the last tile, which only a point beyond 1e38 can be near: no centre either)
     if (bk >= 0 && bk < n && sqrtf(best) <= max_dist) {
-      const size_t row = (size_t)surfel_row(sel[bk], P);
+      const size_t row = (size_t)clamp_row(sel[bk], P);
       const float vx = points[3 * (size_t)i] - xyz[3 * row], vy = points[3 * (size_t)i + 1] - xyz[3 * row + 1],
                   vz = points[3 * (size_t)i + 2] - xyz[3 * row + 2];
       float n0, n1, n2;
@@ -251,7 +165,7 @@ __global__ __launch_bounds__(256) void k_surfel_grads(const int P, const int m, 
                                                       float* __restrict__ out4, float* __restrict__ grad_xyz,
                                                       float* __restrict__ grad_scaling,
                                                       float* __restrict__ grad_rotation) {
-  __shared__ __attribute__((aligned(16))) int sk[SF_REC_TILE_];
+  __shared__ __attribute__((aligned(16))) int sk[NEAREST_REC_TILE];
   __shared__ double shsum[4];
   if (blockIdx.x == 0) {  // (uniform over the workgroup)
     double rs, cnt;
@@ -270,15 +184,15 @@ __global__ __launch_bounds__(256) void k_surfel_grads(const int P, const int m, 
   const int kq = k < n ? k : -2;  // (-2 matches no record; the thread still helps to stage)
   float a = 0.f, bx = 0.f, by = 0.f, bz = 0.f;
   if (grad_xyz || grad_rotation) {
-    for (int base = 0; base < m; base += SF_REC_TILE_) {
+    for (int base = 0; base < m; base += NEAREST_REC_TILE) {
       __syncthreads();
 #pragma unroll
-      for (int q = 0; q < SF_REC_TILE_ / 256; q++) {
+      for (int q = 0; q < NEAREST_REC_TILE / 256; q++) {
         const int i = base + q * 256 + (int)threadIdx.x;
         sk[q * 256 + threadIdx.x] = i < m ? rec_k[i] : -1;
       }
       __syncthreads();
-      const int cntv = min(SF_REC_TILE_, m - base);
+      const int cntv = min(NEAREST_REC_TILE, m - base);
       for (int q = 0; q < cntv; q += 4) {  // ascending point order: the sum of a shared row has ONE order
         const int4 v = *reinterpret_cast<const int4*>(&sk[q]);  // (the same address in every lane: a broadcast read)
         if (v.x == kq || v.y == kq || v.z == kq || v.w == kq) {
@@ -304,9 +218,8 @@ __global__ __launch_bounds__(256) void k_surfel_grads(const int P, const int m, 
     float n0, n1, n2;
     surfel_axis(ks, qw, qx, qy, qz, n0, n1, n2);
     const float ca = -(c * a);
-    float* g = grad_xyz + 3 * (size_t)row;
-    if (accumulate) { g[0] += ca * n0; g[1] += ca * n1; g[2] += ca * n2; }
-    else { g[0] = ca * n0; g[1] = ca * n1; g[2] = ca * n2; }
+    const float v[3] = {ca * n0, ca * n1, ca * n2};
+    store_row(grad_xyz + 3 * (size_t)row, v, accumulate);
   }
   if (grad_rotation) {
     // (dn/dq)^T b for the column ks of R, b = (lambda/m) B: the derivative of the polynomial, all four components
@@ -328,9 +241,8 @@ __global__ __launch_bounds__(256) void k_surfel_grads(const int P, const int m, 
       gy = 2.f * (qw * b0 + qz * b1) - 4.f * qy * b2;
       gz = 2.f * (qx * b0 + qy * b1);
     }
-    float* g = grad_rotation + 4 * (size_t)row;
-    if (accumulate) { g[0] += gw; g[1] += gx; g[2] += gy; g[3] += gz; }
-    else { g[0] = gw; g[1] = gx; g[2] = gy; g[3] = gz; }
+    const float v[4] = {gw, gx, gy, gz};
+    store_row(grad_rotation + 4 * (size_t)row, v, accumulate);
   }
   if (grad_scaling) {
     // the flatness prior reaches the thin axis only; the choice of k* carries no gradient
@@ -360,7 +272,7 @@ static hipError_t launch_surfel_plane_loss(int P, int m, int n, const float* poi
     hipLaunchKernelGGL(k_surfel_zero4, dim3(1), dim3(64), 0, s, out4);
     return hipGetLastError();
   }
-  const SurfelPlan p = surfel_plan(m, n);
+  const NearestPlan p = nearest_plan(m, n);
   const SurfelWorkspace w = SurfelWorkspace::carve(workspace, m, n);
   {
     ProfScope ps(K_SIMI_NEAREST, s);
@@ -390,7 +302,7 @@ using namespace gsr;
 extern "C" {
 
 size_t gsr_surfel_plane_loss_workspace(int m, int n) {
-  if (m <= 0 || n <= 0 || n > 0x7fffffff - 1024) return 0;
+  if (m <= 0 || n <= 0 || n > NEAREST_MAX_N) return 0;
   return surfel_workspace_bytes(m, n);
 }
 
@@ -399,9 +311,7 @@ int gsr_surfel_plane_loss(int P, int m, int n, const float* points, const int* s
                           float lambda_flat, float* out4, float* grad_xyz, float* grad_scaling, float* grad_rotation,
                           int accumulate, char* workspace, size_t workspace_bytes, void* stream_) {
   clear_error();
-  if (P < 0 || m < 0 || n < 0) return fail(GSR_ERR_INVALID_ARGUMENT, "bad P/m/n");
-  if (n > P) return fail(GSR_ERR_INVALID_ARGUMENT, "n = %d selected rows of P = %d (the selection is unique)", n, P);
-  if (n > 0x7fffffff - 1024) return fail(GSR_ERR_INVALID_ARGUMENT, "n too large");
+  if (int e = check_selection_sizes(P, m, n)) return e;
   if (!(lambda >= 0.f && lambda < __builtin_inff())) return fail(GSR_ERR_INVALID_ARGUMENT, "bad lambda");
   if (!(huber >= 0.f && huber < __builtin_inff())) return fail(GSR_ERR_INVALID_ARGUMENT, "bad huber");
   if (!(lambda_flat >= 0.f && lambda_flat < __builtin_inff())) return fail(GSR_ERR_INVALID_ARGUMENT, "bad lambda_flat");

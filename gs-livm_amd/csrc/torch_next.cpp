@@ -195,15 +195,20 @@ struct WeightedLossFn : public torch::autograd::Function<WeightedLossFn> {
   }
 };
 
+// the selection of operator `op` (the terms on selected Gaussians), as the library reads it
+torch::Tensor selection_rows(const torch::Tensor& sel, const char* op) {
+  if (!sel.defined() || !sel.is_cuda() || sel.scalar_type() != torch::kInt32 || sel.dim() != 1)
+    throw std::invalid_argument(std::string(op) + ": sel is a 1-d int32 tensor on the device");
+  return sel.contiguous();
+}
+
 struct SimilarityLossFn : public torch::autograd::Function<SimilarityLossFn> {
   static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor points, torch::Tensor sel,
                                torch::Tensor xyz, torch::Tensor scaling, double lambda) {
     const torch::Tensor p = dev_f32(points, "points"), x = dev_f32(xyz, "xyz"), s = dev_f32(scaling, "scaling");
-    if (!sel.defined() || !sel.is_cuda() || sel.scalar_type() != torch::kInt32 || sel.dim() != 1)
-      throw std::invalid_argument("similarity_loss: sel is a 1-d int32 tensor on the device");
+    const torch::Tensor rows = selection_rows(sel, "similarity_loss");
     if (p.dim() != 2 || p.size(1) != 3 || x.dim() != 2 || x.size(1) != 3 || s.sizes() != x.sizes())
       throw std::invalid_argument("similarity_loss: points [m,3], xyz [P,3], scaling [P,3]");
-    const torch::Tensor rows = sel.contiguous();
     const int P = x.size(0), m = p.size(0), n = rows.size(0);
     torch::Tensor gx = xyz.requires_grad() ? torch::zeros_like(x) : torch::Tensor();
     torch::Tensor gs = scaling.requires_grad() ? torch::zeros_like(s) : torch::Tensor();
@@ -232,12 +237,10 @@ struct SurfelPlaneLossFn : public torch::autograd::Function<SurfelPlaneLossFn> {
                                double huber, double max_dist, double lambda_flat) {
     const torch::Tensor p = dev_f32(points, "points"), x = dev_f32(xyz, "xyz"), s = dev_f32(scaling, "scaling"),
                         q = dev_f32(rotation, "rotation");
-    if (!sel.defined() || !sel.is_cuda() || sel.scalar_type() != torch::kInt32 || sel.dim() != 1)
-      throw std::invalid_argument("surfel_plane_loss: sel is a 1-d int32 tensor on the device");
+    const torch::Tensor rows = selection_rows(sel, "surfel_plane_loss");
     if (p.dim() != 2 || p.size(1) != 3 || x.dim() != 2 || x.size(1) != 3 || s.sizes() != x.sizes() || q.dim() != 2 ||
         q.size(0) != x.size(0) || q.size(1) != 4)
       throw std::invalid_argument("surfel_plane_loss: points [m,3], xyz [P,3], scaling [P,3], rotation [P,4]");
-    const torch::Tensor rows = sel.contiguous();
     const int P = x.size(0), m = p.size(0), n = rows.size(0);
     torch::Tensor gx = xyz.requires_grad() ? torch::zeros_like(x) : torch::Tensor();
     torch::Tensor gs = scaling.requires_grad() ? torch::zeros_like(s) : torch::Tensor();

@@ -51,13 +51,12 @@ struct VoxelWorkspace {
   size_t bytes;
   static VoxelWorkspace carve(char* base, int n) {
     const size_t nblocks = ((size_t)n + WG_THREADS - 1) / WG_THREADS;
-    char* b = base ? reinterpret_cast<char*>(align_up(reinterpret_cast<uintptr_t>(base))) : nullptr;
-    Carver cv(b);
+    Carver cv = Carver::aligned(base);
     VoxelWorkspace w;
     w.slots = cv.take<int>((size_t)n);
     w.totals = cv.take<int>(VOX_TOTALS * nblocks);
     w.codes = cv.take<unsigned char>((size_t)n);
-    w.bytes = align_up(cv.off) + ALIGN;
+    w.bytes = cv.bytes();
     return w;
   }
 };

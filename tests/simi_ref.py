@@ -52,6 +52,31 @@ def select_by_mask(index, losses, P):
     return points, loss_mask.nonzero().squeeze(1)
 
 
+TIE_CASES = [(64, 768, 64), (32768, 768, 192)]     # (m, n, D)
+TIE_QUATERNIONS = ((1.0, 0.0, 0.0, 0.0), (0.5, 0.5, 0.5, 0.5), (0.5, -0.5, 0.5, 0.25), (0.75, 0.25, -0.5, 0.5))
+
+
+def tie_inputs(m, n, D, device="cpu"):
+    """Inputs on which every point is at the SAME squared distance, bit for bit, from n / D selected centres: D
+    distinct centres on the integer lattice 8 x 8 x (D / 64), position k of `sel` holding lattice point k mod D (P = 2n
+    rows, the odd ones selected, so `sel` itself is unique), point i = lattice point i mod D + (1/8, 1/16, 0).
+    Everything is dyadic: the squared distance to the own lattice point is 5/256 in any order of operations, with or
+    without a fused multiply-add, and the next lattice point is 0.77 away.  All scales are 2^-6 (r = 2^-6 exactly: every
+    point lies outside it; k* = 0 on every row); the quaternion of position k is entry (k + k // D) mod 4 of a dyadic
+    table, so that the copies of a centre differ in their normals."""
+    assert D % 64 == 0 and n % D == 0
+    cell = torch.arange(D)
+    lattice = torch.stack([cell % 8, (cell // 8) % 8, cell // 64], 1).float()
+    k = torch.arange(n)
+    P = 2 * n
+    xyz = lattice[k % D].repeat_interleave(2, 0)
+    rotation = torch.tensor(TIE_QUATERNIONS)[(k + k // D) % 4].repeat_interleave(2, 0)
+    points = lattice[torch.arange(m) % D] + torch.tensor([0.125, 0.0625, 0.0])
+    return dict(P=P, m=m, n=n, D=D, points=points.to(device), sel=(2 * k + 1).int().to(device),
+                xyz=xyz.contiguous().to(device), scaling=torch.full((P, 3), 2.0 ** -6).to(device),
+                rotation=rotation.contiguous().to(device))
+
+
 def voxel_key(ix, iy, iz):
     """A distinct non-negative key per lattice cell (|i| < 2^15 per axis)."""
     return (int(ix) + 32768) | ((int(iy) + 32768) << 16) | ((int(iz) + 32768) << 32)

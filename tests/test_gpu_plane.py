@@ -47,6 +47,7 @@ import torch
 
 import gs_livm_amd as G
 import plane_ref as PR
+import simi_ref
 from arena import Arena, offsets
 from gs_livm_amd import _capi
 
@@ -285,6 +286,29 @@ def test_buffers_at_any_four_byte_offset(off, gpu_device):
     assert A.guards_intact() is None
     for k, w in zip(("out4", "gx", "gs", "gr"), want):
         assert torch.equal(A.t[k], w), k
+
+
+@pytest.mark.parametrize("m,n,D", simi_ref.TIE_CASES)
+def test_a_tie_goes_to_the_lowest_position_in_sel(m, n, D, gpu_device):
+    """The similarity loss's tie rule is this term's (include/gsraster.h): tests/test_gpu_simi.py's test of this name
+    has the inputs and the arithmetic of where the copies of a centre sit in the search (the two terms share the launch
+    plan).  The copies of a centre carry other quaternions than the centre: a point that chose one would change the four
+    outputs too.  lambda_flat = 0, max_dist = inf, and a dyadic knee that some residuals lie inside and some beyond."""
+    c = simi_ref.tie_inputs(m, n, D, gpu_device)
+
+    def run(sel):
+        gx, gs, gr = (torch.zeros_like(c[k]) for k in ("xyz", "scaling", "rotation"))
+        out4 = _capi.surfel_plane_loss(c["points"], sel, c["xyz"], c["scaling"], c["rotation"], LAM, 0.0625,
+                                       float("inf"), 0.0, gx, gs, gr)
+        return out4, gx, gr
+
+    first, copies = c["sel"][:D].long(), c["sel"][D:].long()
+    (out4, gx, gr), (want4, want_gx, want_gr) = run(c["sel"]), run(c["sel"][:D].contiguous())
+    assert float(want4[3]) == 1.0 and float(want4[1]) > 0                  # every point is gated in and off its plane
+    assert bool(want_gx[first].any(1).all())                               # every distinct centre is some point's nearest
+    assert torch.equal(out4, want4)
+    assert torch.equal(gx[first], want_gx[first]) and torch.equal(gr[first], want_gr[first])
+    assert not bool(gx[copies].any()) and not bool(gr[copies].any())
 
 
 def test_the_similarity_loss_keeps_its_bits(gpu_device):

@@ -209,6 +209,35 @@ def test_accumulate_untouched_rows_and_reproducibility(m, n, gpu_device):
     assert _capi.similarity_loss(c["points"], c["sel"][:0], c["xyz"], c["scaling"], LAM).tolist() == [0.0, 0.0, 0.0]
 
 
+@pytest.mark.parametrize("m,n,D", R.TIE_CASES)
+def test_a_tie_goes_to_the_lowest_position_in_sel(m, n, D, gpu_device):
+    """Of several selected centres at bit-equal squared distance the lowest position in `sel` wins (include/gsraster.h),
+    whichever wave, tile or chunk of the search holds the others.  R.tie_inputs: position k holds lattice point k mod D,
+    exact in float32, so the call on the whole selection must give the bits of the call on its first D positions, and
+    no copy (position >= D) may receive a gradient.  Where the copies sit, by the launch plan's arithmetic (64 points
+    per point block, 256 centres per tile, a quarter of a tile per wave, chunks = min(1024 // point blocks, tiles)):
+      m = 64, n = 768, D = 64:      1 point block, 3 tiles, min(1024, 3) = 3 chunks of 1 tile.  Centre j has copies at
+          j + 64, j + 128, j + 192 (the other three waves of its tile) and at j + 256 .. j + 704 (the other two chunks).
+      m = 32768, n = 768, D = 192:  512 point blocks, 3 tiles, 1024 // 512 = 2 chunks of ceil(3 / 2) = 2 tiles: chunk 0
+          is tiles 0-1, chunk 1 is tile 2.  For j < 64, position 64 + j (tile 0, wave 1) ties with 256 + j (tile 1,
+          wave 0): wave 0 scans positions 0 .. 63 and then 256 .. 319, so it holds the LATER position of the two and
+          the combine of the four waves must settle it by the position.  Positions j and 128 + j tie with 576 + j and
+          512 + j, which lie in chunk 1."""
+    c = R.tie_inputs(m, n, D, gpu_device)
+
+    def run(sel):
+        gx, gs = torch.zeros_like(c["xyz"]), torch.zeros_like(c["scaling"])
+        return _capi.similarity_loss(c["points"], sel, c["xyz"], c["scaling"], LAM, gx, gs), gx
+
+    first, copies = c["sel"][:D].long(), c["sel"][D:].long()
+    (out3, gx), (want3, want_gx) = run(c["sel"]), run(c["sel"][:D].contiguous())
+    assert float(want3[2]) == 2.0 ** -6 and float(want3[1]) > 0.1          # r, and every point far outside it
+    assert bool(want_gx[first].any(1).all())                               # every distinct centre is some point's nearest
+    assert torch.equal(out3, want3)
+    assert torch.equal(gx[first], want_gx[first])
+    assert not bool(gx[copies].any())
+
+
 def _model_from(c, fused_tail):
     """GaussianParameters whose activated scales are the scene's (raw = log) -- exp(log(s)) rounds: the float64
     reference is taken at the activated values the node actually saw."""
