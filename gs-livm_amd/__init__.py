@@ -17,6 +17,8 @@ Layout (only what the hot path needs):
                    (per-pixel weights, a silhouette gate, the exposure)
   covis.py         keyframe covisibility: visibility bitsets, their overlap counts, observation counts, the remap a prune needs
   contribution.py  per-Gaussian blend contribution of a forward: pixels touched, summed and largest blend weight
+  normals.py       rendered normal maps (per-Gaussian attributes blended behind a forward, camera-facing surfel normals) and
+                   the depth-normal consistency loss (csrc/normal.hip)
   metrics.py       fused evaluation pass: PSNR / SSIM / L1 of a render, 8-bit frame export, the keyframe sweep
   model.py         fused activations + Adam for the caller's leaf tensors (SURVEY.md 8(f) "next" row 1)
   synthetic.py     synthetic scenes of SURVEY.md section 8(d) for tests and bench
@@ -38,6 +40,8 @@ from .loss import (DeltaDepthLoss, ExposureLoss, LidarDepthLoss, RobustLidarDept
 from .covis import (KeyframeVisibility, covisibility, iou, observation_count, overlap_coefficient,  # noqa: F401
                     visibility_pack, visibility_remap)
 from .contribution import Contribution, contribution, low_contribution, render_contribution  # noqa: F401
+from .normals import (NormalConsistencyLoss, blend_attributes, normal_consistency_loss, render_attributes,  # noqa: F401
+                      render_normals, surfel_normals)
 from .metrics import depth_to_u8, evaluate_keyframes, image_metrics, psnr, side_by_side, to_u8  # noqa: F401
 from .model import FusedActivations, FusedAdam, GaussianParameters, GrowableAdam, GrowableGaussians, VoxelIndex, prune_rows  # noqa: F401
 from . import ply  # noqa: F401
@@ -65,5 +69,5 @@ def torch_ops():
     return mod
 
 
-__all__ = ["Admitted", "admit_sweep", "SweepVoxelMap", "VoxelSeeds", "WeightedPhotometricLoss", "weighted_photometric_loss", "Contribution", "contribution", "render_contribution", "low_contribution", "KeyframeVisibility", "visibility_pack", "covisibility", "observation_count", "visibility_remap", "iou", "overlap_coefficient", "ExposureLoss", "exposure_photometric_loss", "apply_exposure", "identity_exposure", "LidarDepthLoss", "RobustLidarDepthLoss", "lidar_occlusion_filter", "lidar_depth_image", "lidar_depth_loss", "raster_K", "world_to_camera", "prune_rows", "image_metrics", "psnr", "to_u8", "side_by_side", "depth_to_u8", "evaluate_keyframes", "DeltaDepthLoss", "delta_depth_loss", "delta_pose", "SimilarityLoss", "similarity_loss", "SurfelPlaneLoss", "surfel_plane_loss", "VoxelIndex", "PhotometricLoss", "photometric_loss", "reference_window_1d", "FusedActivations", "FusedAdam", "GaussianParameters", "GrowableAdam", "GrowableGaussians", "ply", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "Camera", "render", "render_full", "se3_exp", "pose_gradient", "get_projection_matrix", "rasterize_forward",
+__all__ = ["NormalConsistencyLoss", "blend_attributes", "normal_consistency_loss", "render_attributes", "render_normals", "surfel_normals", "Admitted", "admit_sweep", "SweepVoxelMap", "VoxelSeeds", "WeightedPhotometricLoss", "weighted_photometric_loss", "Contribution", "contribution", "render_contribution", "low_contribution", "KeyframeVisibility", "visibility_pack", "covisibility", "observation_count", "visibility_remap", "iou", "overlap_coefficient", "ExposureLoss", "exposure_photometric_loss", "apply_exposure", "identity_exposure", "LidarDepthLoss", "RobustLidarDepthLoss", "lidar_occlusion_filter", "lidar_depth_image", "lidar_depth_loss", "raster_K", "world_to_camera", "prune_rows", "image_metrics", "psnr", "to_u8", "side_by_side", "depth_to_u8", "evaluate_keyframes", "DeltaDepthLoss", "delta_depth_loss", "delta_pose", "SimilarityLoss", "similarity_loss", "SurfelPlaneLoss", "surfel_plane_loss", "VoxelIndex", "PhotometricLoss", "photometric_loss", "reference_window_1d", "FusedActivations", "FusedAdam", "GaussianParameters", "GrowableAdam", "GrowableGaussians", "ply", "GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians", "Camera", "render", "render_full", "se3_exp", "pose_gradient", "get_projection_matrix", "rasterize_forward",
            "rasterize_backward", "mark_visible", "state_views", "set_reference_rects", "reference_rects", "last_num_rendered", "set_binning_capacity_hint", "speculation_stats", "emit_guard_trips", "mailbox_slow_path_last", "set_near_far", "set_near_far_thread", "set_reference_rects_thread", "async_outcomes_pending", "set_near_far_hints", "last_near_far", "set_far_speculation", "last_far_skipped", "NumRendered", "lib", "torch_ops", "synthetic", "multiview", "GsrError", "LIB_PATH"]

@@ -78,7 +78,8 @@ EXPORTS = ("gsr_forward", "gsr_backward", "gsr_backward_depth", "gsr_mark_visibl
            "gsr_sweep_admit", "gsr_sweep_admit_workspace", "gsr_lidar_occlusion_filter",
            "gsr_lidar_depth_loss_robust", "gsr_lidar_depth_loss_robust_workspace", "gsr_voxel_table_bytes",
            "gsr_voxel_sweep_workspace", "gsr_voxel_sweep", "gsr_voxel_rehash", "gsr_surfel_plane_loss",
-           "gsr_surfel_plane_loss_workspace")
+           "gsr_surfel_plane_loss_workspace", "gsr_blend_attributes", "gsr_surfel_normals",
+           "gsr_normal_consistency_workspace", "gsr_normal_consistency_loss")
 
 
 def lib():
@@ -265,6 +266,14 @@ def lib():
     L.gsr_contribution.argtypes = [ci, ci, ci, ci, vp, vp, vp, vp, vp]
     L.gsr_contribution_finish.restype = ci
     L.gsr_contribution_finish.argtypes = [ci, vp, ci, cf, vp, vp, vp, vp, vp, vp]
+    L.gsr_blend_attributes.restype = ci
+    L.gsr_blend_attributes.argtypes = [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.gsr_surfel_normals.restype = ci
+    L.gsr_surfel_normals.argtypes = [ci, vp, vp, vp, C.POINTER(cf), vp, vp]
+    L.gsr_normal_consistency_workspace.restype = sz
+    L.gsr_normal_consistency_workspace.argtypes = [ci, ci]
+    L.gsr_normal_consistency_loss.restype = ci
+    L.gsr_normal_consistency_loss.argtypes = [ci, ci, vp, vp, vp, cf, cf, cf, cf, cf, cf, cf, cf, vp, vp, vp, vp, sz, vp]
     L.gsr_init_gaussians.restype = ci
     L.gsr_init_gaussians.argtypes = [ci, ci, vp, vp, vp, cf] + [vp] * 6 + [vp]
     L.gsr_ply_row_floats.restype = sz
@@ -1191,6 +1200,59 @@ def contribution_finish(rows, min_pixels=1, min_weight=0.0, n_touched=None, weig
         assert t is None or (t.is_cuda and t.is_contiguous() and t.dtype == dt and t.numel() == n)
     _check(lib().gsr_contribution_finish(P, _ptr(rows), int(min_pixels), float(min_weight), _ptr(n_touched),
                                          _ptr(weight_sum), _ptr(weight_max), _ptr(mask), _ptr(stats), _stream()))
+
+
+# ---- rendered normal maps and the depth-normal consistency loss (include/gsraster.h; csrc/normal.hip) ----
+def blend_attributes(P, R, W, H, attributes, geomBuffer, binningBuffer, imageBuffer, out=None):
+    """Per-Gaussian attributes blended into an image behind a completed forward, one launch (gsr_blend_attributes; the
+    walk is csrc/render.hip's k_attribute_tile).  attributes: [P, C] (or [P], C = 1) f32 on the device, C in 1..4.
+    R: what rasterize_forward returned (its key is used).  out: a contiguous f32 device tensor of C * H * W elements to
+    write instead of a new one.  Returns [C, H, W]."""
+    P, W, H = int(P), int(W), int(H)
+    assert attributes.is_cuda and attributes.is_contiguous() and attributes.dtype == torch.float32
+    assert attributes.dim() in (1, 2) and int(attributes.shape[0]) == P
+    ch = int(attributes.shape[1]) if attributes.dim() == 2 else 1
+    if out is None:
+        out = torch.empty((ch, H, W), dtype=torch.float32, device=attributes.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == ch * H * W
+    _check(lib().gsr_blend_attributes(P, _key(R), W, H, ch, _ptr(attributes), _ptr(geomBuffer), _ptr(binningBuffer),
+                                      _ptr(imageBuffer), _ptr(out), _stream()))
+    return out
+
+
+def surfel_normals(xyz, scaling, rotation, T_cw, out=None):
+    """Camera-facing normals of the surfels' thin axes, one launch (gsr_surfel_normals).  xyz, scaling [P,3] and
+    rotation [P,4]: the ACTIVATED values, f32 on the device; T_cw: [R | t] (3x4 or 4x4) on the host.  Returns [P,3]."""
+    P = int(xyz.shape[0])
+    for t, w in ((xyz, 3), (scaling, 3), (rotation, 4)):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (P, w)
+    if out is None:
+        out = torch.empty((P, 3), dtype=torch.float32, device=xyz.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == 3 * P
+    tcw = (C.c_float * 12)(*[float(v) for v in torch.as_tensor(T_cw).detach().cpu().double()[:3, :4].reshape(-1)])
+    _check(lib().gsr_surfel_normals(P, _ptr(xyz), _ptr(scaling), _ptr(rotation), tcw, _ptr(out), _stream()))
+    return out
+
+
+def normal_consistency_loss(depth, acc, normals, fx, fy, cx, cy, acc_min, normal_min, jump_rel, lambda_,
+                            want_grad_depth=True, want_grad_acc=True):
+    """The depth-normal consistency loss in three launches, two without gradients (include/gsraster.h,
+    gsr_normal_consistency_loss).  depth / acc: the rasterizer's second and third outputs, [H,W] or [1,H,W] f32 on the
+    device; normals: [3,H,W], un-normalised.  Returns (out3 = [loss, mean rho, supervised share] device tensor,
+    dL/ddepth or None, dL/dacc or None), the gradients shaped like depth and acc."""
+    H, W = int(depth.shape[-2]), int(depth.shape[-1])
+    for t, n in ((depth, H * W), (acc, H * W), (normals, 3 * H * W)):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.numel() == n
+    nbytes = int(lib().gsr_normal_consistency_workspace(H, W))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=depth.device)
+    out3 = torch.empty(3, dtype=torch.float32, device=depth.device)
+    gd = torch.empty_like(depth) if want_grad_depth else None
+    ga = torch.empty_like(acc) if want_grad_acc else None
+    _check(lib().gsr_normal_consistency_loss(H, W, _ptr(depth), _ptr(acc), _ptr(normals), float(fx), float(fy),
+                                             float(cx), float(cy), float(acc_min), float(normal_min), float(jump_rel),
+                                             float(lambda_), _ptr(out3), _ptr(gd), _ptr(ga), _ptr(ws), nbytes,
+                                             _stream()))
+    return out3, gd, ga
 
 
 # ---- adaptive density control (include/gsraster.h; csrc/densify.hip) ----

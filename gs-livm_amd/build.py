@@ -50,12 +50,17 @@ UNITS = {
     "contrib.hip": [],  # (entry points + the finish kernel; the walk is built with render.hip, whose alpha it recomputes)
     # the accumulated gradient norm and the clone / split marks are restated bit for bit in float32 on the host
     "densify.hip": ["-ffp-contract=off"],
+    # the thin axis of a surfel (gsr_surfel_axis.hpp) must have surfel.hip's bits, so the unit is built as surfel.hip is;
+    # every multiply-add of the normals kernel is explicit, and the loss kernels are restated operation for operation in
+    # float32 Torch ops (tests/normal_ref.py).  The attribute walk is not here: it is built with render.hip
+    "normal.hip": ["-ffp-contract=off"],
     "metrics.hip": ["-fno-slp-vectorize"],  # (k_metrics_forward is k_loss_forward's arithmetic: built like loss.hip)
     "api.hip": [],
 }
 HEADERS = [os.path.join(CSRC, "gsr_internal.hpp"), os.path.join(CSRC, "gsr_api.hpp"), os.path.join(CSRC, "sort_core.hpp"),
            os.path.join(CSRC, "gsr_workgroup.hpp"), os.path.join(CSRC, "gsr_window.hpp"),
            os.path.join(CSRC, "gsr_lidar_project.hpp"), os.path.join(CSRC, "gsr_nearest.hpp"),
+           os.path.join(CSRC, "gsr_surfel_axis.hpp"),
            os.path.join(ROOT, "include", "gsraster.h")]
 
 

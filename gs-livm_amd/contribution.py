@@ -57,12 +57,10 @@ def contribution(fwd, P, W, H, min_pixels=1, min_weight=0.0, stats=None, want=WA
     return Contribution(rows=rows, **out)
 
 
-@torch.no_grad()
-def render_contribution(viewpoint_camera, gaussian_model, bg_color, scaling_modifier=1.0, override_color=None,
-                        min_pixels=1, min_weight=0.0, stats=None, want=WANT):
-    """A forward of `gaussian_model` from `viewpoint_camera` (no autograd graph) plus the contribution pass:
-    -> (color [3,H,W], depth [1,H,W], depth_acc [1,H,W], radii [P] int32, Contribution).  stats=True folds the view into
-    the model's own statistics (GrowableGaussians.enable_contribution_stats()); a tensor is used as given."""
+def forward_of(viewpoint_camera, gaussian_model, bg_color, scaling_modifier=1.0, override_color=None):
+    """A forward of `gaussian_model` from `viewpoint_camera` for the passes that walk its tile lists afterwards
+    (contribution, attribute blend): -> (the tuple `rasterize_forward` returned, P, W, H, the activated (xyz, scaling,
+    rotation) it rendered).  Call under no_grad."""
     cam = viewpoint_camera
     dev = gaussian_model.Get_xyz().device
     if hasattr(gaussian_model, "activated"):
@@ -80,11 +78,21 @@ def render_contribution(viewpoint_camera, gaussian_model, bg_color, scaling_modi
         rotations.contiguous(), float(scaling_modifier), empty, cam.Get_world_view_transform().contiguous(),
         cam.Get_full_proj_transform().contiguous(), math.tan(cam.Get_FoVx() * 0.5), math.tan(cam.Get_FoVy() * 0.5), H, W,
         shs.contiguous(), int(gaussian_model.Get_max_sh_degree()), cam.Get_camera_center().contiguous(), False, False)
+    return fwd, int(means3D.size(0)), W, H, (means3D, scales, rotations)
+
+
+@torch.no_grad()
+def render_contribution(viewpoint_camera, gaussian_model, bg_color, scaling_modifier=1.0, override_color=None,
+                        min_pixels=1, min_weight=0.0, stats=None, want=WANT):
+    """A forward of `gaussian_model` from `viewpoint_camera` (no autograd graph) plus the contribution pass:
+    -> (color [3,H,W], depth [1,H,W], depth_acc [1,H,W], radii [P] int32, Contribution).  stats=True folds the view into
+    the model's own statistics (GrowableGaussians.enable_contribution_stats()); a tensor is used as given."""
+    fwd, P, W, H, _ = forward_of(viewpoint_camera, gaussian_model, bg_color, scaling_modifier, override_color)
     if stats is True:
         stats = gaussian_model.contribution_stats()
         if stats is None:
             raise RuntimeError("render_contribution: call enable_contribution_stats() first")
-    c = contribution(fwd, int(means3D.size(0)), W, H, min_pixels, min_weight, stats, want)
+    c = contribution(fwd, P, W, H, min_pixels, min_weight, stats, want)
     return fwd[1], fwd[2], fwd[3], fwd[4], c
 
 

@@ -426,6 +426,10 @@ hipError_t launch_blend_backward(const FrameParams& fp, GeomState g, BinningStat
 // recomputes; entry points in contrib.hip): frame_rows [P] 16-byte rows, zero on entry; reads fp.W, H, gx, gy only
 hipError_t launch_contribution(const FrameParams& fp, GeomState g, BinningState b, ImageState im, char* frame_rows,
                                hipStream_t s);
+// per-Gaussian attributes blended into an image behind a completed forward (render.hip, the contribution's walk; entry
+// point in normal.hip): attributes [P][channels], out [channels][H][W], every element written; channels 1..4
+hipError_t launch_attributes(const FrameParams& fp, GeomState g, BinningState b, ImageState im, int channels,
+                             const float* attributes, float* out, hipStream_t s);
 hipError_t launch_gaussian_backward(const FrameParams& fp, GeomState g, BinningState b, const int* radii,
                                     const float* means3D, const float* scales, const float* rotations,
                                     const float* shs, const float* cov3D_precomp, const float* view, const float* proj,

@@ -351,6 +351,23 @@ Contribution contribution_finish(const torch::Tensor& rows, int64_t min_pixels =
                                  bool want_n_touched = true, bool want_weight_sum = true, bool want_weight_max = true,
                                  bool want_mask = true, const torch::Tensor& stats = torch::Tensor());
 
+// ---- rendered normal maps and the depth-normal consistency loss (an extension; csrc/normal.hip) -------------------------
+// Thin tensor-level hosts of gsr_blend_attributes / gsr_surfel_normals / gsr_normal_consistency_loss;
+// include/gsraster.h has the contracts.  blend_attributes: attributes [P, C] (or [P]) f32 on the device, C in 1..4,
+// blended behind the completed forward whose blobs and R are given -> [C, H, W].  surfel_normals: the ACTIVATED xyz
+// [P,3], scaling [P,3], rotation [P,4] and T_cw = [R | t] (3x4 or 4x4, any device) -> the camera-facing thin axes [P,3].
+// Neither builds an autograd graph; nothing waits.
+torch::Tensor blend_attributes(const torch::Tensor& geom, const torch::Tensor& binning, const torch::Tensor& img,
+                               const torch::Tensor& attributes, int64_t R, int64_t W, int64_t H);
+torch::Tensor surfel_normals(const torch::Tensor& xyz, const torch::Tensor& scaling, const torch::Tensor& rotation,
+                             const torch::Tensor& T_cw);
+// normal_consistency_loss: lambda * mean over the supervised pixels of 1 - n_r . n_d as ONE autograd node; depth / acc:
+// the rasterizer's second and third outputs, normals: blend_attributes of surfel_normals ([3,H,W], data), K: the 3x3
+// pinhole of the render.  Gradients w.r.t. depth and acc only.  lambda and normal_min have no default, on purpose.
+torch::Tensor normal_consistency_loss(const torch::Tensor& depth, const torch::Tensor& acc,
+                                      const torch::Tensor& normals, const torch::Tensor& K, float acc_min, float lambda,
+                                      float normal_min, float jump_rel = std::numeric_limits<float>::infinity());
+
 // ---- row 4: map growth and PLY export ---------------------------------------------------------------------------
 // The tensor construction of GaussianModel::addNewPointcloud (src/gs/gaussian.cu:241-313) for n new points -- xyz
 // [n,3], covs [n,3,3], rgbs [n,3] in 0..255 -- written IN PLACE into n-row views (normally the tail rows of capacity

@@ -1060,6 +1060,146 @@ hipError_t launch_contribution(const FrameParams& fp, GeomState g, BinningState 
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// Per-Gaussian attributes blended into an image (gsr_blend_attributes; an extension: the normal map of normal.hip is
+// its first caller).  out[c][pixel] = sum over the splats the pixel took of attr[splat][c] alpha T, front to back:
+// k_contribution_tile's walk written a second time -- the same wave per 16x16 tile, the same staging, the same gather,
+// the same take rule, alpha and T -- with the per-entry reductions and atomics replaced by CH accumulators per pixel,
+// acc <- fma(attr, alpha T, acc) in list order, the forward's own v_fmac for colour and depth.  (Written beside the
+// first rather than shared with it: k_contribution_tile stays the code it was, instruction for instruction.)
+// The attribute row of entry j is loaded by lane j with the splat record (4-byte loads: the rows need no wider
+// alignment) and parked in LDS beside the record's two float4s; a visit reads it back by broadcast.
+// A pixel belongs to one lane: plain stores, no atomics, no cross-lane sums, the same bits on every run.  Every pixel
+// of the image is written; one that takes nothing reads +0.0.  A wave's store per (k, channel) is four rows of 16
+// consecutive floats.
+// ------------------------------------------------------------------------------------------------
+template <int TW, int CH>  // TW tiles (= waves) per workgroup; the waves never synchronise.  CH channels, 1..4
+__global__ __launch_bounds__(64 * TW) void k_attribute_tile(
+    const FrameParams fp, const uint2* __restrict__ ranges, const uint2* __restrict__ rangesB,
+    const uint32_t* __restrict__ quad_last_in, const uint32_t* __restrict__ point_list,
+    const float4* __restrict__ splats, const uint32_t* __restrict__ n_contrib, const float* __restrict__ attributes,
+    float* __restrict__ out) {
+  __shared__ float4 sE[TW][64][2];  // (x, y, A', B' | C', opacity, -, -) per staged entry
+  __shared__ __attribute__((aligned(16))) float sAt[TW][64][CH];
+  const int lane = threadIdx.x & 63, wq = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int tile = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * TW + wq));
+  if (tile >= fp.gx * fp.gy) return;
+  const uint32_t ql0 = quad_last_in[4 * tile], ql1 = quad_last_in[4 * tile + 1], ql2 = quad_last_in[4 * tile + 2],
+                 ql3 = quad_last_in[4 * tile + 3];
+  // entries [0, n) of the tile's list were blended into at least one pixel's prefix (n == 0: the tile stores zeros)
+  const int n = __builtin_amdgcn_readfirstlane((int)max(max(ql0, ql1), max(ql2, ql3)));
+  const int tile_x = tile % fp.gx, tile_y = tile / fp.gx;
+  const uint2 rng = ranges[tile];
+  const uint32_t rbase = rng.x, rbaseB = rangesB[tile].x;
+  const int lenA = (int)(rng.y - rng.x);
+  const int px = tile_x * TILE + (lane & 15);
+  const float pfx = (float)px;
+  const float tx0 = (float)(tile_x * TILE), ty0 = (float)(tile_y * TILE);
+
+  float pfy[4], T[4], acc[4][CH];
+  int lastc[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int py = tile_y * TILE + 4 * k + (lane >> 4);
+    const bool inside = px < fp.W && py < fp.H;
+    pfy[k] = (float)py;
+    T[k] = 1.0f;
+    lastc[k] = inside ? (int)n_contrib[(size_t)fp.W * py + px] : 0;  // a pixel outside the image never takes a splat
+#pragma unroll
+    for (int c = 0; c < CH; c++) acc[k][c] = 0.0f;
+  }
+
+  float4 a = make_float4(0, 0, 0, 0), b = a;
+  float at[CH];
+#pragma unroll
+  for (int c = 0; c < CH; c++) at[c] = 0.0f;
+  bool hit = false;
+  auto gather = [&](const int pos) {
+    hit = false;
+    if (pos < n) {
+      const uint32_t id = pos < lenA ? point_list[rbase + (uint32_t)pos] : point_list[rbaseB + (uint32_t)(pos - lenA)];
+      a = splats[(size_t)id * SPLAT_F4 + 0];
+      b = splats[(size_t)id * SPLAT_F4 + 1];
+      const float4 c = splats[(size_t)id * SPLAT_F4 + 2];
+#pragma unroll
+      for (int ch = 0; ch < CH; ch++) at[ch] = attributes[(size_t)id * CH + ch];  // (id < P: the forward's own list)
+      // footprint box against the tile, then the ellipse itself (hx < 0: never; hx >= 1e6: indefinite conic, no culling)
+      hit = (a.x + c.z >= tx0) && (a.x - c.z <= tx0 + 15.0f) && (a.y + c.w >= ty0) && (a.y - c.w <= ty0 + 15.0f);
+      if (hit && c.z < 1.0e6f)
+        hit = ellipse_reaches_quad<15>(a.x, a.y, a.z, a.w, b.x, footprint_tau(b.y), tx0, ty0);
+    }
+  };
+  gather(lane);
+  for (int base = 0; base < n; base += 64) {
+    constexpr float L2E = 1.4426950408889634f;
+    sE[wq][lane][0] = make_float4(a.x, a.y, a.z * (-0.5f * L2E), a.w * (-L2E));
+    sE[wq][lane][1] = make_float4(b.x * (-0.5f * L2E), b.y, 0.f, 0.f);
+#pragma unroll
+    for (int c = 0; c < CH; c++) sAt[wq][lane][c] = at[c];
+    uint64_t m = __ballot(hit);
+    gather(base + 64 + lane);  // the next sub-chunk's gather completes while this one is walked
+    __builtin_amdgcn_wave_barrier();
+    while (m) {
+      const int jj = __builtin_ctzll(m);
+      m &= m - 1;
+      const int pos = base + jj;  // 0-based position in the tile's list: the forward's `last` of this entry is pos + 1
+      const float4 ea = sE[wq][jj][0];
+      const float4 eb = sE[wq][jj][1];
+      float ev[CH];
+#pragma unroll
+      for (int c = 0; c < CH; c++) ev[c] = sAt[wq][jj][c];
+      const float dx = ea.x - pfx;
+      const float dx2 = dx * dx;
+      const float Adx2 = ea.z * dx2;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const float dy = ea.y - pfy[k];
+        const float power = splat_power_shared(Adx2, ea.w, eb.x, dx, dy);  // = log2(e) x the reference's power
+        const float araw = fminf(0.99f, eb.y * __builtin_amdgcn_exp2f(power));
+        const bool ok = (pos < lastc[k]) && !(power > 0.0f) && !(araw < 1.0f / 255.0f);
+        if (ok) {
+          const float w = araw * T[k];  // the weight is formed from T BEFORE this splat
+#pragma unroll
+          for (int c = 0; c < CH; c++) acc[k][c] = __builtin_fmaf(ev[c], w, acc[k][c]);
+          float oma = 1.0f - araw;
+          asm volatile("" : "+v"(oma));  // (no fma(-alpha, T, T): the forward subtracts, then multiplies)
+          T[k] = T[k] * oma;  // the forward's test_T = T (1 - alpha)
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();  // (the next sub-chunk's stores to the LDS image come after these loads)
+  }
+  const size_t N = (size_t)fp.W * fp.H;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int py = tile_y * TILE + 4 * k + (lane >> 4);
+    if (px < fp.W && py < fp.H) {
+      const size_t pid = (size_t)fp.W * py + px;
+#pragma unroll
+      for (int c = 0; c < CH; c++) out[(size_t)c * N + pid] = acc[k][c];
+    }
+  }
+}
+
+hipError_t launch_attributes(const FrameParams& fp, GeomState g, BinningState b, ImageState im, int channels,
+                             const float* attributes, float* out, hipStream_t s) {
+  constexpr int TW = 4;
+  const int tiles = fp.gx * fp.gy;
+  const dim3 grid((tiles + TW - 1) / TW), block(64 * TW);
+#define GSR_ATTR_LAUNCH(CH)                                                                                          \
+  hipLaunchKernelGGL((k_attribute_tile<TW, CH>), grid, block, 0, s, fp, im.ranges, im.rangesB, im.quad_last,         \
+                     b.point_list, g.splats, im.n_contrib, attributes, out)
+  switch (channels) {
+    case 1: GSR_ATTR_LAUNCH(1); break;
+    case 2: GSR_ATTR_LAUNCH(2); break;
+    case 3: GSR_ATTR_LAUNCH(3); break;
+    case 4: GSR_ATTR_LAUNCH(4); break;
+    default: return hipErrorInvalidValue;
+  }
+#undef GSR_ATTR_LAUNCH
+  return hipGetLastError();
+}
+
 // Near/far frames: summed-area table of the tiles that still have an unfinished quad after the near phase, and their
 // number (total_live).  sat[(y + 1)(gx + 1) + (x + 1)] = live tiles in [0, x] x [0, y]; row 0 and column 0 are zero.
 // One workgroup.  IN_LDS (the table fits 150 KB: every frame up to ~3000 x 3000 px): flags in with coalesced loads,

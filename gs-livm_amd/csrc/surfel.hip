@@ -32,6 +32,7 @@
 #include "gsr_api.hpp"
 #include "gsr_internal.hpp"
 #include "gsr_nearest.hpp"
+#include "gsr_surfel_axis.hpp"
 #include "gsr_workgroup.hpp"
 
 namespace gsr {
@@ -63,18 +64,6 @@ struct SurfelWorkspace {
   }
 };
 
-// Column k of R(q), q = (w, x, y, z) as given.
-__device__ __forceinline__ void surfel_axis(const int k, const float w, const float x, const float y, const float z,
-                                            float& n0, float& n1, float& n2) {
-  if (k == 0) {
-    n0 = 1.f - 2.f * (y * y + z * z); n1 = 2.f * (x * y + w * z); n2 = 2.f * (x * z - w * y);
-  } else if (k == 1) {
-    n0 = 2.f * (x * y - w * z); n1 = 1.f - 2.f * (x * x + z * z); n2 = 2.f * (y * z + w * x);
-  } else {
-    n0 = 2.f * (x * z + w * y); n1 = 2.f * (y * z - w * x); n2 = 1.f - 2.f * (x * x + y * y);
-  }
-}
-
 __global__ __launch_bounds__(256) void k_surfel_nearest(const int P, const int m, const int n,
                                                         const int tiles_per_chunk, const int ntiles,
                                                         const float* __restrict__ points, const int* __restrict__ sel,
@@ -85,12 +74,8 @@ __global__ __launch_bounds__(256) void k_surfel_nearest(const int P, const int m
   __shared__ double shsum[4];
   double ssum = 0.0;
   nearest_chunk_scan(P, m, n, tiles_per_chunk, ntiles, points, sel, xyz, part_d2, part_k, [&](int k, size_t row3) {
-    float smin = scaling[row3];
-    int ks = 0;
-    const float s1 = scaling[row3 + 1], s2 = scaling[row3 + 2];
-    if (s1 < smin) { smin = s1; ks = 1; }
-    if (s2 < smin) { smin = s2; ks = 2; }
-    kstar[k] = ks;
+    float smin;  // (k* and the column: gsr_surfel_axis.hpp, shared with normal.hip)
+    kstar[k] = surfel_thin_index(scaling[row3], scaling[row3 + 1], scaling[row3 + 2], smin);
     ssum += (double)smin;
   });
   if (blockIdx.x == 0) {  // (uniform over the workgroup: the workgroups whose threads ran the side job)

@@ -701,6 +701,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rows"), py::arg("min_pixels") = 1, py::arg("min_weight") = 0.0, py::arg("want_n_touched") = true,
         py::arg("want_weight_sum") = true, py::arg("want_weight_max") = true, py::arg("want_mask") = true,
         py::arg("stats") = py::none());
+  n.def("blend_attributes", &nx::blend_attributes, py::arg("geom"), py::arg("binning"), py::arg("img"),
+        py::arg("attributes"), py::arg("R"), py::arg("W"), py::arg("H"));
+  n.def("surfel_normals", &nx::surfel_normals, py::arg("xyz"), py::arg("scaling"), py::arg("rotation"), py::arg("T_cw"));
+  n.def("normal_consistency_loss", &nx::normal_consistency_loss, py::arg("depth"), py::arg("acc"), py::arg("normals"),
+        py::arg("K"), py::arg("acc_min"), py::arg("lambda_"), py::arg("normal_min"),
+        py::arg("jump_rel") = std::numeric_limits<float>::infinity());
   n.def("init_gaussians", &nx::init_gaussians);
   n.def("pack_ply_rows", &nx::pack_ply_rows);
   n.def("write_ply", &nx::write_ply);

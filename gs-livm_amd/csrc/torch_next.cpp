@@ -332,6 +332,40 @@ struct LidarDepthLossFn : public torch::autograd::Function<LidarDepthLossFn> {
   }
 };
 
+struct NormalConsistencyLossFn : public torch::autograd::Function<NormalConsistencyLossFn> {
+  static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor depth, torch::Tensor acc,
+                               torch::Tensor normals, double fx, double fy, double cx, double cy, double acc_min,
+                               double normal_min, double jump_rel, double lambda) {
+    const torch::Tensor d = dev_f32(depth, "depth"), a = dev_f32(acc, "acc"), nr = dev_f32(normals, "normals");
+    if (d.dim() < 2) throw std::invalid_argument("normal_consistency_loss: [H,W] or [1,H,W] images");
+    const int64_t H = d.size(-2), W = d.size(-1);
+    if (d.numel() != H * W || a.numel() != H * W || nr.numel() != 3 * H * W)
+      throw std::invalid_argument("normal_consistency_loss: depth and acc [H,W] or [1,H,W], normals [3,H,W]");
+    torch::Tensor gd = depth.requires_grad() ? torch::empty_like(d) : torch::Tensor();
+    torch::Tensor ga = acc.requires_grad() ? torch::empty_like(d) : torch::Tensor();
+    const size_t nbytes = gsr_normal_consistency_workspace(static_cast<int>(H), static_cast<int>(W));
+    torch::Tensor ws = workspace(nbytes, d);
+    torch::Tensor out3 = torch::empty({3}, d.options());
+    check(gsr_normal_consistency_loss(static_cast<int>(H), static_cast<int>(W), fp(d), fp(a), fp(nr),
+                                      static_cast<float>(fx), static_cast<float>(fy), static_cast<float>(cx),
+                                      static_cast<float>(cy), static_cast<float>(acc_min),
+                                      static_cast<float>(normal_min), static_cast<float>(jump_rel),
+                                      static_cast<float>(lambda), out3.data_ptr<float>(), fp(gd), fp(ga),
+                                      reinterpret_cast<char*>(ws.data_ptr()), nbytes, current_stream()),
+          "gsr_normal_consistency_loss");
+    ctx->save_for_backward({gd.defined() ? gd : torch::empty({0}, d.options()),
+                            ga.defined() ? ga.view_as(acc) : torch::empty({0}, d.options())});
+    return out3[0];
+  }
+  static torch::autograd::tensor_list backward(torch::autograd::AutogradContext* ctx,
+                                               torch::autograd::tensor_list grad_outputs) {
+    const auto saved = ctx->get_saved_variables();
+    const torch::Tensor gd = saved[0], ga = saved[1], g = grad_outputs[0];
+    return {scaled(gd, g), scaled(ga, g), torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor(),
+            torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor(), torch::Tensor()};
+  }
+};
+
 struct RobustLidarDepthLossFn : public torch::autograd::Function<RobustLidarDepthLossFn> {
   static torch::Tensor forward(torch::autograd::AutogradContext* ctx, torch::Tensor depth, torch::Tensor acc,
                                torch::Tensor lidar_depth, double acc_min, double lambda, double huber_abs,
@@ -1118,6 +1152,59 @@ Contribution contribution_finish(const torch::Tensor& rows, int64_t min_pixels, 
                                 stats.defined() ? stats.data_ptr<float>() : nullptr, current_stream()),
         "gsr_contribution_finish");
   return out;
+}
+
+torch::Tensor blend_attributes(const torch::Tensor& geom, const torch::Tensor& binning, const torch::Tensor& img,
+                               const torch::Tensor& attributes, int64_t R, int64_t W, int64_t H) {
+  torch::NoGradGuard no_grad;
+  torch::Tensor at = dev_f32(attributes.detach(), "attributes");
+  if (at.dim() == 1) at = at.unsqueeze(1);
+  if (at.dim() != 2 || at.size(1) < 1 || at.size(1) > 4)
+    throw std::invalid_argument("blend_attributes: attributes is [P, C] with C in 1..4");
+  const int64_t P = at.size(0), C = at.size(1);
+  const auto int32 = [](int64_t v) { return v >= 0 && v <= 0x7fffffffLL; };
+  if (!int32(P) || !int32(R) || !int32(W) || !int32(H))
+    throw std::invalid_argument("blend_attributes: P, R, W and H are non-negative int32");
+  for (const torch::Tensor* t : {&geom, &binning, &img})
+    if (!t->defined() || !t->is_cuda() || !t->is_contiguous())
+      throw std::invalid_argument("blend_attributes: the forward's three blobs, contiguous on the device");
+  const auto blob = [](const torch::Tensor& t) { return t.numel() ? static_cast<const char*>(t.data_ptr()) : nullptr; };
+  torch::Tensor out = torch::empty({C, H, W}, at.options());
+  check(gsr_blend_attributes(static_cast<int>(P), static_cast<int>(R), static_cast<int>(W), static_cast<int>(H),
+                             static_cast<int>(C), fp(at), blob(geom), blob(binning), blob(img), fp(out),
+                             current_stream()),
+        "gsr_blend_attributes");
+  return out;
+}
+
+torch::Tensor surfel_normals(const torch::Tensor& xyz, const torch::Tensor& scaling, const torch::Tensor& rotation,
+                             const torch::Tensor& T_cw) {
+  torch::NoGradGuard no_grad;
+  const torch::Tensor x = dev_f32(xyz.detach(), "xyz"), sc = dev_f32(scaling.detach(), "scaling"),
+                      q = dev_f32(rotation.detach(), "rotation");
+  const int64_t P = x.dim() == 2 ? x.size(0) : -1;
+  if (P < 0 || x.size(1) != 3 || sc.dim() != 2 || sc.size(0) != P || sc.size(1) != 3 || q.dim() != 2 ||
+      q.size(0) != P || q.size(1) != 4)
+    throw std::invalid_argument("surfel_normals: xyz [P,3], scaling [P,3], rotation [P,4]");
+  const torch::Tensor tcw = host_rows3(T_cw, "T_cw");
+  if (tcw.numel() != 12) throw std::invalid_argument("surfel_normals: T_cw is 3x4 or 4x4");
+  torch::Tensor out = torch::empty({P, 3}, x.options());
+  check(gsr_surfel_normals(static_cast<int>(P), fp(x), fp(sc), fp(q), tcw.data_ptr<float>(), fp(out), current_stream()),
+        "gsr_surfel_normals");
+  return out;
+}
+
+torch::Tensor normal_consistency_loss(const torch::Tensor& depth, const torch::Tensor& acc,
+                                      const torch::Tensor& normals, const torch::Tensor& K, float acc_min, float lambda,
+                                      float normal_min, float jump_rel) {
+  const torch::Tensor k = host_rows3(K, "K");
+  if (k.numel() != 9) throw std::invalid_argument("normal_consistency_loss: K is 3x3");
+  const float* const kp = k.data_ptr<float>();
+  return NormalConsistencyLossFn::apply(depth, acc, normals.detach(), static_cast<double>(kp[0]),
+                                        static_cast<double>(kp[4]), static_cast<double>(kp[2]),
+                                        static_cast<double>(kp[5]), static_cast<double>(acc_min),
+                                        static_cast<double>(normal_min), static_cast<double>(jump_rel),
+                                        static_cast<double>(lambda));
 }
 
 namespace {

@@ -526,6 +526,57 @@ int gsr_surfel_plane_loss(int P, int m, int n, const float* points, const int* s
                           float lambda_flat, float* out4, float* grad_xyz, float* grad_scaling, float* grad_rotation,
                           int accumulate, char* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- rendered normal maps and the depth-normal consistency loss (an extension: the reference has neither) ----
+ * gsr_blend_attributes: a forward-only pass behind a completed gsr_forward, in gsr_contribution's shape (P, R, width,
+ * height and the three state blobs as that call takes them).  attributes [P][channels] float32, channels 1..4;
+ * out [channels][height][width] planar float32:
+ *   out[c][pixel] = sum over the splats the pixel took, front to back, of attributes[splat][c] * alpha * T
+ * with the forward's own alpha and T and its take rule (gsr_contribution), accumulated by fused multiply-adds in list
+ * order as the forward accumulates colour and depth: attributes = 1 gives the forward's acc image bit for bit, the
+ * splats' view depths its depth image, the colours (under a zero background) its colour image.  There is no background
+ * term.  EVERY element of out is written; a pixel that takes nothing reads +0.0.  Rows the forward culled are never
+ * read.  P == 0 or R == 0: legal, out is zeros written by a fill and the blobs are not read.  One launch, plain stores,
+ * no atomics: bitwise reproducible.  Profiled under k_visibility.
+ * Refused, in this order: channels outside 1..4; a negative P or R, a non-positive width or height; width * height
+ * >= 2^31; a null out, and with P, R > 0 null attributes or a null blob; attributes or out off 4-byte alignment.
+ *
+ * gsr_surfel_normals: one launch, one thread per row.  xyz [P,3], scaling [P,3] and rotation [P,4] are the ACTIVATED
+ * values as gsr_surfel_plane_loss takes them; T_cw12 is [R | t] on the HOST, row-major 3 x 4, x_c = R x_w + t.
+ *   k* and n_w = column k* of R(q): as gsr_surfel_plane_loss (lowest index on a tie, q not renormalised)
+ *   n_c = R n_w, p_c = R x + t, normals[i] = n_c, negated when n_c . p_c > 0 (exactly 0: not negated)
+ * normals [P,3]: every row is written, whatever the rasterizer's radii.  Explicit fused multiply-adds throughout.
+ * Refused, in this order: negative P; with P > 0 a null pointer; an array off 4-byte alignment.  Profiled under
+ * k_visibility.
+ *
+ * gsr_normal_consistency_loss: depth D and acc A are the rasterizer's second and third outputs [H][W], normals N is
+ * [3][H][W] = sum n_c alpha T (gsr_blend_attributes of gsr_surfel_normals), un-normalised.  fx, fy, cx, cy: the pinhole
+ * under which pixel (u, v) of a render is pixel (u, v) (cx = (W - 1) / 2 for a centred camera).  At pixel (u, v):
+ *   z = D / A,  X = ((u - cx) z / fx, (v - cy) z / fy, z);  valid: A >= acc_min (false for NaN)
+ *   supervised: 1 <= u <= W-2 and 1 <= v <= H-2; the pixel and its four neighbours valid; |z(nb) - z| <= jump_rel z for
+ *   each of the four (jump_rel = +inf: the gate is off and nothing is compared); |N| >= normal_min A; |c| > 0
+ *   a = X(u+1, v) - X(u-1, v),  b = X(u, v+1) - X(u, v-1),  c = b x a,  rho = 1 - (N / |N|) . (c / |c|)
+ *   L = lambda * sum rho / max(S, 1) over the S supervised pixels
+ * out3 (device) = {L, sum rho / S, S / (W H)}.  dL_ddepth, dL_dacc [H][W] (each nullable) for upstream gradient 1:
+ * dL/dD = g_z / A and dL/dA = -g_z D / A^2, g_z the derivative through the a and b of the pixel's four neighbours; N is
+ * data and the gates are steps.  Every element is written, zeros where nothing flows.  Images with W < 3 or H < 3 are
+ * legal: no interior, out3 = {0, 0, 0} and zero gradients.
+ * Three launches (two without gradients) on the caller's stream, no host synchronisation, no allocation, no atomics,
+ * fixed-order reductions: bitwise reproducible.  Profiled under k_lidar_loss_fwd / _finish / _grads (the id word is full).
+ * Refused, in this order: height or width < 1; width * height >= 2^31; acc_min, normal_min or lambda negative or NaN;
+ * jump_rel negative or NaN; fx or fy not positive and finite; a null depth, acc, normals, out3 or workspace; a float
+ * array off 4-byte alignment; the workspace off 8-byte alignment; workspace_bytes below the query (which returns 0 for
+ * a refused shape). */
+int gsr_blend_attributes(int P, int R, int width, int height, int channels, const float* attributes,
+                         const char* geom_buffer, const char* binning_buffer, const char* image_buffer, float* out,
+                         void* stream);
+int gsr_surfel_normals(int P, const float* xyz, const float* scaling, const float* rotation, const float* T_cw12,
+                       float* normals, void* stream);
+size_t gsr_normal_consistency_workspace(int height, int width);
+int gsr_normal_consistency_loss(int height, int width, const float* depth, const float* acc, const float* normals,
+                                float fx, float fy, float cx, float cy, float acc_min, float normal_min,
+                                float jump_rel, float lambda, float* out3, float* dL_ddepth, float* dL_dacc,
+                                char* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the delta-depth loss between a history keyframe and its successor (step 5 of optimize_vis), fused ----
  * For every SOURCE pixel (u, v) with d = depth_src[v][u]:
  *   p' = R_rel inv_K_src (u d, v d, d) + t_rel,  Z'[v][u] = p'.z,  (X, Y) = (K_ref p').xy / (K_ref p').z
